@@ -10,11 +10,18 @@ Adam, nothing skipped.  Inputs are resident in HBM before the timed region.
 
 `--gpus N` launched plainly starts N ranks itself (torch.distributed.run, 127.0.0.1).
 
-Prints ONE JSON line (rank 0) carrying `roofline` (dominant kernel: the fp32 MFMA GEMM, timed live
-with HIP events), `roofline_sparse` (the whole embedding path of the step against SURVEY 8d's bytes),
-`dcnv2` (the configs[2] step measured in the same run: the metric names both models) and
-`cpu_baseline` (the oracle's dense-semantics step — a restatement of the reference — timed on this
-box's host cores; rank 0, N=1 only).
+A plain run does what the headline needs and nothing else: build the model, age it, warm up, time
+exactly --steps steps, and print ONE JSON line (rank 0) with `value`, `ms_per_step` and the run's
+configuration.  `--dump-outputs DIR` then writes what the last timed step handed its caller (see
+dump_outputs()).
+
+`--full` adds every secondary measurement to the same line: `young_run` and `step_us` (extra timed
+passes), `roofline` (dominant kernel: the fp32 MFMA GEMM, timed live with HIP events),
+`roofline_sparse` (the whole embedding path of the step against SURVEY 8d's bytes), `dcnv2` / `din` /
+`uniform` (the configs[2] and configs[3] steps and the uniform-id DeepFM step, measured in the same
+run), `parity_full_vocab` (native vs oracle), `reference_dataloader` and `cpu_baseline` (the oracle's
+dense-semantics step — a restatement of the reference — timed on this box's host cores; rank 0, N=1
+only).  The `--no-*` switches below drop single parts of a `--full` run.
 """
 import argparse
 import json
@@ -66,7 +73,7 @@ def parse():
     ap.add_argument("--pool", type=int, default=512,
                     help="distinct synthetic batches cycled (bounded by warmup + steps + 24)")
     ap.add_argument("--no-dcnv2", action="store_true",
-                    help="skip the DCNv2 (configs[2]) sub-measurement of the default DeepFM run")
+                    help="skip the DCNv2 (configs[2]) sub-measurement of a --full DeepFM run")
     ap.add_argument("--probe-loss", action="store_true",
                     help="before the warm-up: seeded weights (by parameter NAME and global row, so any "
                          "shard layout holds the same model) and two training steps on a seeded GLOBAL "
@@ -80,25 +87,36 @@ def parse():
                          "default <repo>/.ref_checkout or /root/reference) - the true drop-in; native: "
                          "fuxictr_amd.zoo's mirrors of the same classes (what travels to the GPU box)")
     ap.add_argument("--no-step-events", action="store_true",
-                    help="skip the second pass that records one HIP event per step (step_us)")
+                    help="skip the second pass of a --full run that records one HIP event per step (step_us)")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch the step eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--age-steps", type=int, default=300,
                     help="training steps (on distinct batches) before the clock starts: the exact-mode Adam "
                          "catch-up replays the steps a row missed, so a young run is faster than the rate a "
                          "training run sustains (round 4: 0.981 vs 1.035-1.046 ms); `value` is the steady state, "
-                         "the young-run figure is reported beside it (`young_run`)")
+                         "--full reports the young-run figure beside it (`young_run`)")
     ap.add_argument("--no-uniform", action="store_true",
-                    help="skip the uniform-id measurement (`value_uniform`, SURVEY 8d: both distributions)")
+                    help="skip the uniform-id measurement of a --full run (`value_uniform`, SURVEY 8d: both "
+                         "distributions)")
     ap.add_argument("--no-din", action="store_true",
-                    help="skip the DIN (configs[3]) sub-measurement of the default DeepFM run")
+                    help="skip the DIN (configs[3]) sub-measurement of a --full DeepFM run")
     ap.add_argument("--long-parity-steps", type=int, default=400,
                     help="steps of the long native-vs-oracle trajectory (`parity_full_vocab.steps_400`: c2 with "
                          "the tables x 0.01, 131 072 hold-out rows; ~1 min); 0 skips it")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the full-vocabulary parity leg (`parity_full_vocab`: the native step against the "
-                         "oracle at 33.76 M rows, same weights, same batches)")
-    return ap.parse_args()
+                    help="skip the full-vocabulary parity leg of a --full run (`parity_full_vocab`: the native "
+                         "step against the oracle at 33.76 M rows, same weights, same batches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (young run, per-step events, per-kernel timing and "
+                         "rooflines, the DCNv2 / DIN / uniform-id legs, parity legs, reference data-loader rate, "
+                         "CPU baseline); without it the run only produces the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss and the "
+                         "trained parameters, large tables as a fixed seeded row sample) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _reference_zoo():
@@ -646,6 +664,38 @@ def gather_at_c5_batch(args, model, cards, dev, n_batches=12):
     return None
 
 
+DUMP_ROWS = 4096                # rows sampled from each table larger than this
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(model, loss, out_dir, rank):
+    """--dump-outputs: what the last timed step handed its caller — its loss and the model it trained — as
+    float32 DIR/<name>.npy.  The tables are settled first (exact mode: the zero-gradient Adam steps a row
+    still owes), as fit()'s evaluation or save_weights() would read them.  A tensor with more than DUMP_ROWS
+    rows is sampled: DUMP_ROWS sorted row indices drawn from a generator seeded by the tensor's name, so two
+    runs with the same arguments compare row for row.  Rank 0 writes (its rows of a row-sharded model)."""
+    import zlib
+    arrays = {"loss": loss.detach().reshape(-1).to(torch.float32).cpu().numpy()}
+    if hasattr(model.optimizer, "flush"):
+        model.optimizer.flush()
+    if rank != 0:
+        return
+    for k, v in model.state_dict().items():
+        if not torch.is_floating_point(v):
+            continue
+        if v.dim() >= 1 and v.shape[0] > DUMP_ROWS:
+            rng = np.random.default_rng(zlib.crc32(k.encode()))
+            idx = np.sort(rng.choice(v.shape[0], DUMP_ROWS, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        arrays[k] = v.detach().to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_BYTES_MAX))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def measure(args, rank, local_rank, world, world1, dev, dist):
     """Build args.model, warm up, time exactly args.steps steps, then the instrumented pass.
     -> dict(dt, ktimes, launch, parallelism, cards, timing_mode, rows)."""
@@ -728,7 +778,7 @@ def measure(args, rank, local_rank, world, world1, dev, dist):
                 prepare_pool()
             model.train_step(next_batch(step_i))
             step_i += 1
-        if warm_run > 20 + args.steps:
+        if args.full and warm_run > 20 + args.steps:
             sync()
             y0 = torch.cuda.Event(enable_timing=True)
             y1 = torch.cuda.Event(enable_timing=True)
@@ -784,18 +834,20 @@ def measure(args, rank, local_rank, world, world1, dev, dist):
     t0 = time.perf_counter()
     ev0.record()                 # on the launch stream (torch's current stream): first launch ...
     for _ in range(args.steps):
-        model.train_step(next_batch(step_i))
+        loss = model.train_step(next_batch(step_i))
         step_i += 1
     ev1.record()                 # ... to the end of the last kernel, without the host's sync latency
     sync()
     dt = time.perf_counter() - t0
     dt_events = 1e-3 * ev0.elapsed_time(ev1)
     model.optimizer.check_errors()
+    if args.dump_outputs and getattr(args, "dump_here", False):
+        dump_outputs(model, loss, args.dump_outputs, rank)
     # per-step spread: a SECOND pass of the same number of steps with one event per step (the events
     # cost a few us of launch boundary each, so this pass is not the headline; it shows whether the
     # mean hides a ramp or outliers)
     step_us = None
-    if not args.no_step_events:
+    if args.full and not args.no_step_events:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         sync()
         evs[0].record()
@@ -811,7 +863,7 @@ def measure(args, rank, local_rank, world, world1, dev, dist):
                    "note": "second pass of %d steps, one HIP event per step on the launch stream "
                            "(events add launch boundaries: not the headline)" % args.steps}
     timing_mode, ktimes = None, {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # Per-kernel durations cannot be observed inside a replayed hipGraph, and an event pair around
         # a single launch adds ~10 us on this platform.  So ONE eager step over the next batch of the
         # pool is RECORDED (every native entry point with its live arguments) and each recorded launch
@@ -1174,9 +1226,11 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
 
+    args.dump_here = True            # the headline leg writes --dump-outputs; the --full legs below do not
     m = measure(args, rank, local_rank, world, world1, dev, dist)
+    args.dump_here = False
     second = None
-    if (args.model == "DeepFM" and world == 1 and not world1 and not args.no_dcnv2
+    if (args.full and args.model == "DeepFM" and world == 1 and not world1 and not args.no_dcnv2
             and not args.loader and not args.host_inputs):
         # BASELINE.json's metric names both models: the c3 DCNv2 step (CrossNet 624x624 GEMMs) is
         # measured in the same run and reported as a sub-object of the same line
@@ -1186,7 +1240,7 @@ def main():
         m2 = measure(args2, rank, local_rank, world, world1, dev, dist)
         second = (args2, m2)
     fourth = None
-    if (args.model == "DeepFM" and world == 1 and not world1 and not args.no_din
+    if (args.full and args.model == "DeepFM" and world == 1 and not world1 and not args.no_din
             and not args.loader and not args.host_inputs and args.zoo == "native"):
         # configs[3]: DIN on the synthetic Taobao-shape sequence schema (seq_len 50), same protocol
         import copy
@@ -1194,8 +1248,8 @@ def main():
         args4.model = "DIN"
         fourth = (args4, measure(args4, rank, local_rank, world, world1, dev, dist))
     third = None
-    if (args.model == "DeepFM" and world == 1 and not world1 and not args.no_uniform and args.dist == "powerlaw"
-            and not args.loader and not args.host_inputs):
+    if (args.full and args.model == "DeepFM" and world == 1 and not world1 and not args.no_uniform
+            and args.dist == "powerlaw" and not args.loader and not args.host_inputs):
         import copy
         args3 = copy.copy(args)
         args3.dist, args3.no_kernel_timing, args3.no_step_events = "uniform", True, True
@@ -1236,7 +1290,8 @@ def main():
                        "parallelism": m["parallelism"]},
         }
         out.update(timing_detail(m, args))
-        out.update(rooflines(m, args, world))
+        if args.full:
+            out.update(rooflines(m, args, world))
         if m.get("probe") is not None:
             out["probe_loss"] = m["probe"]
             out.update(PROBE_EXTRA)
@@ -1264,7 +1319,7 @@ def main():
                               "warmup_steps_run": m3["warmup_run"],
                               "note": "the same DeepFM step on UNIFORM ids (SURVEY 8d: both distributions): "
                                       "~106 K unique rows per batch instead of ~25 K"}
-        if world == 1 and not args.no_parity and not world1 and args.model in ("DeepFM", "DCNv2") \
+        if args.full and world == 1 and not args.no_parity and not world1 and args.model in ("DeepFM", "DCNv2") \
                 and args.vocab_scale == 1.0 and args.zoo == "native":
             out["parity_full_vocab"] = {}
             for case in (("c2_deepfm", "c3_dcnv2") if args.model == "DeepFM" and not args.no_dcnv2 else
@@ -1278,9 +1333,9 @@ def main():
                                                                   max(1, args.long_parity_steps // 2),
                                                                   args.long_parity_steps})))
                 out["parity_full_vocab"]["steps_%d" % args.long_parity_steps] = r
-        if world == 1 and not world1:
+        if args.full and world == 1 and not world1:
             out["reference_dataloader"] = reference_dataloader_rate(args)
-        if world == 1 and not args.no_cpu_baseline and args.model in ("DeepFM", "DCNv2"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model in ("DeepFM", "DCNv2"):
             out["cpu_baseline"] = cpu_baseline(args, m["cards"], args.cpu_baseline_steps)
         assert out["n_gpus"] == args.gpus
         _emit(json.dumps(out))

@@ -9,8 +9,8 @@ timeout 2400 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider 
 echo "pytest exit $?" | tee -a $S
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/pytest_gpu_$TAG.log | tail -20 | tee -a $S
 grep -E "^E  " $OUT/pytest_gpu_$TAG.log | head -20 | cut -c1-300 | tee -a $S
-echo "== python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command)" | tee -a $S
-T0=$(date +%s); timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_settings_final.json 2> $OUT/bench_$TAG.err
+echo "== python bench.py --gpus 1 --steps 20 --warmup 5 --full (the driver's command with every leg)" | tee -a $S
+T0=$(date +%s); timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_driver_settings_final.json 2> $OUT/bench_$TAG.err
 echo "exit $? wall $(( $(date +%s) - T0 )) s" | tee -a $S
 python - $OUT/${TAG}_bench_driver_settings_final.json <<'PY' | tee -a $S
 import json, sys
@@ -35,7 +35,7 @@ print("cpu_baseline:", round(d["cpu_baseline"]["value"]), "samples/s on", d["cpu
 PY
 echo "== other models (50 steps, steady state)" | tee -a $S
 for M in DIN DLRM xDeepFM; do
-  timeout 600 python bench.py --model $M --steps 50 --warmup 10 --no-cpu-baseline > $OUT/${TAG}_bench_${M}_final.json 2>> $OUT/bench_$TAG.err
+  timeout 600 python bench.py --model $M --steps 50 --warmup 10 --full --no-cpu-baseline > $OUT/${TAG}_bench_${M}_final.json 2>> $OUT/bench_$TAG.err
   python -c "import json; d=json.load(open('$OUT/${TAG}_bench_${M}_final.json')); print('$M', round(d['value']), 'samples/s', round(d['ms_per_step'],4), 'ms steady (young', d.get('young_run',{}).get('ms_per_step'), ')', {k: round(v['frac'],3) for k,v in d.items() if k.startswith('roofline') and isinstance(v, dict) and 'frac' in v})" | tee -a $S
 done
 echo "== row-sharded step on one RCCL rank" | tee -a $S

@@ -3,7 +3,7 @@
 TAG=$1
 REPO=$PWD; OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 for M in ${MODELS:-DIN DLRM xDeepFM}; do
-  timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-dcnv2 --model $M > $OUT/bench_${TAG}_$M.json 2> $OUT/bench_${TAG}_$M.err
+  timeout 600 python bench.py --steps 50 --warmup 10 --full --no-cpu-baseline --no-dcnv2 --model $M > $OUT/bench_${TAG}_$M.json 2> $OUT/bench_${TAG}_$M.err
   python - $OUT/bench_${TAG}_$M.json $M <<'PY'
 import json, sys
 try:

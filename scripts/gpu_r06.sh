@@ -17,7 +17,7 @@ if [ -n "$AB" ]; then
   for R in $(seq 1 $REPS); do
     for V in A B; do
       if [ $V = A ]; then E="$A"; else E="$B"; fi
-      env $E timeout 400 python bench.py --model $MODEL --steps 100 --warmup 10 --no-cpu-baseline --no-dcnv2 --no-din --no-parity --no-uniform 2>$OUT/ab_$TAG.err | head -1 > $OUT/ab_tmp.json
+      env $E timeout 400 python bench.py --model $MODEL --steps 100 --warmup 10 --full --no-cpu-baseline --no-dcnv2 --no-din --no-parity --no-uniform 2>$OUT/ab_$TAG.err | head -1 > $OUT/ab_tmp.json
       python - "$V [$E]" $OUT/ab_tmp.json <<'PY' | tee -a $S
 import json, sys
 try:

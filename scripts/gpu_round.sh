@@ -15,7 +15,7 @@ timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider 
 echo "pytest exit $?" | tee -a $OUT/summary_$TAG.txt
 tail -40 $OUT/pytest_gpu_$TAG.log | tee -a $OUT/summary_$TAG.txt
 echo "== bench" | tee -a $OUT/summary_$TAG.txt
-timeout 900 python bench.py --steps $STEPS --warmup 10 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout 900 python bench.py --steps $STEPS --warmup 10 --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "bench exit $?" | tee -a $OUT/summary_$TAG.txt
 cat $OUT/bench_$TAG.json | tee -a $OUT/summary_$TAG.txt
 tail -5 $OUT/bench_$TAG.err | tee -a $OUT/summary_$TAG.txt

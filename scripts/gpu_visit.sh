@@ -14,7 +14,7 @@ if [ -n "$PYT" ]; then
   grep -E "^E  " $OUT/pytest_$TAG.log | head -30 | cut -c1-400 | tee -a $S
 fi
 echo "== bench $@" | tee -a $S
-timeout 900 python bench.py --steps 50 --warmup 10 "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout 900 python bench.py --steps 50 --warmup 10 --full "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "bench exit $?" | tee -a $S
 python - $OUT/bench_$TAG.json <<'PY' | tee -a $S
 import json, sys

@@ -20,6 +20,11 @@ def _shutdown(model):
     from fuxictr_amd.dist import DistContext
     DistContext.shutdown([model])
 
+def _model_root(out_path, rank):
+    """This rank's model_root, in the calling test's own temporary directory (beside its output)."""
+    return os.path.join(os.path.dirname(os.path.abspath(out_path)), "model_root_rank%d" % rank)
+
+
 def run_c5(rank, world, port, out_path):
     """configs[4] in miniature: the c5 DLRM (bottom [512,256,16], dot, top [1024,1024,512,256],
     26 tables with the Criteo-skewed split) row-sharded over `world` ranks, each rank on its slice of
@@ -33,7 +38,7 @@ def run_c5(rank, world, port, out_path):
     import baseline_shapes as BS
     from fuxictr_amd import zoo
     from oracle import ctr_oracle as O
-    model, features, cfg, spec, cards = BS.build("c5_dlrm", zoo, -1, "/tmp/fx_dist_c5_%d" % rank,
+    model, features, cfg, spec, cards = BS.build("c5_dlrm", zoo, -1, _model_root(out_path, rank),
                                                  vocab_scale=0.0005, shard="row")
     # identical on every rank (tables all-gathered); cloned: the dense entries are live views
     state0 = {k: v.detach().clone() for k, v in model.full_state_dict().items()}
@@ -97,7 +102,7 @@ def run(rank, world, case, port, out_path, use_gpu):
     common = dict(gpu=0 if use_gpu else -1, embedding_dim=m["embedding_dim"],
                   learning_rate=m["lr"], optimizer=m["optimizer"], loss="binary_crossentropy",
                   task="binary_classification", metrics=["logloss", "AUC"], verbose=0,
-                  model_root="/tmp/fx_dist_%d" % rank, shard="row",
+                  model_root=_model_root(out_path, rank), shard="row",
                   embedding_regularizer=m.get("emb_reg", 0), net_regularizer=m.get("net_reg", 0),
                   hip_graph=os.environ.get("FX_HIP_GRAPH", "0") == "1")
     if m["model"] == "DeepFM":
