@@ -33,10 +33,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FX_CIN_WAVES 8        // waves per workgroup (512 threads, 2 per SIMD)
 
 static int fx_cin_mfma_mode() {     // FX_CIN_MFMA=0: the VALU kernels everywhere (A/B runs)
-    static const int mode = []() {
-        const char* e = getenv("FX_CIN_MFMA");
-        return e ? atoi(e) : 1;
-    }();
+    static const int mode = fx_env_int("FX_CIN_MFMA", 1);
     return mode;
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/fxctr.h"
@@ -35,6 +36,14 @@ void fx_set_error(const char* fmt, ...);
 static inline hipStream_t fx_hip_stream(fx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int64_t fx_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// An experiment switch FX_... of the environment: `dflt` when unset, atoi of its text otherwise (so anything
+// that is no number reads as 0).  Callers keep the value in a function-local `static const`: one read per
+// process.
+static inline int fx_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // ---- fx_sort.hip: device-wide stable LSD radix sort of (uint32 key, uint32 value) pairs --------
 size_t fx_sort_temp_bytes(int64_t n);

@@ -446,10 +446,7 @@ size_t fx_dedup_buckets_bytes(int64_t n) {
 }
 
 bool fx_dedup_buckets_ok(int64_t n) {
-    static const bool on = []() {
-        const char* e = getenv("FX_DEDUP_BUCKETS");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = fx_env_int("FX_DEDUP_BUCKETS", 1) != 0;
     // 256 buckets x 8192 pairs in LDS; the partition reads nblk x 256 tile counts per workgroup
     return on && n > 0 && n <= (int64_t)BK_NB * BK_TILE;
 }

@@ -1503,10 +1503,7 @@ static void da_fill(DinAttnArgs& a, const float* q, int64_t q_ld, const float* K
 
 // the q-split formulation: E = 8 / 16 with 16-byte rows, L >= 32 (FX_DIN_ATTN_QSPLIT=0: never)
 static bool da2_ok(const DinAttnArgs& a) {
-    static const bool on = []() {
-        const char* e = getenv("FX_DIN_ATTN_QSPLIT");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = fx_env_int("FX_DIN_ATTN_QSPLIT", 1) != 0;
     return on && a.vec && (a.E == 16 || a.E == 8) && a.L >= 32;
 }
 #define DA2_LAUNCH(KERNEL, THREADS, GRID, STREAM, ARGS)                                            \

@@ -719,10 +719,8 @@ __global__ __launch_bounds__(256) void k_dot_interact_bwd_mfma(const float* emb,
 }
 
 static bool fx_dot_mfma_ok(int F, int D) {
-    static const bool on = []() {   // FX_DOT_MFMA=0: the workgroup-per-sample kernels (A/B runs)
-        const char* e = getenv("FX_DOT_MFMA");
-        return !(e && atoi(e) == 0);
-    }();
+    // FX_DOT_MFMA=0: the workgroup-per-sample kernels (A/B runs)
+    static const bool on = fx_env_int("FX_DOT_MFMA", 1) != 0;
     return on && F <= 32 && D <= 32 && D % 2 == 0;
 }
 

@@ -261,10 +261,8 @@ __device__ __forceinline__ void fx_catchup_quad(const FxTableDev& t0, const FxTa
     }
 }
 
-static const bool fx_catchup_quad_on = []() {     // FX_CATCHUP_QUAD=0: the two plain replays (A/B runs)
-    const char* e = getenv("FX_CATCHUP_QUAD");
-    return !(e && atoi(e) == 0);
-}();
+// FX_CATCHUP_QUAD=0: the two plain replays (A/B runs)
+static const bool fx_catchup_quad_on = fx_env_int("FX_CATCHUP_QUAD", 1) != 0;
 
 // one unique row of a de-dup result, in every table group that shares the id plan
 __device__ __forceinline__ void fx_catchup_tables(const FxTableDev* t, int n_tables, int64_t row,
@@ -646,10 +644,7 @@ extern "C" int fx_dedup_catchup(const int32_t* ids, int64_t ids_ld, int64_t B, i
     // the scan / scatter launch, as in round 2): there a lane group exists per LOOKUP and only the 24 % that
     // head a run have a row to replay — 99 % of the waves walked the row path with a quarter of their
     // lanes; over the compacted rows every lane works (profiles/r03_sparse_ab.txt).
-    static const bool split = []() {
-        const char* e = getenv("FX_SPLIT_CATCHUP");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool split = fx_env_int("FX_SPLIT_CATCHUP", 1) != 0;
     const bool two = split && n_tables > 0;
     fa.n_tables = two ? 0 : n_tables;
     fa.group_log2 = two ? 0 : gl;
@@ -989,8 +984,7 @@ extern "C" int fx_emb_fm_fwd(const void* table, int32_t table_dtype, int32_t D, 
     hipStream_t s = fx_hip_stream(stream);
     // A/B switch, read per call so that a test can compare the two forms in one process:
     // FX_EMB_FWD2=0 = the first version for every shape
-    const char* e2 = getenv("FX_EMB_FWD2");
-    const bool v2 = !(e2 && atoi(e2) == 0);
+    const bool v2 = fx_env_int("FX_EMB_FWD2", 1) != 0;
     const int ngrp = 64 / g.lanes;
     const int ni = (int)fx_ceil_div(C + Fd, ngrp);
     if (v2 && C <= 64 && Fd <= 64 && ni <= 4) {

@@ -1,6 +1,8 @@
-// fx_gemm_int.h — definitions shared by the two GEMM translation units of libfxctr (internal, not part of
-// the C ABI): fx_gemm.hip (fp32 MFMA kernels, skinny kernels, dispatch) and fx_gemm_x6.hip (the split-bf16
-// kernels).  Everything here used to live at the top of fx_gemm.hip.
+// fx_gemm_int.h — definitions shared by the GEMM translation units of libfxctr (internal, not part of the
+// C ABI): fx_gemm.hip (host only: validation, planning, dispatch), fx_gemm_tile.hip (the fp32-MFMA tile
+// kernels), fx_gemm_x6.hip (the split-bf16 kernels), fx_gemm_skinny.hip (K <= 8 / N <= 4 / M <= 4 and the
+// fused head backward) and fx_gemm_reduce.hip (the split-K slab reduces).  A kernel is launched only from
+// the unit that defines it: the units export the host launchers declared at the end of this file.
 #pragma once
 #include "fx_common.h"
 
@@ -101,6 +103,44 @@ struct MultiArgs {
     int32_t n;
 };
 
+// ---- fx_gemm_tile.hip -------------------------------------------------------------------------------
+// the 16-byte epilogue (TR) applies: every vector access of the epilogue / the slab stores is aligned
+bool fx_gemm_tr_ok(const GemmArgs& a);
+// `a` prepared by fx_gemm_prepare with tiles_m / tiles_n counted in bm x bn tiles (128x128 | 128x64 | 64x64).
+// pipe: the software-pipelined kernel (operands must pass fx_gemm_pipe_ok); plain: k_gemm_f32, av / bv =
+// 16-byte loads of op(A) / op(B) are possible
+int fx_gemm_tile_launch_pipe(int bm, int bn, bool a_kc, bool b_kc, const GemmArgs& a, hipStream_t s);
+void fx_gemm_tile_launch_plain(int bm, int bn, bool a_kc, bool b_kc, bool av, bool bv, const GemmArgs& a,
+                               hipStream_t s);
+// two problems on 64x64 tiles in one grid (k_gemm_f32_pair), the first one's workgroups first.  bwd: dW = dZ^T X
+// (m- / n-contiguous operands) and dX = dZ W; fwd: two x W^T products (16-byte epilogue, no K split)
+void fx_gemm_tile_launch_pair_bwd(const GemmArgs& dw, const GemmArgs& dx, hipStream_t s);
+void fx_gemm_tile_launch_pair_fwd(const GemmArgs& first, const GemmArgs& second, hipStream_t s);
+// cfg[i] bit 0: A k-contiguous, bit 1: B k-contiguous, bit 2: 128x64 tile (else 128x128)
+void fx_gemm_tile_launch_multi(const MultiArgs& ma, int64_t workgroups, hipStream_t s);
+
+// ---- fx_gemm_reduce.hip -----------------------------------------------------------------------------
+// C = epilogue(sum of the a.split_k slabs of a.ws) (+ the fused row sums); the caller checks the launch
+void fx_launch_splitk_reduce(const GemmArgs& a, hipStream_t s);
+// the same for every split-K problem of p[0 .. n): one launch where two or more take the vector kernel
+void fx_launch_splitk_reduces(const GemmArgs* p, int n, hipStream_t s);
+
+// ---- fx_gemm_skinny.hip -----------------------------------------------------------------------------
+// K <= 8, N <= 4 with op(A) = A, or M <= 4 with A^T B and a workspace: the bandwidth-bound kernels
+bool fx_gemm_is_skinny(int32_t transa, int32_t transb, int64_t M, int64_t N, int64_t K, const void* workspace);
+// launches a prepared problem if it is skinny (-> true, *rc = FX_OK or the error); false: not skinny
+bool fx_gemm_skinny_launch(int32_t transa, int32_t transb, GemmArgs& a, hipStream_t s, int* rc);
+// backward of a Linear(hidden -> 1) head in one pass (k_head_bwd_v4)
+struct HeadBwdArgs {
+    GemmArgs dw;          // A = dz [K, 1] (lda), B = x [K, N] (ldb), ws slabs, rowsum
+    float* dx;            // [K, N] (ldx)
+    int64_t ldx;
+    const float* w;       // [N]
+    int32_t use_mask;
+};
+// h.dw as fx_gemm_prepare left it: the K split of the skinny weight gradient is settled here, by the rule of
+// fx_gemm_skinny_launch.  Launches the kernel and its slab reduce.
+int fx_head_bwd_launch(HeadBwdArgs& h, hipStream_t s);
 
 // ---- fx_gemm_x6.hip ---------------------------------------------------------------------------------
 // fp32-accurate GEMM on the bf16 matrix cores (operands split into three exact bf16 planes inside the

@@ -1,5 +1,5 @@
 // fx_gemm_x6.hip — fp32-accurate GEMM on the CDNA4 bf16 matrix cores ("bf16 x 6"), operands split INSIDE the
-// kernel.  Same products as fx_gemm.hip's fp32-MFMA kernels:
+// kernel.  Same products as fx_gemm_tile.hip's fp32-MFMA kernels:
 //   fuxictr/pytorch/layers/blocks/mlp_block.py:96            (Linear -> ReLU stack: x W^T + b)
 //   fuxictr/pytorch/layers/interactions/cross_net.py:126-129 (X_{i+1} = X_i + X_0 * (W X_i + b))
 // and their autograd (dX = dZ W, dW = dZ^T X, db = colsum dZ) triggered at rank_model.py:320.
@@ -435,7 +435,7 @@ void k_gemm_x6_multi(MultiArgs a) {
     int i = 0;
     while (i + 1 < a.n && (int32_t)blockIdx.x >= a.start[i + 1]) ++i;
     // (arguments through the kernarg segment pointer: indexing the by-value struct with a run-time index
-    // makes the compiler copy it to scratch — fx_gemm.hip, k_gemm_f32_multi)
+    // makes the compiler copy it to scratch — fx_gemm_tile.hip, k_gemm_f32_multi)
     const MultiArgs* ka = (const MultiArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     const GemmArgs& g = ka->p[i];
     int64_t L = (int64_t)blockIdx.x - a.start[i];
@@ -451,10 +451,7 @@ void k_gemm_x6_multi(MultiArgs a) {
 }
 
 bool fx_gemm_x6_enabled() {
-    static const bool on = []() {
-        const char* e = getenv("FX_GEMM_BF16X6");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = fx_env_int("FX_GEMM_BF16X6", 1) != 0;
     return on;
 }
 

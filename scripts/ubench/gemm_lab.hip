@@ -1,5 +1,5 @@
 // gemm_lab.hip — stand-alone bench / timeline / correctness harness around the PRODUCTION GEMM source
-// (fuxictr_amd/csrc/fx_gemm.hip is #included with FX_GEMM_LAB, which adds per-workgroup timestamps).
+// (the GEMM units of fuxictr_amd/csrc/ are #included with FX_GEMM_LAB, which adds per-workgroup timestamps).
 // No torch: starts in a second on the GPU box.  Kernel switches are the library's own environment
 // variables (FX_GEMM_TILE, FX_GEMM_TR, FX_GEMM_W64, FX_GEMM_PAIR ...), read once per process — run one
 // process per configuration.
@@ -7,6 +7,9 @@
 //               scripts/ubench/gemm_lab.hip -o scripts/ubench/gemm_lab
 //   run:    gemm_lab [suite] [--trace] [--check]      suite = tower | cross | ksweep | all
 #define FX_GEMM_LAB 1
+#include "../../fuxictr_amd/csrc/fx_gemm_tile.hip"
+#include "../../fuxictr_amd/csrc/fx_gemm_reduce.hip"
+#include "../../fuxictr_amd/csrc/fx_gemm_skinny.hip"
 #include "../../fuxictr_amd/csrc/fx_gemm.hip"
 #include "../../fuxictr_amd/csrc/fx_gemm_x6.hip"     // (round 5: fx_gemm.hip dispatches into it; FX_GEMM_BF16X6=0 keeps the lab on the fp32 kernels)
 

@@ -1,4 +1,4 @@
-"""The k-loop body selection of the pipelined GEMM (fx_gemm.hip, fx_gemm_pipe_tile) must not change a
+"""The k-loop body selection of the pipelined GEMM (fx_gemm_tile.hip, fx_gemm_pipe_tile) must not change a
 single bit: tiles on the M / N edge on the unmasked bodies (FX_GEMM_EDGE_PLAIN=1, the round-4 default)
 against the masked bodies wherever an edge is near (=0, rounds 1-3).  The switch is read once per
 process: one subprocess per setting, the outputs compared bit for bit — on the shapes where edges matter (the 624-wide record:
