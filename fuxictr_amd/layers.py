@@ -2829,6 +2829,83 @@ class CrossNetV2(nn.Module):
         return _CrossNetV2Fn.apply(X_0, *wb)
 
 
+class _MHSAFn(torch.autograd.Function):
+    """One self-attention layer over the fields as ONE autograd node (AutoInt.py:157-191): forward one
+    launch, backward two (ops.mhsa_fwd / mhsa_bwd).  Kept for the backward: the layer's output (the ReLU
+    mask), nothing else; Q, K, V and the attention weights are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, num_heads, use_scale, residual, relu, W_q, W_k, W_v, W_res):
+        if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
+            x = x.contiguous()         # (a prefix of the gather record — fewer fields, same rows — is read in place)
+        B, F, _ = x.shape
+        A = W_q.shape[0]
+        y = torch.empty(B, F, A, dtype=torch.float32, device=x.device)
+        ops.mhsa_fwd(x, W_q, W_k, W_v, W_res, num_heads, use_scale, residual, relu, y)
+        ctx.x, ctx.y = x, (y if relu else None)
+        ctx.w = (W_q, W_k, W_v, W_res)
+        ctx.cfg = (num_heads, use_scale, residual, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, (W_q, W_k, W_v, W_res) = ctx.x, ctx.w
+        num_heads, use_scale, residual, relu = ctx.cfg
+        B, F, D = x.shape
+        A = W_q.shape[0]
+        n_w = 4 if W_res is not None else 3
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        dW = torch.empty(n_w, A, D, dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(x.device, ops.mhsa_workspace_floats(B, D, A, W_res is not None), tag="mhsa")
+        ops.mhsa_bwd(x, W_q, W_k, W_v, W_res, num_heads, use_scale, residual, relu, ctx.y,
+                     dy.contiguous(), dx, dW, ws)
+        return (dx, None, None, None, None, dW[0], dW[1], dW[2], dW[3] if n_w == 4 else None)
+
+
+class MultiHeadSelfAttention(nn.Module):
+    """The interaction layer of AutoInt (model_zoo/AutoInt/src/AutoInt.py:122-191): same constructor, same
+    parameter containers (`W_q`, `W_k`, `W_v`, `W_res`, `layer_norm`) and keys; the arithmetic is fx_mhsa_*.
+    X: [batch, fields, input_dim] -> [batch, fields, attention_dim]."""
+
+    def __init__(self, input_dim, attention_dim=None, num_heads=1, dropout_rate=0., use_residual=True,
+                 use_scale=False, layer_norm=False):
+        nn.Module.__init__(self)
+        width = input_dim if attention_dim is None else attention_dim
+        if dropout_rate > 0:
+            raise NotImplementedError("MultiHeadSelfAttention(dropout_rate > 0): dropout on the attention "
+                                      "probabilities is outside the fused kernel's scope")
+        for what, n in (("input_dim", input_dim), ("attention_dim", width)):
+            if not 1 <= n <= ops.MHSA_MAX:
+                raise NotImplementedError("MultiHeadSelfAttention: {}={}, the fused kernel's limit is "
+                                          "{} <= {}".format(what, n, what, ops.MHSA_MAX))
+        if num_heads < 1 or width % num_heads:
+            raise ValueError("MultiHeadSelfAttention: {} heads do not split an attention width of {} evenly"
+                             .format(num_heads, width))
+        dev = _alloc_device()
+        self.num_heads, self.head_dim = num_heads, width // num_heads
+        self.use_scale, self.use_residual = bool(use_scale), bool(use_residual)
+
+        def projection():
+            return nn.Linear(input_dim, width, bias=False, device=dev)
+        self.W_q, self.W_k, self.W_v = projection(), projection(), projection()
+        # a projected residual only where the widths differ; equal widths add X itself
+        self.W_res = projection() if (self.use_residual and input_dim != width) else None
+        self.layer_norm = nn.LayerNorm(width, device=dev) if layer_norm else None
+
+    def forward(self, X):
+        if X.dim() != 3 or X.shape[1] > ops.MHSA_MAX:
+            raise NotImplementedError("MultiHeadSelfAttention: input {}, the fused kernel takes [batch, "
+                                      "fields <= {}, dim]".format(tuple(X.shape), ops.MHSA_MAX))
+        # with a LayerNorm between the residual and the ReLU the kernel stops before its ReLU
+        fused_relu = self.layer_norm is None
+        out = _MHSAFn.apply(X, self.num_heads, self.use_scale, self.use_residual, fused_relu,
+                            self.W_q.weight, self.W_k.weight, self.W_v.weight,
+                            self.W_res.weight if self.W_res is not None else None)
+        if not fused_relu:
+            out = self.layer_norm(out).relu()
+        return out
+
+
 
 def link_fusion(model):
     """Called by BaseModel.compile(): tell the model's embedding layer which LogisticRegression

@@ -1015,6 +1015,52 @@ def cin_bwd(X0, Xi, W, dXn, dpool, dX0, accumulate_dx0, dXi, partial, w_img=None
           "fx_cin_bwd")
 
 
+# ---- multi-head self-attention over the fields (AutoInt) -------------------------------------------
+MHSA_MAX = 64        # F, D_in, A of fx_mhsa_*
+
+
+def _mhsa_flops(X, Wq, *a, **kw):
+    # per sample: 3 (+1) projections 2 F D A each, scores and P V 2 F F A each
+    B, F, D = X.shape
+    A = Wq.shape[0]
+    return 2.0 * B * F * A * (3 * D + 2 * F)
+
+
+def mhsa_workspace_floats(B, D_in, A, has_wres):
+    return int(_lib.load().fx_mhsa_workspace_floats(B, D_in, A, 1 if has_wres else 0))
+
+
+def _mhsa_x(X):
+    """X [B, F, D] as the kernels address it: unit stride over d, D over f, any sample stride."""
+    assert X.dim() == 3 and X.stride(2) == 1 and (X.shape[1] == 1 or X.stride(1) == X.shape[2])
+    return X.stride(0) if X.shape[0] > 1 else X.shape[1] * X.shape[2]
+
+
+@_timed("mhsa_fwd", "mhsa", _mhsa_flops)
+def mhsa_fwd(X, Wq, Wk, Wv, Wres, H, use_scale, residual, relu, Y):
+    """One self-attention layer: Y [B, F, A] contiguous."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    check(_lib.load().fx_mhsa_fwd(ptr(X), _mhsa_x(X), B, F, D, ptr(Wq), ptr(Wk), ptr(Wv), ptr(Wres),
+                                  Wq.shape[0], H, 1 if use_scale else 0, 1 if residual else 0,
+                                  1 if relu else 0, ptr(Y), stream_ptr(X.device)), "fx_mhsa_fwd")
+    return Y
+
+
+@_timed("mhsa_bwd", "mhsa", lambda *a, **kw: 3.0 * _mhsa_flops(*a, **kw))   # recompute + dX + dW passes
+def mhsa_bwd(X, Wq, Wk, Wv, Wres, H, use_scale, residual, relu, Y, dY, dX, dW, workspace,
+             dx_accumulate=False):
+    """dX [B, F, D] (sample stride free), dW [3 | 4, A, D] = dWq | dWk | dWv (| dWres); dY contiguous."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    check(_lib.load().fx_mhsa_bwd(ptr(X), _mhsa_x(X), B, F, D, ptr(Wq), ptr(Wk), ptr(Wv), ptr(Wres),
+                                  Wq.shape[0], H, 1 if use_scale else 0, 1 if residual else 0,
+                                  1 if relu else 0, ptr(Y), ptr(dY), ptr(dX), _mhsa_x(dX),
+                                  1 if dx_accumulate else 0, ptr(dW), ptr(workspace),
+                                  stream_ptr(X.device)), "fx_mhsa_bwd")
+    return dX, dW
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

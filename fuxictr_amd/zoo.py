@@ -1,8 +1,8 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
-model_zoo/xDeepFM/src/xDeepFM.py:41-97), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -14,13 +14,13 @@ from torch import nn
 
 from .layers import (CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FxLinear,
-                     InnerProductInteraction, LogisticRegression, MLP_Block, _DlrmMixFn, _MLP_PAD,
-                     _RecordGradSlot, din_record_layout)
+                     InnerProductInteraction, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
+                     _DlrmMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
 from .rank_model import BaseModel
 
 
 class _ZooModel(BaseModel):
-    """Shared plumbing of the five models: base-class construction and the closing
+    """Shared plumbing of the models: base-class construction and the closing
     compile / reset_parameters / model_to_device sequence every model_zoo ctor ends with."""
 
     def _base(self, feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs):
@@ -310,6 +310,42 @@ class xDeepFM(_ZooModel):
         emb = self.embedding_layer(X)
         # linear part + explicit interactions (+ implicit ones): the sums ride in the GEMM epilogues
         logit = self.cin(emb, out_add=self.lr_layer(X))
+        if self.dnn is not None:
+            logit = self.dnn(emb.flatten(start_dim=1), out_add=logit)
+        return {"y_pred": self.output_activation(logit)}
+
+
+class AutoInt(_ZooModel):
+    def __init__(self, feature_map, model_id="AutoInt", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[64, 64, 64], dnn_activations="ReLU", attention_layers=2, num_heads=1,
+                 attention_dim=8, net_dropout=0, batch_norm=False, layer_norm=False, use_scale=False,
+                 use_wide=False, use_residual=True, embedding_regularizer=None, net_regularizer=None,
+                 **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        if feature_map.num_fields > 64:
+            raise NotImplementedError("AutoInt: {} fields, the fused self-attention takes fields <= 64"
+                                      .format(feature_map.num_fields))
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.lr_layer = LogisticRegression(feature_map, use_bias=False) if use_wide else None
+        self.dnn = self._tower(feature_map.sum_emb_out_dim(), dnn_hidden_units, dnn_activations,
+                               net_dropout, batch_norm) if dnn_hidden_units else None
+        # (AutoInt.py:89 hands net_dropout to the attention layers as well: > 0 raises there)
+        self.self_attention = nn.Sequential(
+            *[MultiHeadSelfAttention(embedding_dim if i == 0 else attention_dim,
+                                     attention_dim=attention_dim, num_heads=num_heads,
+                                     dropout_rate=net_dropout, use_residual=use_residual,
+                                     use_scale=use_scale, layer_norm=layer_norm)
+              for i in range(attention_layers)])
+        self.fc = FxLinear(feature_map.num_fields * attention_dim, 1, device=self.device)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # [B, F, D]
+        attended = self.self_attention(emb)                 # [B, F, A]
+        # wide part + attention head (+ deep tower): the sums ride in the GEMM epilogues
+        logit = self.lr_layer(X) if self.lr_layer is not None else None
+        logit = self.fc(attended.flatten(start_dim=1), out_add=logit)
         if self.dnn is not None:
             logit = self.dnn(emb.flatten(start_dim=1), out_add=logit)
         return {"y_pred": self.output_activation(logit)}

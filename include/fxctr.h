@@ -657,6 +657,33 @@ int fx_cin_bwd(const float* X0, int64_t x0_ld, int32_t F0, const float* Xi, int6
                int64_t B, const float* w_img, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AutoInt's multi-head self-attention over the fields of a sample, one layer per launch
+ * (MultiHeadSelfAttention.forward, model_zoo/AutoInt/src/AutoInt.py:157-191, and ScaledDotProductAttention,
+ * fuxictr/pytorch/layers/attentions/dot_product_attention.py:48-58; their autograd at rank_model.py:320):
+ *     Q = X Wq^T, K = X Wk^T, V = X Wv^T          X: [B, F, D_in] (sample stride x_ld), W*: [A, D_in]
+ *     per head h (head_dim = A / H): P = softmax_rows(Q_h K_h^T (/ sqrt(head_dim) when use_scale)); O_h = P V_h
+ *     Y = concat_h(O_h) (+ X Wres^T when residual and Wres, + X when residual and Wres == NULL: D_in == A)
+ *     Y = relu(Y) when relu                        Y: [B, F, A] contiguous
+ * Neither Q / K / V nor the [B, H, F, F] scores reach memory; all the forward leaves for the backward is Y (the
+ * ReLU mask; Y may be NULL when relu == 0).
+ *   fx_mhsa_bwd : from dY [B, F, A]: dX [B, F, D_in] (sample stride dx_ld; added to when dx_accumulate) and
+ *                 dW = [dWq | dWk | dWv (| dWres)], each [A, D_in]; Q, K, V and P are recomputed.  The weight
+ *                 gradients are summed per workgroup, written to workspace and reduced in a fixed order by a
+ *                 second launch (deterministic, no atomics).
+ * workspace: fx_mhsa_workspace_floats(B, D_in, A, Wres != NULL) floats.
+ * Limits: F <= 64, D_in <= 64, A <= 64, H divides A.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fx_mhsa_workspace_floats(int64_t B, int32_t D_in, int32_t A, int32_t has_wres);
+int fx_mhsa_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in, const float* Wq,
+                const float* Wk, const float* Wv, const float* Wres, int32_t A, int32_t H,
+                int32_t use_scale, int32_t residual, int32_t relu, float* Y, fx_stream_t stream);
+int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in, const float* Wq,
+                const float* Wk, const float* Wv, const float* Wres, int32_t A, int32_t H,
+                int32_t use_scale, int32_t residual, int32_t relu, const float* Y,
+                const float* dY, float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dW,
+                float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
