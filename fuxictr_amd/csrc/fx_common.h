@@ -61,6 +61,15 @@ int fx_dedup_columns_launch(const int32_t* ids, int64_t ids_ld, int64_t B, int32
                             uint32_t* seg_start, int32_t* n_unique, uint32_t* sorted_uid,
                             fx_scalars* begin_scal, hipStream_t s);
 
+// ---- fx_rowopt.hip: the exact-mode catch-up of the unique rows of a de-dup result in 1..FX_MAX_TABLES table
+// groups, for fx_dedup_catchup (fx_fused.hip).  _check reports the argument errors of `tables_host` without
+// launching anything; quad_ok = false keeps the plain replays for the D = 16 (+ D = 1) shapes too.
+#define FX_MAX_TABLES 4
+int fx_catchup_rows_check(const fx_row_state* tables_host, int32_t n_tables, const char* who);
+int fx_catchup_rows_launch(const fx_row_state* tables_host, int32_t n_tables, const uint32_t* uniq_row,
+                           const int32_t* n_unique, int64_t n_max, int32_t upto_offset,
+                           const fx_scalars* scal, bool quad_ok, const char* who, hipStream_t s);
+
 // ---- fx_dedup_lds.hip: the bucketed in-LDS de-dup of the generic (n_shards = 1) path: rows hashed into 256
 // buckets by their low 8 bits (one stable partition pass), one workgroup sorts a bucket in LDS.  4 launches.
 // workspace: fx_dedup_buckets_bytes(n) bytes (<= fx_dedup_workspace_bytes(n)).
@@ -131,6 +140,17 @@ __device__ __forceinline__ void fx_begin_step_dev(fx_scalars* sc) {
     sc->bc1 = (float)bc1;
     sc->bc2_sqrt = (float)sqrt(bc2);
     sc->step_size = (float)(fx_dec_f64(sc->lr) / bc1);
+}
+
+// torch.optim.Adam._single_tensor_adam, one element (the table rows of fx_rowopt.hip and the dense
+// parameters of fx_sparse.hip's multi-tensor kernel)
+__device__ __forceinline__ void fx_adam_elem(float& p, float& m, float& v, float g, float w1,
+                                             float beta2, float w2, float bc2_sqrt, float eps,
+                                             float step_size) {
+    m = m + w1 * (g - m);                  // exp_avg.lerp_(grad, 1 - beta1)
+    v = fmaf(w2 * g, g, v * beta2);        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = p - step_size * (m / denom);       // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
 template <int VEC>

@@ -1,12 +1,13 @@
 // fx_sparse.hip — sparse side of the training step: index de-duplication, run-wise gradient
-// reduction to unique rows, global-norm clip coefficient, sparse-row Adam / SGD with the
-// "exact" catch-up replay, and the multi-tensor dense optimizer kernels.
+// reduction to unique rows, global-norm clip coefficient, and the multi-tensor dense optimizer
+// kernels.  (The sparse-row Adam / SGD, the "exact" catch-up replay and the embedding regularizer:
+// fx_rowopt.hip.)
 //
 // What this replaces in the reference (paths relative to the reference checkout):
 //   aten::embedding_dense_backward (zero-filled [V,D] grad + index_add), triggered at
 //     fuxictr/pytorch/models/rank_model.py:320
 //   nn.utils.clip_grad_norm_ over every parameter            rank_model.py:321
-//   torch.optim.Adam / SGD step over every table row          rank_model.py:322, torch_utils.py:76
+//   torch.optim.Adam / SGD step over the dense parameters     rank_model.py:322, torch_utils.py:76
 // None of the table-sized passes exist here: the gradient only ever exists for the unique rows
 // a batch touches.  All reductions use a fixed order (stable sort by row, ascending lookup
 // position inside a run, fixed trees) so results are run-to-run deterministic.
@@ -14,13 +15,17 @@
 #include <stdlib.h>
 
 
+// opens the optimizer step (fx_opt_begin_step; fx_dedup's generic path launches it too)
+__global__ void k_opt_begin_step(fx_scalars* sc) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) fx_begin_step_dev(sc);
+}
+
 // ---------------------------------------------------------------------------------------------
 // de-duplication
 // ---------------------------------------------------------------------------------------------
 // key = global packed row g, or — with the table row-sharded over n_shards ranks — the
 // owner-major pair (g % n_shards) * rows_per_shard + g / n_shards, so that a sort groups the
 // lookups by owning rank and the key itself carries (owner, local row).
-__global__ void k_opt_begin_step(fx_scalars* sc);
 
 __global__ void k_zero_words(int32_t* p, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
@@ -1133,10 +1138,6 @@ extern "C" int fx_split_rows(const float* src, int64_t src_ld, int64_t n_rows, i
 // ---------------------------------------------------------------------------------------------
 // optimizer scalars
 // ---------------------------------------------------------------------------------------------
-__global__ void k_opt_begin_step(fx_scalars* sc) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) fx_begin_step_dev(sc);
-}
-
 extern "C" int fx_opt_begin_step(fx_scalars* scal, fx_stream_t stream) {
     FX_CHECK_ARG(scal, "fx_opt_begin_step: null scal");
     hipLaunchKernelGGL(k_opt_begin_step, dim3(1), dim3(64), 0, fx_hip_stream(stream), scal);
@@ -1230,362 +1231,6 @@ extern "C" int fx_clip_coef(const float* const* parts_host, const int64_t* count
     a.scal = scal;
     hipLaunchKernelGGL(k_clip_coef, dim3(1), dim3(1024), 0, fx_hip_stream(stream), a);
     FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// sparse-row optimizers
-// ---------------------------------------------------------------------------------------------
-struct RowOptArgs {
-    float* table;
-    float* m;
-    float* v;
-    int32_t* last_step;
-    const uint32_t* uniq_row;
-    const int32_t* n_unique;
-    const float* G;
-    const fx_scalars* scal;
-    int64_t total_rows;
-    int32_t D, lanes_log2, upto_offset;
-};
-
-// torch.optim.Adam._single_tensor_adam, one element
-__device__ __forceinline__ void fx_adam_elem(float& p, float& m, float& v, float g, float w1,
-                                             float beta2, float w2, float bc2_sqrt, float eps,
-                                             float step_size) {
-    m = m + w1 * (g - m);                  // exp_avg.lerp_(grad, 1 - beta1)
-    v = fmaf(w2 * g, g, v * beta2);        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p - step_size * (m / denom);       // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
-
-// d/dp of (l1 * |p| + l2/2 * p^2): the embedding regularizer of rank_model.py:106-112
-__device__ __forceinline__ float fx_reg_grad(float p, float l1, float l2) {
-    float r = l2 * p;
-    if (l1 != 0.f) r += p > 0.f ? l1 : (p < 0.f ? -l1 : 0.f);
-    return r;
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void k_sparse_adam(RowOptArgs a) {
-    const int lanes = 1 << a.lanes_log2;
-    const int sub = threadIdx.x & (lanes - 1);
-    const int d0 = sub * VEC;
-    const int nu = *a.n_unique;
-    const int64_t rpb = 256 >> a.lanes_log2;
-    const fx_scalars sc = *a.scal;
-    const float w1 = fx_one_minus(sc.beta1), w2 = fx_one_minus(sc.beta2);   // torch's float(1 - beta)
-    for (int64_t u = (int64_t)blockIdx.x * rpb + (threadIdx.x >> a.lanes_log2); u < nu;
-         u += (int64_t)gridDim.x * rpb) {
-        const int64_t row = a.uniq_row[u];
-        if (d0 < a.D) {
-            float p[VEC], m[VEC], v[VEC], g[VEC];
-            const int64_t o = row * a.D + d0;
-            fx_load<VEC>(a.table + o, p);
-            fx_load<VEC>(a.m + o, m);
-            fx_load<VEC>(a.v + o, v);
-            fx_load<VEC>(a.G + u * a.D + d0, g);
-            if (sc.reg_l1 != 0.f || sc.reg_l2 != 0.f) {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) g[k] += fx_reg_grad(p[k], sc.reg_l1, sc.reg_l2);
-            }
-#pragma unroll
-            for (int k = 0; k < VEC; ++k)
-                fx_adam_elem(p[k], m[k], v[k], g[k] * sc.clip_coef, w1, sc.beta2, w2, sc.bc2_sqrt,
-                             sc.eps, sc.step_size);
-            fx_store<VEC>(a.table + o, p);
-            fx_store<VEC>(a.m + o, m);
-            fx_store<VEC>(a.v + o, v);
-        }
-        if (sub == 0 && a.last_step) a.last_step[row] = sc.step;
-    }
-}
-
-// Replay of the zero-gradient Adam steps a dense optimizer would have applied to a row that no
-// batch touched since last_step[row].  With g = 0 the per-step update is
-//     m *= beta1 ; v *= beta2 ; p -= lr/(1-beta1^j) * m / (sqrt(v)/sqrt(1-beta2^j) + eps)
-// whose magnitude decays like (beta1/sqrt(beta2))^j ~ 0.9^j, so after FX_REPLAY_MAX steps the
-// remaining terms are below fp32 resolution of the accumulated update; the tail only decays m, v
-// (fx_adam_replay in fx_common.h).
-
-template <int VEC>
-__global__ __launch_bounds__(256) void k_adam_catchup(RowOptArgs a) {
-    const int lanes = 1 << a.lanes_log2;
-    const int sub = threadIdx.x & (lanes - 1);
-    const int d0 = sub * VEC;
-    const int64_t rpb = 256 >> a.lanes_log2;
-    const fx_scalars sc = *a.scal;
-    const int upto = sc.step + a.upto_offset;
-    const int64_t n = a.uniq_row ? (int64_t)(*a.n_unique) : a.total_rows;
-    const FxLogs lg = fx_logs_of(sc);
-    const FxSeries ser = fx_series_of(a.scal, sc);
-    for (int64_t u = (int64_t)blockIdx.x * rpb + (threadIdx.x >> a.lanes_log2); u < n;
-         u += (int64_t)gridDim.x * rpb) {
-        const int64_t row = a.uniq_row ? (int64_t)a.uniq_row[u] : u;
-        const int last = a.last_step[row];
-        const int k_steps = upto - last;
-        if (k_steps <= 0) continue;
-        if (d0 < a.D) {
-            float p[VEC], m[VEC], v[VEC];
-            const int64_t o = row * a.D + d0;
-            fx_load<VEC>(a.m + o, m);
-            fx_load<VEC>(a.v + o, v);
-            bool any = false;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) any = any || (m[k] != 0.f) || (v[k] != 0.f);
-            if (any) {
-                fx_load<VEC>(a.table + o, p);
-                fx_adam_replay<VEC>(p, m, v, last, k_steps, sc, lg, ser);
-                fx_store<VEC>(a.table + o, p);
-                fx_store<VEC>(a.m + o, m);
-                fx_store<VEC>(a.v + o, v);
-            }
-        }
-        if (sub == 0) a.last_step[row] = upto;
-    }
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void k_sparse_sgd(RowOptArgs a) {
-    const int lanes = 1 << a.lanes_log2;
-    const int sub = threadIdx.x & (lanes - 1);
-    const int d0 = sub * VEC;
-    const int nu = *a.n_unique;
-    const int64_t rpb = 256 >> a.lanes_log2;
-    const float scale = a.scal->lr * a.scal->clip_coef;
-    const float l1 = a.scal->reg_l1, l2 = a.scal->reg_l2;
-    const int step = a.scal->step;
-    for (int64_t u = (int64_t)blockIdx.x * rpb + (threadIdx.x >> a.lanes_log2); u < nu;
-         u += (int64_t)gridDim.x * rpb) {
-        if (d0 >= a.D) continue;
-        const int64_t row = a.uniq_row[u];
-        float p[VEC], g[VEC];
-        fx_load<VEC>(a.table + row * a.D + d0, p);
-        fx_load<VEC>(a.G + u * a.D + d0, g);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) p[k] = p[k] - scale * (g[k] + fx_reg_grad(p[k], l1, l2));
-        fx_store<VEC>(a.table + row * a.D + d0, p);
-        if (sub == 0 && a.last_step) a.last_step[row] = step;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// embedding regularizer (rank_model.py:95-112): a dense term over EVERY table row.  Three kernels:
-//   k_reg_stats   sum p^2, sum |p|, sum r^2 (r = l1 sign(p) + l2 p) over the whole packed table
-//   k_reg_cross   sum 2 G.r over the rows the batch touched: with it
-//                 |G + r|^2 summed over all rows = sum r^2 + sum G^2 + sum 2 G.r
-//   k_reg_dense   the optimizer step with g = r for the rows the batch did NOT touch
-//                 (touched rows: k_sparse_adam / k_sparse_sgd add r themselves and mark last_step)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_reg_stats(const float* __restrict__ x, int64_t n,
-                                                   const fx_scalars* scal, float* partials) {
-    __shared__ float red4[4];
-    const float l1 = scal->reg_l1, l2 = scal->reg_l2;
-    float s2 = 0.f, s1 = 0.f, sr = 0.f;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    const int64_t n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? (n >> 2) : 0;
-    const float4* x4 = reinterpret_cast<const float4*>(x);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        const float4 q = x4[i];
-        const float e[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float r = fx_reg_grad(e[k], l1, l2);
-            s2 = fmaf(e[k], e[k], s2);
-            s1 += fabsf(e[k]);
-            sr = fmaf(r, r, sr);
-        }
-    }
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float e = x[i], r = fx_reg_grad(e, l1, l2);
-        s2 = fmaf(e, e, s2);
-        s1 += fabsf(e);
-        sr = fmaf(r, r, sr);
-    }
-    const float t2 = fx_block_sum_256(s2, red4);
-    __syncthreads();
-    const float t1 = fx_block_sum_256(s1, red4);
-    __syncthreads();
-    const float tr = fx_block_sum_256(sr, red4);
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = t2;
-        partials[FX_REG_BLOCKS + blockIdx.x] = t1;
-        partials[2 * FX_REG_BLOCKS + blockIdx.x] = tr;
-    }
-}
-
-extern "C" int fx_reg_stats(const float* x, int64_t n, const fx_scalars* scal, float* partials,
-                            fx_stream_t stream) {
-    FX_CHECK_ARG(n >= 0, "fx_reg_stats: n=%lld", (long long)n);
-    FX_CHECK_ARG((x || n == 0) && scal && partials, "fx_reg_stats: null pointer");
-    hipLaunchKernelGGL(k_reg_stats, dim3(FX_REG_BLOCKS), dim3(256), 0, fx_hip_stream(stream), x, n,
-                       scal, partials);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void k_reg_cross(RowOptArgs a, float* partials) {
-    __shared__ float red4[4];
-    const int lanes = 1 << a.lanes_log2;
-    const int sub = threadIdx.x & (lanes - 1);
-    const int d0 = sub * VEC;
-    const int nu = *a.n_unique;
-    const int64_t rpb = 256 >> a.lanes_log2;
-    const float l1 = a.scal->reg_l1, l2 = a.scal->reg_l2;
-    float acc = 0.f;
-    for (int64_t u = (int64_t)blockIdx.x * rpb + (threadIdx.x >> a.lanes_log2); u < nu;
-         u += (int64_t)gridDim.x * rpb) {
-        if (d0 >= a.D) continue;
-        const int64_t row = a.uniq_row[u];
-        float p[VEC], g[VEC];
-        fx_load<VEC>(a.table + row * a.D + d0, p);
-        fx_load<VEC>(a.G + u * a.D + d0, g);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc = fmaf(2.f * g[k], fx_reg_grad(p[k], l1, l2), acc);
-    }
-    const float tot = fx_block_sum_256(acc, red4);
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
-}
-
-extern "C" int fx_reg_cross(const float* table, int32_t D, const uint32_t* uniq_row,
-                            const int32_t* n_unique, int64_t n_max, const float* G,
-                            const fx_scalars* scal, float* partials, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_reg_cross: D=%d not in [1,256]", D);
-    FX_CHECK_ARG(table && uniq_row && n_unique && G && scal && partials,
-                 "fx_reg_cross: null pointer");
-    RowOptArgs a{const_cast<float*>(table), nullptr, nullptr, nullptr, uniq_row, n_unique, G, scal,
-                 0, D, 0, 0};
-    const FxRowGeom g = fx_row_geom(D);
-    int ll = 0;
-    while ((1 << ll) < g.lanes) ++ll;
-    a.lanes_log2 = ll;
-    hipStream_t s = fx_hip_stream(stream);
-    dim3 grid(FX_REG_CROSS_BLOCKS);       // fixed: every block writes its (possibly zero) partial
-    if (g.vec == 4) hipLaunchKernelGGL(k_reg_cross<4>, grid, dim3(256), 0, s, a, partials);
-    else if (g.vec == 2) hipLaunchKernelGGL(k_reg_cross<2>, grid, dim3(256), 0, s, a, partials);
-    else hipLaunchKernelGGL(k_reg_cross<1>, grid, dim3(256), 0, s, a, partials);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
-template <int VEC, bool ADAM>
-__global__ __launch_bounds__(256) void k_reg_dense(RowOptArgs a) {
-    const int lanes = 1 << a.lanes_log2;
-    const int sub = threadIdx.x & (lanes - 1);
-    const int d0 = sub * VEC;
-    const int64_t rpb = 256 >> a.lanes_log2;
-    const fx_scalars sc = *a.scal;
-    const float w1 = fx_one_minus(sc.beta1), w2 = fx_one_minus(sc.beta2);   // torch's float(1 - beta)
-    const float scale = sc.lr * sc.clip_coef;
-    for (int64_t row = (int64_t)blockIdx.x * rpb + (threadIdx.x >> a.lanes_log2); row < a.total_rows;
-         row += (int64_t)gridDim.x * rpb) {
-        if (d0 >= a.D) continue;
-        if (a.last_step[row] == sc.step) continue;       // updated by the sparse kernel this step
-        const int64_t o = row * a.D + d0;
-        float p[VEC];
-        fx_load<VEC>(a.table + o, p);
-        if constexpr (ADAM) {
-            float m[VEC], v[VEC];
-            fx_load<VEC>(a.m + o, m);
-            fx_load<VEC>(a.v + o, v);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k)
-                fx_adam_elem(p[k], m[k], v[k], fx_reg_grad(p[k], sc.reg_l1, sc.reg_l2) * sc.clip_coef,
-                             w1, sc.beta2, w2, sc.bc2_sqrt, sc.eps, sc.step_size);
-            fx_store<VEC>(a.m + o, m);
-            fx_store<VEC>(a.v + o, v);
-        } else {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) p[k] = p[k] - scale * fx_reg_grad(p[k], sc.reg_l1, sc.reg_l2);
-        }
-        fx_store<VEC>(a.table + o, p);
-    }
-}
-
-extern "C" int fx_reg_dense_update(float* table, float* m, float* v, const int32_t* last_step,
-                                   int64_t total_rows, int32_t D, int32_t adam,
-                                   const fx_scalars* scal, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_reg_dense_update: D=%d not in [1,256]", D);
-    if (total_rows <= 0) return FX_OK;
-    FX_CHECK_ARG(table && last_step && scal && (!adam || (m && v)),
-                 "fx_reg_dense_update: null pointer");
-    RowOptArgs a{table, m, v, const_cast<int32_t*>(last_step), nullptr, nullptr, nullptr, scal,
-                 total_rows, D, 0, 0};
-    const FxRowGeom g = fx_row_geom(D);
-    int ll = 0;
-    while ((1 << ll) < g.lanes) ++ll;
-    a.lanes_log2 = ll;
-    int64_t blocks = fx_ceil_div(total_rows, 256 / g.lanes);
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    dim3 grid((unsigned)blocks);
-    hipStream_t s = fx_hip_stream(stream);
-#define FX_REG_DENSE(V)                                                                      \
-    do {                                                                                     \
-        if (adam) hipLaunchKernelGGL((k_reg_dense<V, true>), grid, dim3(256), 0, s, a);      \
-        else hipLaunchKernelGGL((k_reg_dense<V, false>), grid, dim3(256), 0, s, a);          \
-    } while (0)
-    if (g.vec == 4) FX_REG_DENSE(4);
-    else if (g.vec == 2) FX_REG_DENSE(2);
-    else FX_REG_DENSE(1);
-#undef FX_REG_DENSE
-    FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
-#define FX_LAUNCH_ROWOPT(KERNEL, n_rows_max)                                             \
-    do {                                                                                 \
-        const FxRowGeom g = fx_row_geom(D);                                              \
-        int ll = 0;                                                                      \
-        while ((1 << ll) < g.lanes) ++ll;                                                \
-        a.lanes_log2 = ll;                                                               \
-        int64_t blocks = fx_ceil_div((n_rows_max), 256 / g.lanes);                       \
-        if (blocks > 256 * 64) blocks = 256 * 64;                                        \
-        if (blocks < 1) blocks = 1;                                                      \
-        dim3 grid((unsigned)blocks);                                                     \
-        hipStream_t s = fx_hip_stream(stream);                                           \
-        if (g.vec == 4) hipLaunchKernelGGL(KERNEL<4>, grid, dim3(256), 0, s, a);         \
-        else if (g.vec == 2) hipLaunchKernelGGL(KERNEL<2>, grid, dim3(256), 0, s, a);    \
-        else hipLaunchKernelGGL(KERNEL<1>, grid, dim3(256), 0, s, a);                    \
-        FX_CHECK_LAUNCH();                                                               \
-    } while (0)
-
-extern "C" int fx_sparse_adam(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                              const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                              const float* G, const fx_scalars* scal, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_sparse_adam: D=%d not in [1,256]", D);
-    if (n_max <= 0) return FX_OK;
-    FX_CHECK_ARG(table && m && v && uniq_row && n_unique && G && scal,
-                 "fx_sparse_adam: null pointer");
-    RowOptArgs a{table, m, v, last_step, uniq_row, n_unique, G, scal, 0, D, 0, 0};
-    FX_LAUNCH_ROWOPT(k_sparse_adam, n_max);
-    return FX_OK;
-}
-
-extern "C" int fx_adam_catchup(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                               const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                               int64_t total_rows, int32_t upto_offset, const fx_scalars* scal,
-                               fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_adam_catchup: D=%d not in [1,256]", D);
-    FX_CHECK_ARG(table && m && v && last_step && scal, "fx_adam_catchup: null pointer");
-    FX_CHECK_ARG(uniq_row == nullptr || n_unique != nullptr,
-                 "fx_adam_catchup: uniq_row given without n_unique");
-    const int64_t rows = uniq_row ? n_max : total_rows;
-    if (rows <= 0) return FX_OK;
-    RowOptArgs a{table, m, v, last_step, uniq_row, n_unique, nullptr, scal, total_rows, D, 0,
-                 upto_offset};
-    FX_LAUNCH_ROWOPT(k_adam_catchup, rows);
-    return FX_OK;
-}
-
-extern "C" int fx_sparse_sgd(float* table, int32_t* last_step, int32_t D, const uint32_t* uniq_row,
-                             const int32_t* n_unique, int64_t n_max, const float* G,
-                             const fx_scalars* scal, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_sparse_sgd: D=%d not in [1,256]", D);
-    if (n_max <= 0) return FX_OK;
-    FX_CHECK_ARG(table && uniq_row && n_unique && G && scal, "fx_sparse_sgd: null pointer");
-    RowOptArgs a{table, nullptr, nullptr, last_step, uniq_row, n_unique, G, scal, 0, D, 0, 0};
-    FX_LAUNCH_ROWOPT(k_sparse_sgd, n_max);
     return FX_OK;
 }
 

@@ -514,8 +514,8 @@ class _TableGroup(object):
         if dd is None:
             dd = self.dedup(plan, ids, inputs)
         if todo:
-            # generic de-dup (sequence columns that alias a table, B > 8192): one dtype-aware launch
-            # for every table group of the id plan (fx_adam_catchup is fp32-only)
+            # generic de-dup (sequence columns that alias a table, B > 8192): one launch for every table
+            # group of the id plan
             ops.adam_catchup_rows([g.row_state() for g in todo], dd, -1, self.scal)
             if cache is not None:
                 for g in todo:
@@ -703,11 +703,7 @@ class _TableGroup(object):
         """exact mode: replay pending zero-gradient Adam steps for EVERY row (before eval/save)."""
         if self.exact and self.opt_kind == "adam" and self.table is not None:
             rows = self.rows_per_shard + 1 if self.sharded else self.total_rows
-            if self.table.dtype == torch.bfloat16 or self.record is not None:
-                ops.adam_catchup_all(self.row_state(), rows, 0, self.scal)
-            else:
-                ops.adam_catchup(self.table, self.m, self.v, self.last_step, self.D, None,
-                                 rows, 0, self.scal)
+            ops.adam_catchup_all(self.row_state(), rows, 0, self.scal)
 
 
 def finish_shard_backward(groups):

@@ -477,9 +477,9 @@ def clip_coef(parts, scal):
 
 def _need_fp32_table(table, who):
     if table.dtype != torch.float32:
-        raise _lib.FxError("%s is the fp32-only kernel of round 1 and got a %s table; bf16 tables go "
-                           "through the RowState entry points (adam_catchup_rows / "
-                           "sparse_update_multi)" % (who, table.dtype))
+        raise _lib.FxError("%s takes one packed fp32 table (its C prototype has no dtype) and got a %s "
+                           "table; bf16 tables go through the RowState entry points "
+                           "(adam_catchup_rows / sparse_update_multi)" % (who, table.dtype))
 
 
 @_timed("sparse_adam", "sparse_path")

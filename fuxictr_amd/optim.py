@@ -376,11 +376,7 @@ class _NativeOptimizer(torch.optim.Optimizer):
             for rec in grp.pending:
                 buckets.setdefault(id(rec.dd), []).append((grp, rec))
         for items in buckets.values():
-            if len(items) == 1 and items[0][0].table.dtype == torch.float32 and items[0][0].record is None:
-                self._sparse_update(*items[0])
-                continue
-            # dtype-aware multi-table kernel, FX_MAX_TABLES groups per launch (a bf16 table must never
-            # reach the fp32-only single-table kernels)
+            # FX_MAX_TABLES groups per launch
             for i in range(0, len(items), _lib.FX_MAX_TABLES):
                 part = items[i:i + _lib.FX_MAX_TABLES]
                 ops.sparse_update_multi(self.kind, [g.row_state(G=r.G) for g, r in part],
@@ -456,9 +452,6 @@ class NativeAdam(_NativeOptimizer):
         ms, vs = self._moments(ps)
         ops.mt_adam(ps, gs, ms, vs, self.scal)
 
-    def _sparse_update(self, grp, rec):
-        ops.sparse_adam(grp.table, grp.m, grp.v, grp.last_step, grp.D, rec.dd, rec.G, self.scal)
-
 
 class NativeSGD(_NativeOptimizer):
     """torch.optim.SGD(params, lr) defaults (no momentum, no weight decay)."""
@@ -466,9 +459,6 @@ class NativeSGD(_NativeOptimizer):
 
     def _dense_update(self, ps, gs):
         ops.mt_sgd(ps, gs, self.scal)
-
-    def _sparse_update(self, grp, rec):
-        ops.sparse_sgd(grp.table, grp.D, rec.dd, rec.G, self.scal, last_step=grp.last_step)
 
 
 def get_optimizer(optimizer, params, lr, model=None, sparse_update="exact", emb_reg=None):

@@ -142,9 +142,9 @@ def test_bf16_model_error_report_at_c2_shapes(tmp_path):
 @pytest.mark.parametrize("case,B", [("c2_deepfm", 8448), ("c4_din", 2048)])
 def test_bf16_tables_on_the_generic_dedup_path(case, B, tmp_path):
     """outside the column fast path — B > 8192, or sequence columns that alias a
-    table (DIN) — the exact-mode catch-up and the row update of a bf16 table must go through the
-    dtype-aware kernels (fx_adam_catchup_rows / fx_sparse_adam_multi); the fp32-only round-1 kernels
-    would write 4-byte floats into the 2-byte table.  Checked: rows no batch touched are bit-identical
+    table (DIN) — the exact-mode catch-up and the row update of a bf16 table go through the same
+    dtype-aware kernels (fx_adam_catchup_rows / fx_sparse_adam_multi); a kernel that took the table for
+    fp32 would write 4-byte floats into the 2-byte table.  Checked: rows no batch touched are bit-identical
     to their initial value after training (a stray fp32 write lands in other rows), the losses follow
     the fp32 oracle within the bf16 storage error, nothing is flagged."""
     dist = "powerlaw"

@@ -409,6 +409,56 @@ def test_sparse_update_multi_equals_one_launch_per_table(kind, dims):
             assert torch.equal(m, sb.m) and torch.equal(v, sb.v), D
 
 
+@pytest.mark.parametrize("series", [False, True])
+@pytest.mark.parametrize("D", [10, 16, 1])
+def test_single_table_catchup_equals_the_row_state_entry_points(D, series):
+    """fx_adam_catchup (one packed fp32 table) against fx_adam_catchup_rows / fx_adam_catchup_all on the same
+    state, to the bit: the plain replay of a row does not depend on the entry point it came in through.  D = 16
+    is the shape fx_adam_catchup_rows hands to the quad replay (equal to fp32 rounding only, see
+    test_dedup_catchup_equals_dedup_plus_catchup); fx_adam_catchup must keep the plain replay there, which is
+    pinned against the same rows of a flush."""
+    rng = np.random.default_rng(17 + D)
+    R = 300
+    t, m, v = _tables(rng, R, D)
+    idle = torch.from_numpy(rng.random(R) < 0.2)
+    m[idle] = 0.0                                            # rows that never had a gradient
+    v[idle] = 0.0
+    last = torch.from_numpy(rng.integers(0, 7, R).astype(np.int32))
+    scal = ops.new_scalars(DEV, series=series)
+    scal.view(torch.int32)[_lib.SC_STEP] = 8
+    rows = rng.choice(R, 40, replace=False)
+    ids = np.concatenate([rows, rng.choice(rows, 24)]).reshape(64, 1)
+    ws = torch.empty(ops.dedup_workspace_bytes(64), dtype=torch.uint8, device=DEV)
+    dd = ops.dedup(_dev(ids, torch.int32), _dev([0], torch.int64), _dev([R], torch.int32),
+                   _dev([-1], torch.int32), R, ws)
+    assert int(dd.n_unique.item()) == 40
+
+    def fresh():
+        return [x.clone().to(DEV) for x in (t, m, v, last)]
+
+    names = ("table", "m", "v", "last_step")
+    one = fresh()
+    ops.adam_catchup(*one, D, dd, R, -1, scal)
+    assert int(one[3].cpu()[rows].min()) == 7 and not torch.equal(one[0].cpu(), t)
+    if D != 16:
+        rs = fresh()
+        ops.adam_catchup_rows([ops.RowState(*rs, D)], dd, -1, scal)
+        for a, b, what in zip(one, rs, names):
+            assert torch.equal(a, b), (D, "rows", what)
+    else:
+        every = fresh()
+        ops.adam_catchup_all(ops.RowState(*every, D), R, -1, scal)
+        sel = torch.from_numpy(np.sort(rows)).to(DEV)
+        for a, b, what in zip(one, every, names):
+            assert torch.equal(a[sel], b[sel]), (D, "plain replay of the listed rows", what)
+    flush_a, flush_b = fresh(), fresh()
+    ops.adam_catchup(*flush_a, D, None, R, 0, scal)
+    ops.adam_catchup_all(ops.RowState(*flush_b, D), R, 0, scal)
+    assert int(flush_a[3].min()) == 8
+    for a, b, what in zip(flush_a, flush_b, names):
+        assert torch.equal(a, b), (D, "flush", what)
+
+
 def test_pack_columns_multi_all_dtypes():
     g = torch.Generator().manual_seed(0)
     B = 1000

@@ -302,6 +302,92 @@ def test_sparse_sgd_and_clip():
     assert (table.cpu() - ref).abs().max().item() <= 1e-6
 
 
+def _wide_row_state(D, R=50):
+    g = torch.Generator().manual_seed(D)
+    rows = np.array([0, 3, 7, 8, 21, 30, 48, 49])
+    p = torch.randn(R, D, generator=g)
+    m, v = torch.zeros(R, D), torch.zeros(R, D)
+    m[rows] = torch.randn(8, D, generator=g) * 0.1
+    v[rows] = torch.rand(8, D, generator=g) * 0.01
+    return g, rows, p, m, v
+
+
+@pytest.mark.parametrize("kind", ["adam", "sgd"])
+@pytest.mark.parametrize("D", [65, 130, 255])
+def test_sparse_update_of_rows_wider_than_a_wave(D, kind):
+    """Rows of 128 / 256 lanes (odd D > 64, D % 4 == 2 above 128): one step of fx_sparse_adam / fx_sparse_sgd
+    against the fp32 torch step, and the multi-table entry point on the same state to the bit."""
+    g, rows, p0, m0, v0 = _wide_row_state(D)
+    R, lr = p0.shape[0], 1e-2
+    ids = np.concatenate([rows, rows[:4]]).reshape(12, 1)
+    ws = torch.empty(ops.dedup_workspace_bytes(12), dtype=torch.uint8, device=DEV)
+    dd = ops.dedup(_dev(ids, torch.int32), _dev([0], torch.int64), _dev([R], torch.int32),
+                   _dev([-1], torch.int32), R, ws)
+    nu = int(dd.n_unique.item())
+    assert nu == 8 and dd.uniq_row[:nu].cpu().tolist() == rows.tolist()
+    G = torch.zeros(dd.n_max, D)
+    G[:nu] = torch.randn(nu, D, generator=g) * 0.1
+    g_dense = torch.zeros(R, D)
+    g_dense[rows] = G[:nu]
+    scal = ops.new_scalars(DEV, lr=lr)
+    ops.opt_begin_step(scal)
+    one = [_dev(x) for x in (p0, m0, v0)] + [torch.zeros(R, dtype=torch.int32, device=DEV)]
+    two = [x.clone() for x in one]
+    if kind == "adam":
+        ops.sparse_adam(*one, D, dd, _dev(G), scal)
+        p_ref, m_ref, v_ref = p0.clone(), m0.clone(), v0.clone()
+        _adam_ref_step(p_ref, g_dense, m_ref, v_ref, 1, lr)
+        p64, m64, v64 = p0.double(), m0.double(), v0.double()
+        O.adam_dense(p64, g_dense.double(), m64, v64, 1, lr)
+        _within_yardstick(one[0].cpu(), p_ref, p64, 2e-6, ("wide adam", D))
+        assert (one[1].cpu() - m_ref).abs().max().item() <= 1e-6
+        assert (one[2].cpu() - v_ref).abs().max().item() <= 1e-6
+        state = ops.RowState(*two, D, G=_dev(G))
+    else:
+        ops.sparse_sgd(one[0], D, dd, _dev(G), scal, last_step=one[3])
+        assert (one[0].cpu() - (p0 - lr * g_dense)).abs().max().item() <= 1e-6
+        state = ops.RowState(two[0], None, None, two[3], D, G=_dev(G))
+    assert one[3].cpu().nonzero().view(-1).tolist() == rows.tolist()
+    ops.sparse_update_multi(kind, [state], dd, scal)
+    for a, b, what in zip(one, two, ("table", "m", "v", "last_step")):
+        assert torch.equal(a, b), (D, kind, what)
+
+
+@pytest.mark.parametrize("D", [65, 130, 255])
+def test_adam_catchup_of_rows_wider_than_a_wave(D):
+    """The same widths through fx_adam_catchup, as a row list and as the flush: k zero-gradient steps of dense
+    torch Adam (the fp64 trajectory is the yardstick).  The state the rows idle from is one Adam reaches — t0 real
+    steps from zero moments — so |m| / sqrt(v) is bounded as in a run and a row moves by at most ~lr a step: the
+    yardstick's 2e-6 floor is an absolute bound on p, written for such moves."""
+    g, rows, p0, _, _ = _wide_row_state(D)
+    R, lr, t0, k = p0.shape[0], 1e-2, 3, 5
+    m0, v0 = torch.zeros(R, D), torch.zeros(R, D)
+    for t in range(1, t0 + 1):                              # every row has moved before
+        _adam_ref_step(p0, torch.randn(R, D, generator=g) * 0.1, m0, v0, t, lr)
+    p_ref, m_ref, v_ref = p0.clone(), m0.clone(), v0.clone()
+    p64, m64, v64 = p0.double(), m0.double(), v0.double()
+    for t in range(t0 + 1, t0 + k + 1):
+        _adam_ref_step(p_ref, torch.zeros(R, D), m_ref, v_ref, t, lr)
+        O.adam_dense(p64, torch.zeros(R, D, dtype=torch.float64), m64, v64, t, lr)
+    ids = rows.reshape(8, 1)
+    ws = torch.empty(ops.dedup_workspace_bytes(8), dtype=torch.uint8, device=DEV)
+    dd = ops.dedup(_dev(ids, torch.int32), _dev([0], torch.int64), _dev([R], torch.int32),
+                   _dev([-1], torch.int32), R, ws)
+    scal = ops.new_scalars(DEV, lr=lr)
+    scal.view(torch.int32)[_lib.SC_STEP] = t0 + k
+    for form in ("rows", "flush"):
+        p, m, v = _dev(p0), _dev(m0), _dev(v0)
+        last = torch.full((R,), t0, dtype=torch.int32, device=DEV)
+        ops.adam_catchup(p, m, v, last, D, dd if form == "rows" else None, R, 0, scal)
+        sel = rows if form == "rows" else np.arange(R)
+        rest = np.setdiff1d(np.arange(R), sel)
+        _within_yardstick(p.cpu()[sel], p_ref[sel], p64[sel], 2e-6, ("wide catch-up", form, D))
+        assert (m.cpu()[sel] - m_ref[sel]).abs().max().item() <= 1e-6
+        assert (v.cpu()[sel] - v_ref[sel]).abs().max().item() <= 1e-6
+        assert torch.equal(p.cpu()[rest], p0[rest]) and torch.equal(m.cpu()[rest], m0[rest])
+        assert last.cpu()[sel].tolist() == [t0 + k] * len(sel) and last.cpu()[rest].tolist() == [t0] * len(rest)
+
+
 def test_multi_tensor_adam_sqnorm_clip():
     g = torch.Generator().manual_seed(9)
     shapes = [(1024, 624), (1024,), (1, 1024), (1,), (13, 16), (37,)]
