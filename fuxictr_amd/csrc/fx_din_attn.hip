@@ -38,8 +38,9 @@
 // All sums have a fixed order (register loops, fixed trees across half-waves / waves / workgroups):
 // deterministic, hipGraph-replay bit-identical.
 // Limits of the fused form: E <= 16 (4E <= 64), H <= 64, one hidden layer with Dice; everything else
-// takes the unfused kernels (fx_din.hip) — both are native paths.
-#include "fx_common.h"
+// takes the unfused kernels (fx_din.hip, fx_dice.hip) — both are native paths.  The per-workgroup partial
+// sums of the statistics and backward passes are finished by the kernels of fx_dice.hip (fx_dice_int.h).
+#include "fx_dice_int.h"
 
 #include <stdlib.h>
 
@@ -1310,104 +1311,6 @@ void k_din_attn2_bwd(DinAttnArgs a) {
     }
 }
 
-// out[k * H + h] = sum over chunks c (fixed order) of partial[(c * nt + k) * H + h]
-__global__ __launch_bounds__(256) void k_da_chunks_sum(const float* partial, int chunks, int nt,
-                                                       int64_t H, float* out) {
-    __shared__ float red[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int64_t h = (int64_t)blockIdx.x * 16 + tx;
-    const int k = blockIdx.y;
-    float s = 0.f;
-    if (h < H) {
-        int c = ty;
-        for (; c + 7 * 16 < chunks; c += 8 * 16) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = partial[((int64_t)(c + u * 16) * nt + k) * H + h];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; c < chunks; c += 16) s += partial[((int64_t)c * nt + k) * H + h];
-    }
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && h < H) {
-        float t = 0.f;
-#pragma unroll
-        for (int y = 0; y < 16; ++y) t += red[y][tx];
-        out[(int64_t)k * H + h] = t;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_da_stats_from_sums(const float* sums, int H, double n_total,
-                                                            float momentum, float* stats,
-                                                            float* running_mean,
-                                                            float* running_var,
-                                                            int64_t* num_batches_tracked) {
-    const int h = blockIdx.x * 256 + threadIdx.x;
-    if (h == 0 && num_batches_tracked) *num_batches_tracked += 1;   // nn.BatchNorm1d's step counter
-    if (h >= H) return;
-    const double mean = (double)sums[h] / n_total;
-    double var = (double)sums[H + h] / n_total - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[h] = (float)mean;
-    stats[H + h] = (float)var;
-    if (running_mean) {
-        const double unb = n_total > 1.0 ? var * n_total / (n_total - 1.0) : var;
-        running_mean[h] = (float)((1.0 - momentum) * running_mean[h] + momentum * mean);
-        running_var[h] = (float)((1.0 - momentum) * running_var[h] + momentum * unb);
-    }
-}
-
-// k_da_chunks_sum (k = 0, 1: sum h, sum h^2) and k_da_stats_from_sums in one launch — the single-rank
-// case, where nothing (no all-reduce) happens between them.  Same chunk order, same statistics code.
-__global__ __launch_bounds__(256) void k_da_chunks_stats(const float* partial, int chunks, int H,
-                                                         double n_total, float momentum, float* sums,
-                                                         float* stats, float* running_mean,
-                                                         float* running_var, int64_t* num_batches_tracked) {
-    __shared__ float red[2][16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int h = blockIdx.x * 16 + tx;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches_tracked) *num_batches_tracked += 1;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        float s = 0.f;
-        if (h < H) {
-            int c = ty;
-            for (; c + 7 * 16 < chunks; c += 8 * 16) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = partial[((int64_t)(c + u * 16) * 2 + k) * H + h];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
-            for (; c < chunks; c += 16) s += partial[((int64_t)c * 2 + k) * H + h];
-        }
-        red[k][ty][tx] = s;
-    }
-    __syncthreads();
-    if (ty == 0 && h < H) {
-        float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int y = 0; y < 16; ++y) {
-            t0 += red[0][y][tx];
-            t1 += red[1][y][tx];
-        }
-        sums[h] = t0;
-        sums[H + h] = t1;
-        const double mean = (double)t0 / n_total;
-        double var = (double)t1 / n_total - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stats[h] = (float)mean;
-        stats[H + h] = (float)var;
-        if (running_mean) {
-            const double unb = n_total > 1.0 ? var * n_total / (n_total - 1.0) : var;
-            running_mean[h] = (float)((1.0 - momentum) * running_mean[h] + momentum * mean);
-            running_var[h] = (float)((1.0 - momentum) * running_var[h] + momentum * unb);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -1536,33 +1439,11 @@ extern "C" int fx_din_attn_stats(const float* q, int64_t q_ld, const float* K, i
     if (q2) DA2_LAUNCH(k_din_attn2_stats, 256, g.wgs_flat, s, a);
     else DA_DISPATCH(k_din_attn_stats, 256, g.wgs_flat, s, a);
     if (stats)      // one rank: the sums ARE the batch's — statistics in the same launch
-        hipLaunchKernelGGL(k_da_chunks_stats, dim3((unsigned)fx_ceil_div(H, 16)), dim3(256), 0, s,
-                           (const float*)workspace, (int)g.wgs_flat, (int)H, (double)(B * (int64_t)L), momentum,
-                           sums, stats, running_mean, running_var, num_batches_tracked);
+        fx_chunks_stats_launch(workspace, (int)g.wgs_flat, H, B * (int64_t)L, momentum, sums, stats,
+                               running_mean, running_var, num_batches_tracked, s);
     else
-        hipLaunchKernelGGL(k_da_chunks_sum, dim3((unsigned)fx_ceil_div(H, 16), 2), dim3(256), 0, s,
-                           (const float*)workspace, (int)g.wgs_flat, 2, (int64_t)H, sums);
+        fx_chunks_sum_launch(workspace, (int)g.wgs_flat, 2, H, sums, s);
     FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
-extern "C" int fx_dice_stats_from_sums(const float* sums, int32_t H, int64_t n_total, float momentum,
-                                       int32_t training, float* running_mean, float* running_var,
-                                       int64_t* num_batches_tracked, float* stats, fx_stream_t stream) {
-    FX_CHECK_ARG(H >= 1 && stats, "fx_dice_stats_from_sums: bad arguments");
-    hipStream_t s = fx_hip_stream(stream);
-    if (training) {
-        FX_CHECK_ARG(sums && n_total >= 1, "fx_dice_stats_from_sums: training mode needs the sums");
-        hipLaunchKernelGGL(k_da_stats_from_sums, dim3((unsigned)fx_ceil_div(H, 256)), dim3(256), 0, s,
-                           sums, (int)H, (double)n_total, momentum, stats, running_mean, running_var,
-                           num_batches_tracked);
-        FX_CHECK_LAUNCH();
-    } else {
-        FX_CHECK_ARG(running_mean && running_var, "fx_dice_stats_from_sums: null running statistics");
-        FX_CHECK_HIP(hipMemcpyAsync(stats, running_mean, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
-        FX_CHECK_HIP(hipMemcpyAsync(stats + H, running_var, sizeof(float) * H,
-                                    hipMemcpyDeviceToDevice, s));
-    }
     return FX_OK;
 }
 
@@ -1611,8 +1492,7 @@ extern "C" int fx_din_attn_bwd_sums(const float* q, int64_t q_ld, const float* K
     hipStream_t s = fx_hip_stream(stream);
     if (q2) DA2_LAUNCH(k_din_attn2_bwd_sums, 256, g.wgs_flat, s, a);
     else DA_DISPATCH(k_din_attn_bwd_sums, 256, g.wgs_flat, s, a);
-    hipLaunchKernelGGL(k_da_chunks_sum, dim3((unsigned)fx_ceil_div(H, 16), 5), dim3(256), 0, s,
-                       (const float*)workspace, (int)g.wgs_flat, 5, (int64_t)H, sums5);
+    fx_chunks_sum_launch(workspace, (int)g.wgs_flat, 5, H, sums5, s);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }
@@ -1649,8 +1529,7 @@ extern "C" int fx_din_attn_bwd(const float* q, int64_t q_ld, const float* K, int
     if (q2) DA2_LAUNCH(k_din_attn2_bwd, 128, g.wgs_bwd, s, a);
     else DA_DISPATCH(k_din_attn_bwd, 128, g.wgs_bwd, s, a);
     const int64_t tot = (int64_t)H * 4 * E + H;
-    hipLaunchKernelGGL(k_da_chunks_sum, dim3((unsigned)fx_ceil_div(tot, 16), 1), dim3(256), 0, s,
-                       (const float*)workspace, (int)g.wgs_bwd, 1, tot, dW1b1);
+    fx_chunks_sum_launch(workspace, (int)g.wgs_bwd, 1, tot, dW1b1, s);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }

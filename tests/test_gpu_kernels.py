@@ -844,7 +844,7 @@ def test_din_concat_and_pool_match_autograd():
 
 
 @pytest.mark.parametrize("training", [True, False])
-@pytest.mark.parametrize("N,H", [(20480, 64), (777, 16), (5, 100)])
+@pytest.mark.parametrize("N,H", [(20480, 64), (777, 16), (5, 100), (1300, 7)])
 def test_dice_matches_reference_batchnorm_gate(training, N, H):
     g = torch.Generator().manual_seed(N + H)
     z = (torch.randn(N, H, generator=g) * 1.5 + 0.3)
@@ -872,6 +872,87 @@ def test_dice_matches_reference_batchnorm_gate(training, N, H):
     scale = max(1.0, zr.grad.abs().max().item())
     assert (dz.cpu() - zr.grad).abs().max().item() <= 5e-5 * scale
     assert (da.cpu() - state["p.alpha"].grad).abs().max().item() <= 2e-4 * max(1.0, state["p.alpha"].grad.abs().max().item())
+
+
+# (N, H, off): fewer rows than chunks | float4 reduce kernels | scalar reduce kernels (H % 4 != 0), more than one
+# row per chunk | scalar reduce kernels with H % 4 == 0: the [N, H] inputs start `off` floats into their
+# buffers, which breaks the 16-byte alignment
+_DICE_SPLIT_CASES = [(5, 100, 0), (777, 16, 0), (1300, 7, 0), (2050, 36, 1)]
+
+
+def _dice_split_case(N, H, off):
+    g = torch.Generator().manual_seed(N + H)
+
+    def rows(scale, shift):
+        buf = _dev(torch.randn(off + N * H, generator=g) * scale + shift)
+        return buf[off:off + N * H].view(N, H)
+
+    z, dy = rows(1.5, 0.3), rows(1.0, 0.0)
+    alpha = _dev(torch.rand(H, generator=g) - 0.5)
+    rm0 = _dev(torch.randn(H, generator=g) * 0.1)
+    rv0 = _dev(torch.rand(H, generator=g) + 0.5)
+    return z, dy, alpha, rm0, rv0, torch.empty(ops.dice_workspace_floats(H), device=DEV)
+
+
+@pytest.mark.parametrize("N,H,off", _DICE_SPLIT_CASES)
+def test_dice_fwd_equals_local_sums_then_fwd_from_sums(N, H, off):
+    """One rank: fx_dice_fwd == fx_dice_local_sums -> fx_dice_fwd_from_sums(n_total = N), bit for bit (the same
+    additions in the same order, so no tolerance)."""
+    z, _, alpha, rm0, rv0, ws = _dice_split_case(N, H, off)
+    rm1, rv1, rm2, rv2 = rm0.clone(), rv0.clone(), rm0.clone(), rv0.clone()
+    stats1, stats2 = torch.empty(2 * H, device=DEV), torch.empty(2 * H, device=DEV)
+    y1, y2 = torch.empty(N, H, device=DEV), torch.empty(N, H, device=DEV)
+    ops.dice_fwd(z, alpha, 1e-9, 0.01, True, rm1, rv1, stats1, y1, ws)
+    sums = torch.empty(2 * H, device=DEV)
+    ops.dice_local_sums(z, sums, ws)
+    ops.dice_fwd_from_sums(z, alpha, 1e-9, 0.01, sums, N, rm2, rv2, stats2, y2)
+    assert torch.equal(stats1, stats2)
+    assert torch.equal(y1, y2)
+    assert torch.equal(rm1, rm2) and torch.equal(rv1, rv2)
+    assert not torch.equal(rm1, rm0) and not torch.equal(rv1, rv0)
+
+
+@pytest.mark.parametrize("N,H,off", _DICE_SPLIT_CASES)
+def test_dice_bwd_equals_bwd_local_sums_then_bwd_from_sums(N, H, off):
+    """One rank: fx_dice_bwd == fx_dice_bwd_local_sums -> fx_dice_bwd_from_sums(n_total = N), bit for bit."""
+    z, dy, alpha, rm, rv, ws = _dice_split_case(N, H, off)
+    stats = torch.empty(2 * H, device=DEV)
+    ops.dice_fwd(z, alpha, 1e-9, 0.01, True, rm, rv, stats, torch.empty(N, H, device=DEV), ws)
+    dz1, dz2 = torch.empty(N, H, device=DEV), torch.empty(N, H, device=DEV)
+    dalpha = torch.empty(H, device=DEV)
+    ops.dice_bwd(z, dy, alpha, 1e-9, True, stats, dz1, dalpha, ws)
+    sums3 = torch.empty(3 * H, device=DEV)
+    ops.dice_bwd_local_sums(z, dy, alpha, 1e-9, stats, sums3, ws)
+    ops.dice_bwd_from_sums(z, dy, alpha, 1e-9, stats, sums3, N, dz2)
+    assert torch.equal(dalpha, sums3[:H])
+    assert torch.equal(dz1, dz2)
+
+
+# general formulation | q-split formulation (E = 8 / 16, L >= 32), one and two hidden blocks
+@pytest.mark.parametrize("B,L,E,H", [(7, 3, 4, 16), (3, 32, 8, 7), (19, 33, 16, 64)])
+def test_din_attn_stats_in_one_call_equals_sums_then_dice_stats_from_sums(B, L, E, H):
+    """One rank: fx_din_attn_stats with `stats` == fx_din_attn_stats without -> fx_dice_stats_from_sums(training,
+    n_total = B * L), bit for bit, BatchNorm1d's step counter included."""
+    g = torch.Generator().manual_seed(B * L + E + H)
+    q, K = _dev(torch.randn(B, E, generator=g)), _dev(torch.randn(B, L, E, generator=g))
+    W1 = _dev(torch.randn(H, 4 * E, generator=g) * 0.3)
+    b1 = _dev(torch.randn(H, generator=g) * 0.1)
+    rm0 = _dev(torch.randn(H, generator=g) * 0.1)
+    rv0 = _dev(torch.rand(H, generator=g) + 0.5)
+    ws = torch.empty(ops.din_attn_workspace_floats(B, L, E, H), device=DEV)
+    rm1, rv1, rm2, rv2 = rm0.clone(), rv0.clone(), rm0.clone(), rv0.clone()
+    nbt1 = torch.zeros(1, dtype=torch.long, device=DEV)
+    nbt2 = torch.zeros(1, dtype=torch.long, device=DEV)
+    sums1, sums2 = torch.empty(2 * H + 1, device=DEV), torch.empty(2 * H + 1, device=DEV)
+    stats1, stats2 = torch.empty(2 * H, device=DEV), torch.empty(2 * H, device=DEV)
+    ops.din_attn_stats(q, K, W1, b1, sums1, ws, stats1, 0.01, rm1, rv1, nbt1)
+    ops.din_attn_stats(q, K, W1, b1, sums2, ws)
+    ops.dice_stats_from_sums(sums2, H, B * L, 0.01, True, rm2, rv2, stats2, nbt2)
+    assert torch.equal(sums1[:2 * H], sums2[:2 * H])
+    assert torch.equal(stats1, stats2)
+    assert torch.equal(rm1, rm2) and torch.equal(rv1, rv2)
+    assert not torch.equal(rm1, rm0) and not torch.equal(rv1, rv0)
+    assert int(nbt1.item()) == 1 and int(nbt2.item()) == 1
 
 
 @pytest.mark.parametrize("F,D", [(27, 16), (15, 8), (2, 3), (40, 40), (32, 32), (31, 2), (3, 4), (2, 16)])
