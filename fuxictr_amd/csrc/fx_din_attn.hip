@@ -40,9 +40,15 @@
 // Limits of the fused form: E <= 16 (4E <= 64), H <= 64, one hidden layer with Dice; everything else
 // takes the unfused kernels (fx_din.hip, fx_dice.hip) — both are native paths.  The per-workgroup partial
 // sums of the statistics and backward passes are finished by the kernels of fx_dice.hip (fx_dice_int.h).
+// Every pass has two formulations, the general one (k_din_attn_*) and the "q split" (k_din_attn2_*, below);
+// the host side picks one per call in da_prepare and the instantiation in da_dispatch.  The two kernels of
+// a pass are still written out separately: building both from shared helpers was measured and not adopted
+// (profiles/din_attn_fold_ab.txt).
 #include "fx_dice_int.h"
 
 #include <stdlib.h>
+
+#include <type_traits>
 
 typedef float da_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -100,16 +106,10 @@ struct DaSmem {
     float Ps[POOL ? WAVES : 1][POOL ? 16 * DA_LDX : 1];   // a mask k per wave, [feature][position]
 };
 
-// W1 and the per-unit parameters into LDS (padding = neutral values); ends with a barrier
+// The per-unit parameters into LDS (padding = neutral values); the caller ends with a barrier
 template <class S>
-__device__ __forceinline__ void da_load_params(S& sm, const DinAttnArgs& a, int nthreads) {
-    const int KX = 4 * a.E, H = a.H;
-    for (int i = threadIdx.x; i < S::FP * S::LDW; i += nthreads) sm.W1s[i] = 0.f;
-    __syncthreads();
-    for (int i = threadIdx.x; i < H * KX; i += nthreads) {
-        const int n = i / KX, f = i - n * KX;
-        sm.W1s[f * S::LDW + n] = a.W1[i];
-    }
+__device__ __forceinline__ void da_fill_units(S& sm, const DinAttnArgs& a, int nthreads) {
+    const int H = a.H;
     for (int n = threadIdx.x; n < S::HP; n += nthreads) {
         float4 pa = make_float4(0.f, 0.f, 1.f, 0.f), pb = make_float4(0.f, 0.f, 0.f, 0.f);
         if (n < H) {
@@ -128,6 +128,19 @@ __device__ __forceinline__ void da_load_params(S& sm, const DinAttnArgs& a, int 
         sm.PA[n] = pa;
         sm.PB[n] = pb;
     }
+}
+
+// W1 and the per-unit parameters into LDS (padding = neutral values); ends with a barrier
+template <class S>
+__device__ __forceinline__ void da_load_params(S& sm, const DinAttnArgs& a, int nthreads) {
+    const int KX = 4 * a.E, H = a.H;
+    for (int i = threadIdx.x; i < S::FP * S::LDW; i += nthreads) sm.W1s[i] = 0.f;
+    __syncthreads();
+    for (int i = threadIdx.x; i < H * KX; i += nthreads) {
+        const int n = i / KX, f = i - n * KX;
+        sm.W1s[f * S::LDW + n] = a.W1[i];
+    }
+    da_fill_units(sm, a, nthreads);
     __syncthreads();
 }
 
@@ -789,24 +802,7 @@ __device__ __forceinline__ void da2_load_params(S& sm, const DinAttnArgs& a, int
         sm.Ws[(EC + e) * S::LDW + n] = wd;
         sm.Wqs[e * S::LDW + n] = wa + wc;
     }
-    for (int n = threadIdx.x; n < S::HP; n += nthreads) {
-        float4 pa = make_float4(0.f, 0.f, 1.f, 0.f), pb = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n < H) {
-            pa.x = a.b1 ? a.b1[n] : 0.f;
-            if (a.stats) {
-                pa.y = a.stats[n];
-                pa.z = rsqrtf(a.stats[H + n] + a.eps);
-            }
-            pa.w = a.alpha ? a.alpha[n] : 0.f;
-            pb.x = a.W2 ? a.W2[n] : 0.f;
-            if (a.sums) {
-                pb.y = a.sums[H + n] * a.inv_n;
-                pb.z = a.sums[2 * H + n] * a.inv_n;
-            }
-        }
-        sm.PA[n] = pa;
-        sm.PB[n] = pb;
-    }
+    da_fill_units(sm, a, nthreads);
     __syncthreads();
 }
 
@@ -846,10 +842,10 @@ __device__ __forceinline__ void da2_hq(const S& sm, const DinAttnArgs& a, uint32
 
 // sample bookkeeping of a wave that owns whole samples, L >= 32: c = positions of the tile that
 // belong to sample bcur (the rest opens bcur + 1)
-__device__ __forceinline__ int da2_cut(int nvalid, int L, int lcur) {
+__device__ __forceinline__ int da_cut(int nvalid, int L, int lcur) {
     return (L - lcur < nvalid) ? L - lcur : nvalid;
 }
-__device__ __forceinline__ void da2_advance(int nvalid, int L, int c, uint32_t& bcur, int& lcur) {
+__device__ __forceinline__ void da_advance(int nvalid, int L, int c, uint32_t& bcur, int& lcur) {
     if (lcur + c == L) {
         ++bcur;
         lcur = nvalid - c;
@@ -882,7 +878,7 @@ __global__ __launch_bounds__(256) void k_din_attn2_stats(DinAttnArgs a) {
     da_load_rows<EC, false, false>(a, R0 + l31, R0 + l31 < R1, half, cur);
     for (int64_t rb = R0; rb < R1; rb += 32) {
         const int nvalid = (R1 - rb < 32) ? (int)(R1 - rb) : 32;
-        const int c = da2_cut(nvalid, L, lcur);
+        const int c = da_cut(nvalid, L, lcur);
         float hq[2][NB];
         da2_hq<NB, EC>(sm, a, bcur, l31, hq);
         da2_store_x<EC>(Xs, l31, half, cur);
@@ -900,7 +896,7 @@ __global__ __launch_bounds__(256) void k_din_attn2_stats(DinAttnArgs a) {
                     s2[j] = fmaf(z, z, s2[j]);
                 }
             }
-        da2_advance(nvalid, L, c, bcur, lcur);
+        da_advance(nvalid, L, c, bcur, lcur);
     }
     __syncthreads();
     float* red = &sm.Xs[0][0];                     // [4 waves][2][HP]
@@ -946,7 +942,7 @@ __global__ __launch_bounds__(256) void k_din_attn2_fwd(DinAttnArgs a) {
         const int64_t row = rb + l31;
         const bool valid = row < R1;
         const int nvalid = (R1 - rb < 32) ? (int)(R1 - rb) : 32;
-        const int c = da2_cut(nvalid, L, lcur);
+        const int c = da_cut(nvalid, L, lcur);
         const float m = cur.m;
         {
             float hq[2][NB];
@@ -1023,7 +1019,7 @@ void k_din_attn2_bwd_sums(DinAttnArgs a) {
         const int64_t row = rb + l31;
         const bool valid = row < R1;
         const int nvalid = (R1 - rb < 32) ? (int)(R1 - rb) : 32;
-        const int c = da2_cut(nvalid, L, lcur);
+        const int c = da_cut(nvalid, L, lcur);
         float hq[2][NB];
         da2_hq<NB, EC>(sm, a, bcur, l31, hq);
         da2_store_x<EC>(Xs, l31, half, cur);
@@ -1058,7 +1054,7 @@ void k_din_attn2_bwd_sums(DinAttnArgs a) {
                 sw[j] = fmaf(dar, y, sw[j]);
             }
         }
-        da2_advance(nvalid, L, c, bcur, lcur);
+        da_advance(nvalid, L, c, bcur, lcur);
     }
     sb2 = fx_wave_sum(sb2);
     __syncthreads();
@@ -1129,7 +1125,7 @@ void k_din_attn2_bwd(DinAttnArgs a) {
         const int64_t row = rb + l31;
         const bool valid = row < R1;
         const int nvalid = (R1 - rb < 32) ? (int)(R1 - rb) : 32;
-        const int c = da2_cut(nvalid, L, lcur);
+        const int c = da_cut(nvalid, L, lcur);
         const uint32_t b = cur.b;
         const int l = cur.l;
         const float da_i = da_n;
@@ -1330,8 +1326,8 @@ static DaGeom da_geom(int64_t B, int32_t L, bool qsplit = false) {
     // the same number of tiles (measured: profiles/r02_din_attn_passes.txt)
     static const int64_t cap_flat = da_env_cap("FX_DIN_ATTN_WAVES", 2048);
     static const int64_t cap_fwd = da_env_cap("FX_DIN_ATTN_FWD_WAVES", 2048);
-    static const int64_t cap_bwd = da_env_cap("FX_DIN_ATTN_BWD_WAVES", 1536);
-    static const int64_t cap_bwd2 = da_env_cap("FX_DIN_ATTN_BWD_WAVES", 2048);   // q split: 4 WGs per CU
+    static const int64_t env_bwd = da_env_cap("FX_DIN_ATTN_BWD_WAVES", 0);
+    const int64_t cap_bwd = env_bwd ? env_bwd : (qsplit ? 2048 : 1536);   // q split: 4 WGs per CU
     DaGeom g;
     g.n_rows = B * L;
     // statistics passes: 32-position tiles dealt to <= cap_flat waves, no per-sample reduction
@@ -1343,8 +1339,7 @@ static DaGeom da_geom(int64_t B, int32_t L, bool qsplit = false) {
     const int64_t Sf = fx_ceil_div(B, cap_fwd) > 1 ? fx_ceil_div(B, cap_fwd) : 1;
     g.rpw_fwd = Sf * L;
     g.wgs_fwd = fx_ceil_div(fx_ceil_div(B, Sf), 4);
-    const int64_t cb = qsplit ? cap_bwd2 : cap_bwd;
-    const int64_t Sb = fx_ceil_div(B, cb) > 1 ? fx_ceil_div(B, cb) : 1;
+    const int64_t Sb = fx_ceil_div(B, cap_bwd) > 1 ? fx_ceil_div(B, cap_bwd) : 1;
     g.rpw_bwd = Sb * L;
     g.wgs_bwd = fx_ceil_div(fx_ceil_div(B, Sb), 2);      // 2 waves per workgroup (LDS)
     if (qsplit) {                                        // every pass owns whole samples
@@ -1366,83 +1361,114 @@ extern "C" int64_t fx_din_attn_workspace_floats(int64_t B, int32_t L, int32_t E,
     return need;
 }
 
-static int da_check(const char* who, const float* q, const float* K, int64_t B, int32_t L, int32_t E,
-                    int32_t H, const float* W1) {
-    FX_CHECK_ARG(B >= 1 && L >= 1 && E >= 1 && E <= 16 && H >= 1 && H <= 64,
-                 "%s: bad sizes (1 <= E <= 16, 1 <= H <= 64)", who);
-    FX_CHECK_ARG(B * (int64_t)L < ((int64_t)1 << 31), "%s: B * L too large", who);
-    FX_CHECK_ARG(q && K && W1, "%s: null pointer", who);
-    return FX_OK;
-}
-
 static bool da_al16(const void* p, int64_t ld0, int64_t ld1 = 0) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld0 % 4 == 0 && ld1 % 4 == 0;
 }
 
-static void da_fill(DinAttnArgs& a, const float* q, int64_t q_ld, const float* K, int64_t k_ldb,
-                    int64_t k_ldl, int64_t B, int32_t L, int32_t E, int32_t H, const float* W1,
-                    const float* b1) {
+enum DaPass { DA_STATS, DA_FWD, DA_BWD_SUMS, DA_BWD };
+
+struct DaGradRows {          // the row operands only the backward passes have (null: the pass has none)
+    const float* dout = nullptr;
+    int64_t dout_ld = 0;
+    float* dK = nullptr;
+    int64_t dk_ldb = 0, dk_ldl = 0;
+};
+
+struct DaPlan {
+    DinAttnArgs a;
+    bool qsplit;
+    int64_t wgs;             // workgroups of the pass
+};
+
+// What the four entry points share: the size checks, the arguments every pass has, whether rows may
+// be moved with 16-byte accesses (every row operand the pass has must allow it), the formulation and
+// the geometry of the pass.
+static int da_prepare(DaPass pass, const char* who, const float* q, int64_t q_ld, const float* K,
+                      int64_t k_ldb, int64_t k_ldl, int64_t B, int32_t L, int32_t E, int32_t H,
+                      const float* W1, const float* b1, const DaGradRows& g_, DaPlan& p) {
+    FX_CHECK_ARG(B >= 1 && L >= 1 && E >= 1 && E <= 16 && H >= 1 && H <= 64,
+                 "%s: bad sizes (1 <= E <= 16, 1 <= H <= 64)", who);
+    FX_CHECK_ARG(B * (int64_t)L < ((int64_t)1 << 31), "%s: B * L too large", who);
+    FX_CHECK_ARG(q && K && W1, "%s: null pointer", who);
+    DinAttnArgs& a = p.a;
     memset(&a, 0, sizeof(a));
     a.q = q; a.q_ld = q_ld; a.K = K; a.k_ldb = k_ldb; a.k_ldl = k_ldl;
     a.n_rows = B * L; a.nb = (int32_t)B; a.L = L; a.E = E; a.H = H; a.W1 = W1; a.b1 = b1;
-    a.vec = (E % 8 == 0) && da_al16(q, q_ld) && da_al16(K, k_ldb, k_ldl);
-}
-
-// (NB, FB, EC): hidden blocks, feature blocks, compile-time E (16 / 8 with 16-byte rows, else 0)
-#define DA_LAUNCH(KERNEL, NB_, FB_, EC_, THREADS, GRID, STREAM, ARGS) \
-    hipLaunchKernelGGL((KERNEL<NB_, FB_, EC_>), dim3((unsigned)(GRID)), dim3(THREADS), 0, STREAM, ARGS)
-#define DA_DISPATCH_NB(KERNEL, NB_, THREADS, GRID, STREAM, ARGS)                                  \
-    do {                                                                                          \
-        if (ARGS.vec && ARGS.E == 16) DA_LAUNCH(KERNEL, NB_, 2, 16, THREADS, GRID, STREAM, ARGS); \
-        else if (ARGS.vec && ARGS.E == 8) DA_LAUNCH(KERNEL, NB_, 1, 8, THREADS, GRID, STREAM, ARGS); \
-        else if (4 * ARGS.E <= 32) DA_LAUNCH(KERNEL, NB_, 1, 0, THREADS, GRID, STREAM, ARGS);     \
-        else DA_LAUNCH(KERNEL, NB_, 2, 0, THREADS, GRID, STREAM, ARGS);                           \
-    } while (0)
-#define DA_DISPATCH(KERNEL, THREADS, GRID, STREAM, ARGS)                                          \
-    do {                                                                                          \
-        if (ARGS.H <= 32) DA_DISPATCH_NB(KERNEL, 1, THREADS, GRID, STREAM, ARGS);                 \
-        else DA_DISPATCH_NB(KERNEL, 2, THREADS, GRID, STREAM, ARGS);                              \
-    } while (0)
-
-// the q-split formulation: E = 8 / 16 with 16-byte rows, L >= 32 (FX_DIN_ATTN_QSPLIT=0: never)
-static bool da2_ok(const DinAttnArgs& a) {
+    a.dout = g_.dout; a.dout_ld = g_.dout_ld; a.dK = g_.dK; a.dk_ldb = g_.dk_ldb; a.dk_ldl = g_.dk_ldl;
+    a.vec = (E % 8 == 0) && da_al16(q, q_ld) && da_al16(K, k_ldb, k_ldl) &&
+            (!g_.dout || da_al16(g_.dout, g_.dout_ld)) && (!g_.dK || da_al16(g_.dK, g_.dk_ldb, g_.dk_ldl));
+    // the q-split formulation: E = 8 / 16 with 16-byte rows, L >= 32 (FX_DIN_ATTN_QSPLIT=0: never)
     static const bool on = fx_env_int("FX_DIN_ATTN_QSPLIT", 1) != 0;
-    return on && a.vec && (a.E == 16 || a.E == 8) && a.L >= 32;
+    p.qsplit = on && a.vec && (E == 16 || E == 8) && L >= 32;
+    const DaGeom g = da_geom(B, L, p.qsplit);
+    a.rows_per_wave = pass == DA_FWD ? g.rpw_fwd : pass == DA_BWD ? g.rpw_bwd : g.rpw_flat;
+    p.wgs = pass == DA_FWD ? g.wgs_fwd : pass == DA_BWD ? g.wgs_bwd : g.wgs_flat;
+    return FX_OK;
 }
-#define DA2_LAUNCH(KERNEL, THREADS, GRID, STREAM, ARGS)                                            \
-    do {                                                                                           \
-        if (ARGS.H <= 32 && ARGS.E == 16)                                                          \
-            hipLaunchKernelGGL((KERNEL<1, 16>), dim3((unsigned)(GRID)), dim3(THREADS), 0, STREAM, ARGS); \
-        else if (ARGS.H <= 32)                                                                     \
-            hipLaunchKernelGGL((KERNEL<1, 8>), dim3((unsigned)(GRID)), dim3(THREADS), 0, STREAM, ARGS); \
-        else if (ARGS.E == 16)                                                                     \
-            hipLaunchKernelGGL((KERNEL<2, 16>), dim3((unsigned)(GRID)), dim3(THREADS), 0, STREAM, ARGS); \
-        else                                                                                       \
-            hipLaunchKernelGGL((KERNEL<2, 8>), dim3((unsigned)(GRID)), dim3(THREADS), 0, STREAM, ARGS); \
-    } while (0)
+
+// The instantiation of a pass: (NB, FB, EC) = hidden blocks, feature blocks, compile-time E (16 / 8 with
+// 16-byte rows, else 0) of the general formulation, (NB, EC) of the q split.
+template <DaPass PASS>
+static void da_dispatch(const DaPlan& p, hipStream_t s) {
+    const DinAttnArgs& a = p.a;
+    const dim3 grid((unsigned)p.wgs), block(PASS == DA_BWD ? 128 : 256);
+    auto general = [&](auto nb, auto fb, auto ec) {
+        constexpr int NB = decltype(nb)::value, FB = decltype(fb)::value, EC = decltype(ec)::value;
+        if constexpr (PASS == DA_STATS)
+            hipLaunchKernelGGL((k_din_attn_stats<NB, FB, EC>), grid, block, 0, s, a);
+        else if constexpr (PASS == DA_FWD)
+            hipLaunchKernelGGL((k_din_attn_fwd<NB, FB, EC>), grid, block, 0, s, a);
+        else if constexpr (PASS == DA_BWD_SUMS)
+            hipLaunchKernelGGL((k_din_attn_bwd_sums<NB, FB, EC>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((k_din_attn_bwd<NB, FB, EC>), grid, block, 0, s, a);
+    };
+    auto qsplit = [&](auto nb, auto ec) {
+        constexpr int NB = decltype(nb)::value, EC = decltype(ec)::value;
+        if constexpr (PASS == DA_STATS)
+            hipLaunchKernelGGL((k_din_attn2_stats<NB, EC>), grid, block, 0, s, a);
+        else if constexpr (PASS == DA_FWD)
+            hipLaunchKernelGGL((k_din_attn2_fwd<NB, EC>), grid, block, 0, s, a);
+        else if constexpr (PASS == DA_BWD_SUMS)
+            hipLaunchKernelGGL((k_din_attn2_bwd_sums<NB, EC>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((k_din_attn2_bwd<NB, EC>), grid, block, 0, s, a);
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I8 = std::integral_constant<int, 8>;
+    using I16 = std::integral_constant<int, 16>;
+    auto with_nb = [&](auto nb) {
+        if (p.qsplit && a.E == 16) qsplit(nb, I16());
+        else if (p.qsplit) qsplit(nb, I8());
+        else if (a.vec && a.E == 16) general(nb, I2(), I16());
+        else if (a.vec && a.E == 8) general(nb, I1(), I8());
+        else if (4 * a.E <= 32) general(nb, I1(), I0());
+        else general(nb, I2(), I0());
+    };
+    if (a.H <= 32) with_nb(I1());
+    else with_nb(I2());
+}
 
 extern "C" int fx_din_attn_stats(const float* q, int64_t q_ld, const float* K, int64_t k_ldb,
                                  int64_t k_ldl, int64_t B, int32_t L, int32_t E, const float* W1,
                                  const float* b1, int32_t H, float* sums, float* workspace,
                                  float* stats, float momentum, float* running_mean, float* running_var,
                                  int64_t* num_batches_tracked, fx_stream_t stream) {
-    int rc = da_check("fx_din_attn_stats", q, K, B, L, E, H, W1);
+    DaPlan p;
+    int rc = da_prepare(DA_STATS, "fx_din_attn_stats", q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1,
+                        DaGradRows(), p);
     if (rc != FX_OK) return rc;
     FX_CHECK_ARG(sums && workspace, "fx_din_attn_stats: null pointer");
-    DinAttnArgs a;
-    da_fill(a, q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1);
-    const bool q2 = da2_ok(a);
-    const DaGeom g = da_geom(B, L, q2);
-    a.rows_per_wave = g.rpw_flat;
-    a.partial = workspace;
+    p.a.partial = workspace;
     hipStream_t s = fx_hip_stream(stream);
-    if (q2) DA2_LAUNCH(k_din_attn2_stats, 256, g.wgs_flat, s, a);
-    else DA_DISPATCH(k_din_attn_stats, 256, g.wgs_flat, s, a);
+    da_dispatch<DA_STATS>(p, s);
     if (stats)      // one rank: the sums ARE the batch's — statistics in the same launch
-        fx_chunks_stats_launch(workspace, (int)g.wgs_flat, H, B * (int64_t)L, momentum, sums, stats,
+        fx_chunks_stats_launch(workspace, (int)p.wgs, H, B * (int64_t)L, momentum, sums, stats,
                                running_mean, running_var, num_batches_tracked, s);
     else
-        fx_chunks_sum_launch(workspace, (int)g.wgs_flat, 2, H, sums, s);
+        fx_chunks_sum_launch(workspace, (int)p.wgs, 2, H, sums, s);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }
@@ -1453,19 +1479,15 @@ extern "C" int fx_din_attn_fwd(const float* q, int64_t q_ld, const float* K, int
                                const float* stats, const float* W2, const float* b2,
                                const int32_t* mask, int64_t mask_ld, float* a_out, float* out,
                                int64_t out_ld, fx_stream_t stream) {
-    int rc = da_check("fx_din_attn_fwd", q, K, B, L, E, H, W1);
+    DaPlan p;
+    int rc = da_prepare(DA_FWD, "fx_din_attn_fwd", q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1,
+                        DaGradRows(), p);
     if (rc != FX_OK) return rc;
     FX_CHECK_ARG(alpha && stats && W2 && a_out && out, "fx_din_attn_fwd: null pointer");
-    DinAttnArgs a;
-    da_fill(a, q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1);
-    const bool q2 = da2_ok(a);
-    const DaGeom g = da_geom(B, L, q2);
-    a.rows_per_wave = g.rpw_fwd;
+    DinAttnArgs& a = p.a;
     a.alpha = alpha; a.eps = eps; a.stats = stats; a.W2 = W2; a.b2 = b2;
     a.mask = mask; a.m_ld = mask_ld; a.a_out = a_out; a.out = out; a.out_ld = out_ld;
-    hipStream_t s = fx_hip_stream(stream);
-    if (q2) DA2_LAUNCH(k_din_attn2_fwd, 256, g.wgs_fwd, s, a);
-    else DA_DISPATCH(k_din_attn_fwd, 256, g.wgs_fwd, s, a);
+    da_dispatch<DA_FWD>(p, fx_hip_stream(stream));
     FX_CHECK_LAUNCH();
     return FX_OK;
 }
@@ -1476,23 +1498,19 @@ extern "C" int fx_din_attn_bwd_sums(const float* q, int64_t q_ld, const float* K
                                     const float* stats, const float* W2, const int32_t* mask,
                                     int64_t mask_ld, const float* dout, int64_t dout_ld, float* da,
                                     float* sums5, float* workspace, fx_stream_t stream) {
-    int rc = da_check("fx_din_attn_bwd_sums", q, K, B, L, E, H, W1);
+    DaPlan p;
+    int rc = da_prepare(DA_BWD_SUMS, "fx_din_attn_bwd_sums", q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1,
+                        b1, DaGradRows{dout, dout_ld}, p);
     if (rc != FX_OK) return rc;
     FX_CHECK_ARG(alpha && stats && W2 && dout && da && sums5 && workspace,
                  "fx_din_attn_bwd_sums: null pointer");
-    DinAttnArgs a;
-    da_fill(a, q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1);
-    a.vec = a.vec && da_al16(dout, dout_ld);
-    const bool q2 = da2_ok(a);
-    const DaGeom g = da_geom(B, L, q2);
-    a.rows_per_wave = g.rpw_flat;
+    DinAttnArgs& a = p.a;
     a.alpha = alpha; a.eps = eps; a.stats = stats; a.W2 = W2;
-    a.mask = mask; a.m_ld = mask_ld; a.dout = dout; a.dout_ld = dout_ld; a.da_out = da;
+    a.mask = mask; a.m_ld = mask_ld; a.da_out = da;
     a.partial = workspace;
     hipStream_t s = fx_hip_stream(stream);
-    if (q2) DA2_LAUNCH(k_din_attn2_bwd_sums, 256, g.wgs_flat, s, a);
-    else DA_DISPATCH(k_din_attn_bwd_sums, 256, g.wgs_flat, s, a);
-    fx_chunks_sum_launch(workspace, (int)g.wgs_flat, 5, H, sums5, s);
+    da_dispatch<DA_BWD_SUMS>(p, s);
+    fx_chunks_sum_launch(workspace, (int)p.wgs, 5, H, sums5, s);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }
@@ -1506,30 +1524,25 @@ extern "C" int fx_din_attn_bwd(const float* q, int64_t q_ld, const float* K, int
                                const float* sums5, int64_t n_total, float* dq, int64_t dq_ld,
                                int32_t dq_accumulate, float* dK, int64_t dk_ldb, int64_t dk_ldl,
                                float* dW1b1, float* workspace, fx_stream_t stream) {
-    int rc = da_check("fx_din_attn_bwd", q, K, B, L, E, H, W1);
+    DaPlan p;
+    int rc = da_prepare(DA_BWD, "fx_din_attn_bwd", q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1,
+                        DaGradRows{dout, dout_ld, dK, dk_ldb, dk_ldl}, p);
     if (rc != FX_OK) return rc;
     FX_CHECK_ARG(alpha && stats && W2 && a_logit && dout && da && dq && dK && dW1b1 && workspace,
                  "fx_din_attn_bwd: null pointer");
     FX_CHECK_ARG(!training || (sums5 && n_total >= B * (int64_t)L),
                  "fx_din_attn_bwd: training mode needs the backward sums and the global row count");
-    DinAttnArgs a;
-    da_fill(a, q, q_ld, K, k_ldb, k_ldl, B, L, E, H, W1, b1);
-    a.vec = a.vec && da_al16(dout, dout_ld) && da_al16(dK, dk_ldb, dk_ldl);
-    const bool q2 = da2_ok(a);
-    const DaGeom g = da_geom(B, L, q2);
-    a.rows_per_wave = g.rpw_bwd;
+    DinAttnArgs& a = p.a;
     a.alpha = alpha; a.eps = eps; a.stats = stats; a.W2 = W2;
-    a.mask = mask; a.m_ld = mask_ld; a.a_in = a_logit; a.dout = dout; a.dout_ld = dout_ld;
-    a.da_in = da;
+    a.mask = mask; a.m_ld = mask_ld; a.a_in = a_logit; a.da_in = da;
     a.sums = training ? sums5 : nullptr;
     a.inv_n = training ? 1.f / (float)n_total : 0.f;
-    a.dq = dq; a.dq_ld = dq_ld; a.dq_acc = dq_accumulate; a.dK = dK; a.dk_ldb = dk_ldb; a.dk_ldl = dk_ldl;
+    a.dq = dq; a.dq_ld = dq_ld; a.dq_acc = dq_accumulate;
     a.partial = workspace;
     hipStream_t s = fx_hip_stream(stream);
-    if (q2) DA2_LAUNCH(k_din_attn2_bwd, 128, g.wgs_bwd, s, a);
-    else DA_DISPATCH(k_din_attn_bwd, 128, g.wgs_bwd, s, a);
+    da_dispatch<DA_BWD>(p, s);
     const int64_t tot = (int64_t)H * 4 * E + H;
-    fx_chunks_sum_launch(workspace, (int)g.wgs_bwd, 1, tot, dW1b1, s);
+    fx_chunks_sum_launch(workspace, (int)p.wgs, 1, tot, dW1b1, s);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }

@@ -97,6 +97,7 @@ def _close(got, ref, tol, what):
 SHAPES = [(64, 50, 16, 64), (7, 3, 4, 16), (33, 50, 8, 36), (5, 1, 10, 64), (300, 20, 16, 32),
           (50, 32, 16, 32), (41, 97, 8, 64), (19, 33, 16, 64), (2, 64, 16, 64),
           (3, 32, 8, 7),
+          (6, 5, 12, 20), (9, 4, 8, 40), (5, 3, 4, 33),     # <1,2,0>, <2,1,8>, <2,1,0>: no other shape runs them
           (129, 7, 12, 64), (4096, 50, 16, 64)]
 
 
