@@ -6,6 +6,7 @@ otherwise — there is no CPU path.
 """
 import ctypes as C
 import os
+from collections import OrderedDict
 
 import torch
 
@@ -1084,6 +1085,40 @@ def binary_metrics(y_pred, y_true):
                          "case.")
     auc = (s2 - n_pos * (n_pos + 1)) / (2 * n_pos * n_neg)     # exact integers, one rounding
     return float(ll.item()) / n, auc
+
+
+GROUP_METRIC_MAX_KS = 8
+
+
+def group_metrics(y_pred, y_true, group_key, key_bits, ndcg_ks=()):
+    """{"gAUC", "avgAUC", "MRR", "NDCG(k=K)" for K in ndcg_ks} -> float64 of float32 device vectors and a
+    uint32 group key per sample (an int32 tensor holding the bits; only the low key_bits bits are read), as
+    rank_model.evaluate_metrics computes them on the host.  Among equal predictions of a group the sample that
+    came later in the input ranks first.  A metric whose weights sum to 0 is nan.  One host sync (reads
+    2 * (3 + len(ndcg_ks)) + 1 doubles)."""
+    lib = _lib.load()
+    _need_cuda(y_pred, "y_pred")
+    y_pred = y_pred.reshape(-1).contiguous().float()
+    y_true = y_true.reshape(-1).contiguous().float()
+    group_key = group_key.reshape(-1).contiguous()
+    if group_key.dtype != torch.int32 or group_key.device != y_pred.device:
+        raise _lib.FxError("group_metrics: group_key must be an int32 tensor (uint32 bits) on %s, got %s on %s"
+                           % (y_pred.device, group_key.dtype, group_key.device))
+    n = y_pred.numel()
+    if y_true.numel() != n or group_key.numel() != n:
+        raise _lib.FxError("group_metrics: %d predictions, %d labels, %d group keys"
+                           % (n, y_true.numel(), group_key.numel()))
+    ks = [int(k) for k in ndcg_ks]
+    nbytes = int(lib.fx_group_metrics_workspace_bytes(n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=y_pred.device)
+    out = torch.empty(2 * (3 + len(ks)) + 1, dtype=torch.float64, device=y_pred.device)
+    ks_arr = (C.c_int32 * max(len(ks), 1))(*ks)
+    check(lib.fx_group_metrics(ptr(y_pred), ptr(y_true), ptr(group_key), int(key_bits), n, ks_arr, len(ks),
+                               ptr(ws), nbytes, ptr(out), stream_ptr(y_pred.device)), "fx_group_metrics")
+    sums = out.tolist()
+    names = ["gAUC", "avgAUC", "MRR"] + ["NDCG(k=%d)" % k for k in ks]
+    return OrderedDict((name, sums[2 * s] / sums[2 * s + 1] if sums[2 * s + 1] != 0.0 else float("nan"))
+                       for s, name in enumerate(names))
 
 
 # ---- fused sparse front end / back end (csrc/fx_fused.hip) ----------------------------------------

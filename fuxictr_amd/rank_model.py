@@ -12,6 +12,7 @@ What changed underneath train_step (rank_model.py:307-323):
 """
 import logging
 import os
+import re
 import sys
 from collections import OrderedDict
 
@@ -38,20 +39,109 @@ class Monitor(object):
         return list(self.kv_pairs.keys())
 
 
+_PLAIN_METRICS = ("logloss", "binary_crossentropy", "AUC")
+_NDCG_RE = re.compile(r"^NDCG\((?:k=)?([0-9]+)\)$")
+
+
+def is_group_metric(metric):
+    return metric in ("gAUC", "avgAUC", "MRR") or metric.startswith("NDCG")
+
+
+def ndcg_cutoff(metric):
+    """K of `NDCG(k=K)` / `NDCG(K)`, K >= 1 (parsed, never evaluated).  The reference evals the name
+    (metrics.py:62): a bare `NDCG` is the class itself and fails there too."""
+    m = _NDCG_RE.match(metric)
+    if m is None or int(m.group(1)) < 1:
+        raise NotImplementedError("metrics={} not implemented.".format(metric))
+    return int(m.group(1))
+
+
+def group_keys(group_id):
+    """Host ids of any dtype -> (uint32 keys, bits in use) for ops.group_metrics: id - min when the ids are
+    integers spanning less than 2^32, their index among the sorted distinct ids otherwise."""
+    ids = np.asarray(group_id).reshape(-1)
+    keys = None
+    if ids.dtype.kind in "iu" and ids.size:
+        lo, hi = int(ids.min()), int(ids.max())
+        if hi - lo < 2 ** 32:
+            keys = (ids - ids.dtype.type(lo)).astype(np.uint32)
+    if keys is None:
+        keys = np.unique(ids, return_inverse=True)[1].reshape(-1).astype(np.uint32)
+    return keys, max(1, int(keys.max()).bit_length() if keys.size else 1)
+
+
+def group_metric_values(y_true, y_pred, group_id, metrics):
+    """gAUC / avgAUC / MRR / NDCG(k=K) as metrics.py:57-189 defines them, in numpy (no pandas, no pool).
+    Per group of n samples with n+ positives (y > 0.5): gAUC (AUC n, n) and avgAUC (AUC, 1) over the groups
+    with 0 < n+ < n; MRR sum y / rank / (n+ + 1e-12) and NDCG DCG@K / (IDCG@K + 1e-12) over every group, weight
+    1; metric = sum value / sum weight (nan for 0 / 0).  rank: 1-based position in descending prediction
+    order — the reference's argsort()[::-1] is unstable, so ties are settled here: among equal predictions the
+    sample that came LATER in the input ranks first (the stable ascending order, reversed).  AUC: Mann-Whitney
+    with average ranks for ties, exact integers and one division, as fx_group_metrics computes it."""
+    y = np.asarray(y_true).reshape(-1) > 0.5
+    p = np.asarray(y_pred).reshape(-1)
+    g = np.asarray(group_id).reshape(-1)
+    n = y.size
+    assert p.size == n and g.size == n and n > 0, (n, p.size, g.size)
+    order = np.argsort(p, kind="stable")
+    order = order[np.argsort(g[order], kind="stable")]
+    y, p, g = y[order].astype(np.int64), p[order], g[order]
+    ghead = np.r_[True, g[1:] != g[:-1]]
+    rhead = ghead | np.r_[True, p[1:] != p[:-1]]
+    gstart, rstart = np.flatnonzero(ghead), np.flatnonzero(rhead)
+    gend, rend = np.r_[gstart[1:], n], np.r_[rstart[1:], n]
+    grp, run = np.cumsum(ghead) - 1, np.cumsum(rhead) - 1
+    size, npos = gend - gstart, np.add.reduceat(y, gstart)
+    # twice the average rank (ascending, inside the group) of the tie run [R0, R1): R0 + R1 + 1 - 2 S
+    s2 = np.add.reduceat(y * (rstart[run] + rend[run] + 1 - 2 * gstart[grp]), gstart)
+    mixed = (npos > 0) & (npos < size)
+    auc = ((s2 - npos * (npos + 1))[mixed].astype(np.float64)
+           / (2 * npos * (size - npos))[mixed].astype(np.float64))
+    rank = gend[grp] - np.arange(n)
+    yf = y.astype(np.float64)
+
+    def ratio(value, weight):
+        return float(value) / float(weight) if weight != 0 else float("nan")
+    out = OrderedDict()
+    for metric in metrics:
+        if metric == "gAUC":
+            out[metric] = ratio((auc * size[mixed]).sum(), size[mixed].sum())
+        elif metric == "avgAUC":
+            out[metric] = ratio(auc.sum(), mixed.sum())
+        elif metric == "MRR":
+            out[metric] = ratio((np.add.reduceat(yf / rank, gstart) / (npos + 1e-12)).sum(), size.size)
+        else:
+            k = ndcg_cutoff(metric)
+            dcg = np.add.reduceat(np.where(rank <= k, yf / np.log2(rank + 1.0), 0.0), gstart)
+            top = int(min(k, npos.max()))
+            idcg = np.r_[0.0, np.cumsum(1.0 / np.log2(np.arange(1, top + 1) + 1.0))][np.minimum(npos, k)]
+            out[metric] = ratio((dcg / (idcg + 1e-12)).sum(), size.size)
+    return out
+
+
 def evaluate_metrics(y_true, y_pred, metrics, group_id=None):
-    """logloss / AUC through scikit-learn on float64, exactly as the reference (metrics.py:49-51),
-    so "AUC to 4 decimals" compares like with like.  Group metrics are out of scope (SURVEY §2 #18)."""
+    """metrics.py:26-78.  logloss / AUC through scikit-learn on float64, exactly as the reference
+    (metrics.py:49-51), so "AUC to 4 decimals" compares like with like; the group metrics through
+    group_metric_values."""
     from sklearn.metrics import log_loss, roc_auc_score
     out = OrderedDict()
+    group_metrics = []
     for metric in metrics:
         if metric in ["logloss", "binary_crossentropy"]:
             out[metric] = log_loss(y_true, y_pred)
         elif metric == "AUC":
             out[metric] = roc_auc_score(y_true, y_pred)
-        elif metric in ["gAUC", "avgAUC", "MRR"] or metric.startswith("NDCG"):
-            raise NotImplementedError("metrics={} not implemented.".format(metric))
+        elif is_group_metric(metric):
+            out[metric] = 0
+            group_metrics.append(metric)
         else:
             raise ValueError("metric={} not supported.".format(metric))
+    if group_metrics:
+        assert group_id is not None, "group_index is required."
+        for metric in group_metrics:
+            if metric.startswith("NDCG"):
+                ndcg_cutoff(metric)
+        out.update(group_metric_values(y_true, y_pred, group_id, group_metrics))
     return out
 
 
@@ -790,8 +880,9 @@ class BaseModel(nn.Module):
                 break
         self.optimizer.check_errors()
 
-    def _predict_batches(self, data_generator, with_labels):
-        """eval-mode forward over a generator -> (list of device predictions, list of labels)."""
+    def _predict_batches(self, data_generator, with_labels, group_ids=None):
+        """eval-mode forward over a generator -> (list of device predictions, list of labels); the host group
+        ids of every batch are appended to `group_ids` when it is a list."""
         self.eval()
         preds, labels = [], []
         with torch.no_grad():
@@ -800,16 +891,23 @@ class BaseModel(nn.Module):
                 if with_labels:
                     # clone: a device loader may hand out views of a buffer it reuses
                     labels.append(self.get_labels(batch).reshape(-1).clone())
+                if group_ids is not None:
+                    group_ids.append(np.asarray(self.get_group_id(batch)).reshape(-1))
         return preds, labels
 
     def evaluate(self, data_generator, metrics=None):
         """rank_model.py:350-381.  logloss / AUC are computed on the device (fx_binary_metrics: one
-        sort + exact rank sums over all predictions) unless group metrics are involved, in which
-        case the reference's host path (float64 + scikit-learn) is used."""
+        sort + exact rank sums over all predictions), and so are gAUC / avgAUC / MRR / NDCG(k=K) when one of
+        them is asked for (fx_group_metrics: the group ids are mapped to uint32 keys on the host and uploaded
+        once).  With `group_id` set and no group metric asked for, or with device_metrics off, the reference's
+        host path (float64 + scikit-learn, group metrics in numpy) is used."""
         wanted = list(self.validation_metrics if metrics is None else metrics)
         groups = self.feature_map.group_id is not None
-        on_device = (self._device_metrics and self.device.type == "cuda" and not groups and wanted
-                     and set(wanted) <= {"logloss", "binary_crossentropy", "AUC"})
+        device_ok = self._device_metrics and self.device.type == "cuda" and wanted
+        on_device = (device_ok and not groups and set(wanted) <= set(_PLAIN_METRICS))
+        group_wanted = [m for m in wanted if is_group_metric(m)]
+        groups_on_device = (device_ok and groups and group_wanted
+                            and all(m in _PLAIN_METRICS or is_group_metric(m) for m in wanted))
         if self._dist is not None:
             # every rank scores the GLOBAL validation set (its shard's predictions are gathered),
             # so checkpoint_and_earlystop takes the same decision everywhere
@@ -821,6 +919,26 @@ class BaseModel(nn.Module):
                 preds, labels = (self._dist.all_gather_cat(t) for t in (preds, labels))
             ll, auc = ops.binary_metrics(preds, labels)
             val_logs = OrderedDict((m, auc if m == "AUC" else ll) for m in wanted)
+        elif groups_on_device:
+            ks = sorted(set(ndcg_cutoff(m) for m in group_wanted if m.startswith("NDCG")))
+            g_host = []
+            preds, labels = self._predict_batches(data_generator, True, g_host)
+            preds, labels, g_all = torch.cat(preds), torch.cat(labels), np.concatenate(g_host)
+            if self._dist is not None:
+                preds, labels = (self._dist.all_gather_cat(t) for t in (preds, labels))
+                # the RAW ids are gathered, so that every rank maps them to the same keys
+                g_all = self._dist.all_gather_cat(torch.from_numpy(g_all)).numpy()
+            keys, key_bits = group_keys(g_all)
+            keys = torch.from_numpy(keys.view(np.int32)).to(preds.device)
+            got = OrderedDict()
+            for j in range(0, max(len(ks), 1), ops.GROUP_METRIC_MAX_KS):
+                got.update(ops.group_metrics(preds, labels, keys, key_bits,
+                                             ks[j:j + ops.GROUP_METRIC_MAX_KS]))
+            if any(m in _PLAIN_METRICS for m in wanted):
+                got["logloss"], got["AUC"] = ops.binary_metrics(preds, labels)
+                got["binary_crossentropy"] = got["logloss"]
+            val_logs = OrderedDict((m, got["NDCG(k=%d)" % ndcg_cutoff(m)] if m.startswith("NDCG") else got[m])
+                                   for m in wanted)
         else:
             self.eval()
             p_host, y_host, g_host = [], [], []

@@ -700,6 +700,26 @@ int fx_binary_metrics(const float* y_pred, const float* y_true, int64_t n, void*
                       fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * On-device group metrics (csrc/fx_group_metrics.hip): gAUC, avgAUC, MRR and NDCG@K of
+ * evaluate_metrics (metrics.py:57-77: pandas.groupby + a process pool; gAUC metrics.py:115-130,
+ * avgAUC metrics.py:99-113, MRR metrics.py:132-146, NDCG metrics.py:149-189) over n predictions
+ * resident on the device.  Positive: y_true > 0.5.  group_key: uint32 per sample, only its low
+ * key_bits bits are read (samples with equal keys form a group).  rank = 1-based position in
+ * descending prediction order inside the group; among equal predictions the sample that came
+ * LATER in the input ranks first.  AUC per group: Mann-Whitney with average ranks for ties, exact
+ * integers + one fp64 division.
+ *   out[2 s], out[2 s + 1] = sum over the groups of (value, weight) of slot s:
+ *     s = 0 gAUC, 1 avgAUC, 2 MRR, 3 + j NDCG@ndcg_ks[j]      (metric = value / weight)
+ *   out[2 (3 + n_ks)]      = number of groups
+ * 1 <= n <= 2^26, 1 <= key_bits <= 32, 0 <= n_ks <= 8, every cut-off >= 1; workspace from
+ * fx_group_metrics_workspace_bytes(n).  All fp64 sums run in a fixed order: same input, same bits.
+ * ------------------------------------------------------------------------------------------ */
+size_t fx_group_metrics_workspace_bytes(int64_t n);
+int fx_group_metrics(const float* y_pred, const float* y_true, const uint32_t* group_key,
+                     int32_t key_bits, int64_t n, const int32_t* ndcg_ks, int32_t n_ks,
+                     void* workspace, size_t workspace_bytes, double* out, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused sparse front end / back end (csrc/fx_fused.hip).  For a FeatureEmbeddingDict whose id
  * columns own disjoint tables laid out in column order (every categorical schema of the BASELINE
  * configs) the per-step embedding work collapses to a handful of launches; the entry points above
