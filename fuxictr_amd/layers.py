@@ -2902,6 +2902,188 @@ class MultiHeadSelfAttention(nn.Module):
         return out
 
 
+def _field_view(x):
+    """[B, F, D] as fx_senet_* / fx_bilinear_* read it: unit stride over d, D over the fields, any sample
+    stride (a prefix of the gather record is read in place); anything else is copied."""
+    if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
+        x = x.contiguous()
+    return x
+
+
+class _SENetFn(torch.autograd.Function):
+    """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
+    three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are
+    recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, W1, W2, act):
+        x = _field_view(x)
+        B, F, D = x.shape
+        A = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        V = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        ops.senet_fwd(x, W1, W2, act, A, V)
+        ctx.x, ctx.A, ctx.w, ctx.act = x, A, (W1, W2), act
+        return V
+
+    @staticmethod
+    def backward(ctx, dV):
+        x, A, (W1, W2), act = ctx.x, ctx.A, ctx.w, ctx.act
+        B, F, D = x.shape
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        dW1, dW2 = torch.empty_like(W1), torch.empty_like(W2)
+        ws = _Workspace.get(x.device, ops.senet_workspace_floats(B, F, W1.shape[0]), tag="senet")
+        ops.senet_bwd(x, W1, W2, act, A, None, dV.contiguous(), dx, dW1, dW2, ws)
+        return dx, dW1, dW2, None
+
+
+class SqueezeExcitation(nn.Module):
+    """squeeze_excitation.py:24-64: same constructor, the same `excitation` nn.Sequential (state-dict keys
+    `excitation.0.weight`, `excitation.2.weight`); the arithmetic is fx_senet_*."""
+
+    def __init__(self, num_fields, reduction_ratio=3, excitation_activation="ReLU"):
+        super(SqueezeExcitation, self).__init__()
+        reduced_size = max(1, int(num_fields / reduction_ratio))
+        if excitation_activation.lower() not in ops.SENET_ACTS:
+            raise NotImplementedError("SqueezeExcitation: excitation_activation={} (ReLU or Sigmoid)"
+                                      .format(excitation_activation))
+        for what, n in (("num_fields", num_fields), ("reduced size", reduced_size)):
+            if not 1 <= n <= ops.BILINEAR_MAX:
+                raise NotImplementedError("SqueezeExcitation: {}={}, the fused kernel's limit is {}"
+                                          .format(what, n, ops.BILINEAR_MAX))
+        dev = _alloc_device()
+        self._act = ops.SENET_ACTS[excitation_activation.lower()]
+        self.excitation = nn.Sequential(
+            nn.Linear(num_fields, reduced_size, bias=False, device=dev), nn.ReLU(),
+            nn.Linear(reduced_size, num_fields, bias=False, device=dev),
+            nn.ReLU() if self._act == 0 else nn.Sigmoid())
+
+    def _check(self, feature_emb):
+        if feature_emb.dim() != 3 or feature_emb.shape[1] != self.excitation[0].in_features \
+                or feature_emb.shape[2] > ops.BILINEAR_MAX:
+            raise NotImplementedError("SqueezeExcitation: input {}, the fused kernel takes [batch, {} fields, "
+                                      "dim <= {}]".format(tuple(feature_emb.shape),
+                                                          self.excitation[0].in_features, ops.BILINEAR_MAX))
+
+    def forward(self, feature_emb):
+        self._check(feature_emb)
+        return _SENetFn.apply(feature_emb, self.excitation[0].weight, self.excitation[2].weight, self._act)
+
+
+class _BilinearFn(torch.autograd.Function):
+    """The bilinear interaction as ONE autograd node (bilinear_interaction.py:127-150): forward one launch,
+    backward four (five for field_all / field_each).  Kept for the backward: X (a view) and W."""
+
+    @staticmethod
+    def forward(ctx, x, W, kind):
+        x = _field_view(x)
+        B, F, D = x.shape
+        P = F * (F - 1) // 2
+        out = torch.empty(B, P * D, dtype=torch.float32, device=x.device)
+        ops.bilinear_fwd(x, W, kind, None, out)
+        ctx.x, ctx.W, ctx.kind = x, W, kind
+        return out.view(B, P, D)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W = ctx.x, ctx.W
+        B, F, D = x.shape
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        dW = torch.empty_like(W)
+        ws = _Workspace.get(x.device, ops.bilinear_workspace_floats(B, F, D), tag="bilinear")
+        ops.bilinear_bwd(x, W, ctx.kind, None, g.reshape(B, -1).contiguous(), dx, None, dW, ws)
+        return dx, dW, None
+
+
+class _FiBiNETMixFn(torch.autograd.Function):
+    """FiBiNET's interaction stage as ONE autograd node (FiBiNET.py:97-101): the excitation gates A, the
+    bilinear interaction of X into the columns [0, P D) and that of A * X into [P D, 2 P D) of one buffer, which
+    is the tower's input (`pad` zero columns behind it keep its rows 16-byte aligned): neither V = A * X nor
+    the two branch tensors nor their cat exist.  Backward: both branches add into one dX, the second returns
+    dA, which the excitation's backward turns into its share of dX and its weight gradients.  Kept: X (a view
+    of the gather record), A and the weights."""
+
+    @staticmethod
+    def forward(ctx, x, W1, W2, act, Wp, Wq, kind, pad):
+        x = _field_view(x)
+        B, F, D = x.shape
+        PD = (F * (F - 1) // 2) * D
+        A = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        ops.senet_fwd(x, W1, W2, act, A)
+        out = torch.empty(B, 2 * PD + pad, dtype=torch.float32, device=x.device)
+        if pad:
+            out[:, 2 * PD:].zero_()
+        ops.bilinear_fwd(x, Wp, kind, None, out, out_col=0)
+        ops.bilinear_fwd(x, Wq, kind, A, out, out_col=PD)
+        ctx.x, ctx.A, ctx.w, ctx.cfg = x, A, (W1, W2, Wp, Wq), (act, kind)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, A, (W1, W2, Wp, Wq), (act, kind) = ctx.x, ctx.A, ctx.w, ctx.cfg
+        B, F, D = x.shape
+        PD = (F * (F - 1) // 2) * D
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        dev = x.device
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
+        dA = torch.empty(B, F, dtype=torch.float32, device=dev)
+        dWp, dWq, dW1, dW2 = (torch.empty_like(w) for w in (Wp, Wq, W1, W2))
+        ws = _Workspace.get(dev, ops.bilinear_workspace_floats(B, F, D), tag="bilinear")
+        ops.bilinear_bwd(x, Wp, kind, None, g, dx, None, dWp, ws, dout_col=0)
+        ops.bilinear_bwd(x, Wq, kind, A, g, dx, dA, dWq, ws, dout_col=PD, dx_accumulate=True)
+        ws = _Workspace.get(dev, ops.senet_workspace_floats(B, F, W1.shape[0]), tag="senet")
+        ops.senet_bwd(x, W1, W2, act, A, dA, None, dx, dW1, dW2, ws, dx_accumulate=True)
+        return dx, dW1, dW2, None, dWp, dWq, None, None
+
+
+class _BilinearBase(nn.Module):
+    def _setup(self, num_fields, embedding_dim, bilinear_type):
+        if bilinear_type not in ops.BILINEAR_TYPES:
+            raise NotImplementedError("bilinear_type={}".format(bilinear_type))
+        for what, n, lo in (("num_fields", num_fields, 2), ("embedding_dim", embedding_dim, 1)):
+            if not lo <= n <= ops.BILINEAR_MAX:
+                raise NotImplementedError("{}: {}={}, the fused kernel's limit is {} <= {} <= {}".format(
+                    type(self).__name__, what, n, lo, what, ops.BILINEAR_MAX))
+        self.bilinear_type = bilinear_type
+        self.num_fields, self.embedding_dim = num_fields, embedding_dim
+        self.interact_dim = int(num_fields * (num_fields - 1) / 2)
+        lead = {"field_all": (), "field_each": (num_fields,), "field_interaction": (self.interact_dim,)}
+        self.bilinear_W = nn.Parameter(torch.empty(*lead[bilinear_type], embedding_dim, embedding_dim,
+                                                   device=_alloc_device()))
+
+    def init_weights(self):
+        nn.init.xavier_normal_(self.bilinear_W)
+
+    def forward(self, feature_emb):
+        """-> [batch, interact_dim, embedding_dim]"""
+        if feature_emb.dim() != 3 or tuple(feature_emb.shape[1:]) != (self.num_fields, self.embedding_dim):
+            raise NotImplementedError("{}: input {}, built for [batch, {}, {}]".format(
+                type(self).__name__, tuple(feature_emb.shape), self.num_fields, self.embedding_dim))
+        return _BilinearFn.apply(feature_emb, self.bilinear_W, ops.BILINEAR_TYPES[self.bilinear_type])
+
+
+class BilinearInteraction(_BilinearBase):
+    """bilinear_interaction.py:23-82 (the pair-by-pair formulation: the same numbers as V2, the same kernel)."""
+
+    def __init__(self, num_fields, embedding_dim, bilinear_type="field_interaction"):
+        super(BilinearInteraction, self).__init__()
+        self._setup(num_fields, embedding_dim, bilinear_type)
+        self.init_weights()
+
+
+class BilinearInteractionV2(_BilinearBase):
+    """bilinear_interaction.py:85-150: same constructor, `bilinear_W` in the reference's three shapes and the
+    frozen int64 `triu_index` parameter under the same key (no gradient: the optimizer and the regularizer pass
+    it by); the arithmetic is fx_bilinear_*."""
+
+    def __init__(self, num_fields, embedding_dim, bilinear_type="field_interaction"):
+        super(BilinearInteractionV2, self).__init__()
+        self._setup(num_fields, embedding_dim, bilinear_type)
+        self.triu_index = nn.Parameter(torch.triu_indices(num_fields, num_fields, offset=1).to(_alloc_device()),
+                                       requires_grad=False)
+        self.init_weights()
+
+
 
 def link_fusion(model):
     """Called by BaseModel.compile(): tell the model's embedding layer which LogisticRegression

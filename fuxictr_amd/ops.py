@@ -1062,6 +1062,76 @@ def mhsa_bwd(X, Wq, Wk, Wv, Wres, H, use_scale, residual, relu, Y, dY, dX, dW, w
     return dX, dW
 
 
+# ---- FiBiNET: squeeze-excitation and bilinear interaction -------------------------------------------
+BILINEAR_MAX = 64    # F, D (and the excitation's hidden width) of fx_senet_* / fx_bilinear_*
+BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}
+SENET_ACTS = {"relu": 0, "sigmoid": 1}
+
+
+def senet_workspace_floats(B, F, R):
+    return int(_lib.load().fx_senet_workspace_floats(B, F, R))
+
+
+def bilinear_workspace_floats(B, F, D):
+    return int(_lib.load().fx_bilinear_workspace_floats(B, F, D))
+
+
+@_timed("senet_fwd", "senet", lambda X, W1, *a, **kw: 4.0 * X.shape[0] * W1.numel())
+def senet_fwd(X, W1, W2, act, A, V=None):
+    """A [B, F] = act(W2 relu(W1 mean_d X)); V [B, F, D] = X * A[:, :, None] only when a tensor is given."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    check(_lib.load().fx_senet_fwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W1), ptr(W2), W1.shape[0], act, ptr(A),
+                                   ptr(V), stream_ptr(X.device)), "fx_senet_fwd")
+    return A
+
+
+@_timed("senet_bwd", "senet", lambda X, W1, *a, **kw: 12.0 * X.shape[0] * W1.numel())
+def senet_bwd(X, W1, W2, act, A, dA, dV, dX, dW1, dW2, workspace, dx_accumulate=False):
+    """From dA [B, F] and / or dV [B, F, D] (None: absent): dX (sample stride free), dW1 [R, F], dW2 [F, R]."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    check(_lib.load().fx_senet_bwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W1), ptr(W2), W1.shape[0], act, ptr(A),
+                                   ptr(dA), ptr(dV), ptr(dX), _mhsa_x(dX), 1 if dx_accumulate else 0,
+                                   ptr(dW1), ptr(dW2), ptr(workspace), stream_ptr(X.device)), "fx_senet_bwd")
+    return dX, dW1, dW2
+
+
+def _bilinear_flops(X, *a, **kw):
+    B, F, D = X.shape
+    return 2.0 * B * (F * (F - 1) // 2) * D * D
+
+
+def _rows(buf):
+    """A [B, n] buffer as the kernels address it: unit stride over the columns, any row stride."""
+    assert buf.dim() == 2 and buf.stride(1) == 1
+    return buf.stride(0) if buf.shape[0] > 1 else buf.shape[1]
+
+
+@_timed("bilinear_fwd", "bilinear", _bilinear_flops)
+def bilinear_fwd(X, W, kind, A, out, out_col=0):
+    """out[:, out_col : out_col + P*D] = the bilinear interaction of A[:, :, None] * X (A None: of X), pairs in
+    triu order; `out` is a [B, >= out_col + P*D] buffer that other columns may share."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    assert out.shape[0] == B and out.shape[1] >= out_col + (F * (F - 1) // 2) * D
+    check(_lib.load().fx_bilinear_fwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W), kind, ptr(A), ptr(out), _rows(out),
+                                      out_col, stream_ptr(X.device)), "fx_bilinear_fwd")
+    return out
+
+
+@_timed("bilinear_bwd", "bilinear", lambda *a, **kw: 3.0 * _bilinear_flops(*a, **kw))
+def bilinear_bwd(X, W, kind, A, dOut, dX, dA, dW, workspace, dout_col=0, dx_accumulate=False):
+    """dOut in the layout of the forward's `out`; dX (sample stride free), dA [B, F] (with A), dW like W."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    assert dOut.shape[0] == B and dOut.shape[1] >= dout_col + (F * (F - 1) // 2) * D
+    check(_lib.load().fx_bilinear_bwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W), kind, ptr(A), ptr(dOut), _rows(dOut),
+                                      dout_col, ptr(dX), _mhsa_x(dX), 1 if dx_accumulate else 0, ptr(dA),
+                                      ptr(dW), ptr(workspace), stream_ptr(X.device)), "fx_bilinear_bwd")
+    return dX, dA, dW
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

@@ -16,7 +16,8 @@ import sys
 
 LAYER_NAMES = ["FeatureEmbedding", "FeatureEmbeddingDict", "LogisticRegression",
                "FactorizationMachine", "InnerProductInteraction", "MLP_Block", "CrossNetV2",
-               "MaskedAveragePooling", "MaskedSumPooling", "DIN_Attention", "Dice", "CompressedInteractionNet"]
+               "MaskedAveragePooling", "MaskedSumPooling", "DIN_Attention", "Dice", "CompressedInteractionNet",
+               "SqueezeExcitation", "BilinearInteraction", "BilinearInteractionV2"]
 
 
 def install():

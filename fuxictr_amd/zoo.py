@@ -1,8 +1,9 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt and FiBiNET, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
-model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
+model_zoo/FiBiNET/src/FiBiNET.py:45-104), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -12,10 +13,11 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FxLinear,
                      InnerProductInteraction, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
-                     _DlrmMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
+                     SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
+from . import ops
 from .rank_model import BaseModel
 
 
@@ -349,3 +351,43 @@ class AutoInt(_ZooModel):
         if self.dnn is not None:
             logit = self.dnn(emb.flatten(start_dim=1), out_add=logit)
         return {"y_pred": self.output_activation(logit)}
+
+
+class FiBiNET(_ZooModel):
+    def __init__(self, feature_map, model_id="FiBiNET", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 hidden_units=[], hidden_activations="ReLU", excitation_activation="ReLU", reduction_ratio=3,
+                 bilinear_type="field_interaction", net_dropout=0, batch_norm=False,
+                 embedding_regularizer=None, net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        num_fields = feature_map.num_fields
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.senet_layer = SqueezeExcitation(num_fields, reduction_ratio, excitation_activation)
+        self.bilinear_interaction1 = BilinearInteractionV2(num_fields, embedding_dim, bilinear_type)
+        self.bilinear_interaction2 = BilinearInteractionV2(num_fields, embedding_dim, bilinear_type)
+        self.lr_layer = LogisticRegression(feature_map, use_bias=False)
+        self.dnn = self._tower(num_fields * (num_fields - 1) * embedding_dim, hidden_units,
+                               hidden_activations, net_dropout, batch_norm)
+        # fused=False: the layers one after another, as the reference's class composes them behind
+        # patch.install() (V = A * X, the two branch tensors and their cat in memory): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_FIBINET_FUSED", "1") != "0"))
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # [B, F, D]
+        if self._fused:
+            width = 2 * self.bilinear_interaction1.interact_dim * emb.shape[2]
+            # (the tower pads an unaligned input width itself, one cat: hand it the padded rows instead)
+            fused_dnn = getattr(self.dnn, "_fused", None) is not None
+            pad = (-width) % 4 if (fused_dnn and width >= 64 and _MLP_PAD) else 0
+            excite = self.senet_layer.excitation
+            comb = _FiBiNETMixFn.apply(emb, excite[0].weight, excite[2].weight, self.senet_layer._act,
+                                       self.bilinear_interaction1.bilinear_W,
+                                       self.bilinear_interaction2.bilinear_W,
+                                       ops.BILINEAR_TYPES[self.bilinear_interaction1.bilinear_type], pad)
+        else:
+            senet_emb = self.senet_layer(emb)
+            comb = torch.cat([self.bilinear_interaction1(emb), self.bilinear_interaction2(senet_emb)],
+                             dim=1).flatten(start_dim=1)
+        # the linear part rides into the tower's head through the last GEMM's epilogue
+        return {"y_pred": self.output_activation(self.dnn(comb, out_add=self.lr_layer(X)))}

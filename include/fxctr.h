@@ -684,6 +684,52 @@ int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in
                 float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FiBiNET's squeeze-excitation over the fields of a sample (SqueezeExcitation.forward,
+ * fuxictr/pytorch/layers/attentions/squeeze_excitation.py:51-64; its autograd at rank_model.py:320):
+ *     Z[b,f] = mean_d X[b,f,d]                      X: [B, F, D] (sample stride x_ld)
+ *     A = act(W2 relu(W1 Z))                        W1: [R, F], W2: [F, R], no biases; act: 0 ReLU, 1 Sigmoid
+ *     V = X * A[:,:,None]                           A: [B, F]; V: [B, F, D] contiguous, written only when V != NULL
+ *   fx_senet_bwd : from dA [B, F] and / or dV [B, F, D] (either may be NULL, not both): dX [B, F, D] (sample
+ *                  stride dx_ld; added to when dx_accumulate), dW1 [R, F], dW2 [F, R].  Z and the hidden layer are
+ *                  recomputed, A is the forward's.  The weight gradients are summed per workgroup in LDS, written
+ *                  to workspace and reduced in a fixed order (deterministic, no atomics).
+ * workspace: fx_senet_workspace_floats(B, F, R) floats.   Limits: F, D, R <= 64.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fx_senet_workspace_floats(int64_t B, int32_t F, int32_t R);
+int fx_senet_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W1,
+                 const float* W2, int32_t R, int32_t act, float* A, float* V, fx_stream_t stream);
+int fx_senet_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W1,
+                 const float* W2, int32_t R, int32_t act, const float* A, const float* dA,
+                 const float* dV, float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dW1,
+                 float* dW2, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FiBiNET's bilinear interaction (BilinearInteractionV2.forward,
+ * fuxictr/pytorch/layers/interactions/bilinear_interaction.py:127-150, and BilinearInteraction.forward,
+ * bilinear_interaction.py:60-82: the same numbers), pairs p = (i, j), i < j, in torch.triu_indices(F, F, 1)
+ * order, P = F (F - 1) / 2 of them:
+ *     out[b, out_col + p * D + e] = (sum_d v_i[d] W_w[d, e]) * v_j[e],    v_f = A[b,f] * X[b,f,:]  (A == NULL: X)
+ *     type 0 field_all: W [D, D], w = 0;  1 field_each: W [F, D, D], w = i;  2 field_interaction: W [P, D, D], w = p
+ * X: [B, F, D] with sample stride x_ld; out: rows of out_ld floats, this call's P * D columns from out_col on
+ * (two calls fill one buffer: no cat); with the scale A [B, F] this is the interaction of SqueezeExcitation's V
+ * (squeeze_excitation.py:63) without V in memory.
+ *   fx_bilinear_bwd : dOut in the layout of out; dX [B, F, D] (sample stride dx_ld; added to when dx_accumulate),
+ *                     dA [B, F] (with A, and only then), dW in the shape of W.  Two passes over dOut: dX / dA per
+ *                     sample tile, dW per (pair group, sample slab) into workspace, then fixed-order sums
+ *                     (deterministic, no atomics).
+ * workspace: fx_bilinear_workspace_floats(B, F, D) floats.   Limits: 2 <= F <= 64, D <= 64.
+ * 16-byte accesses when D % 4 == 0 and every pointer / stride / offset is 16-byte aligned, scalar ones otherwise.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fx_bilinear_workspace_floats(int64_t B, int32_t F, int32_t D);
+int fx_bilinear_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W,
+                    int32_t type, const float* A, float* out, int64_t out_ld, int64_t out_col,
+                    fx_stream_t stream);
+int fx_bilinear_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W,
+                    int32_t type, const float* A, const float* dOut, int64_t dout_ld, int64_t dout_col,
+                    float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dA, float* dW,
+                    float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
