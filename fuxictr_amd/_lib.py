@@ -137,6 +137,11 @@ SIGNATURES = {
     "fx_bilinear_workspace_floats": (i64, [i64, i32, i32]),
     "fx_bilinear_fwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, vp, i64, i64, vp]),
     "fx_bilinear_bwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp]),
+    "fx_layernorm_workspace_floats": (i64, [i64, i32, i32]),
+    "fx_layernorm_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, C.c_float, i32, vp, i64, i64, vp, vp]),
+    "fx_layernorm_bwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, i64, i64, vp, vp, i64, i64, vp, i64, i32,
+                               vp, vp, vp, vp]),
+    "fx_mask_grad": (i32, [vp, i64, vp, i64, i64, i32, i32, vp, i64, i32, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

@@ -3084,6 +3084,312 @@ class BilinearInteractionV2(_BilinearBase):
         self.init_weights()
 
 
+def _rows_view(x):
+    """[rows, n] as the GEMMs and fx_layernorm_* read it in place: unit column stride, 16-byte aligned rows
+    (a prefix of the gather record); anything else is copied."""
+    if x.stride(-1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """torch.nn.LayerNorm over G groups of N columns (+ the ReLU behind it) as ONE autograd node: forward one
+    launch, backward three.  `packed` is the [2, G, N] storage that the G per-group weight / bias Parameters in
+    `params` (the weights, then the biases) are views of; None for a single pair (G = 1).  Kept for the backward:
+    x (a view), the statistics, and y when the ReLU is fused."""
+
+    @staticmethod
+    def forward(ctx, x, G, N, eps, relu, packed, *params):
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        rows = x.shape[0]
+        gamma, beta = (packed[0], packed[1]) if packed is not None else (params[0], params[1])
+        y = torch.empty(rows, G * N, dtype=torch.float32, device=x.device)
+        stats = torch.empty(rows * G * 2, dtype=torch.float32, device=x.device)
+        ops.layernorm_fwd(x, G, N, gamma, beta, eps, relu, y, stats)
+        ctx.x, ctx.gamma, ctx.stats, ctx.y = x, gamma, stats, (y if relu else None)
+        ctx.cfg = (G, N, relu, packed is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, stats, y = ctx.x, ctx.gamma, ctx.stats, ctx.y
+        G, N, relu, is_packed = ctx.cfg
+        rows = x.shape[0]
+        if dy.stride(-1) != 1:
+            dy = dy.contiguous()
+        dx = torch.empty(rows, G * N, dtype=torch.float32, device=x.device)
+        dgb = torch.empty(2, G, N, dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(x.device, ops.layernorm_workspace_floats(rows, G, N), tag="layernorm")
+        ops.layernorm_bwd(x, G, N, gamma, relu, y, stats, dy, dx, dgb[0], dgb[1], ws)
+        if is_packed:        # per-field views of the one dgamma / dbeta buffer
+            grads = tuple(dgb[0, i] for i in range(G)) + tuple(dgb[1, i] for i in range(G))
+        else:
+            grads = (dgb[0, 0], dgb[1, 0])
+        return (dx, None, None, None, None, None) + grads
+
+
+class LayerNorm(nn.Module):
+    """torch.nn.LayerNorm over the last axis (keys `weight`, `bias`; ones / zeros, which BaseModel.reset_parameters
+    leaves alone as it does the reference's) on fx_layernorm_*: MaskNet.py:98 and MaskNet.py:256."""
+
+    def __init__(self, normalized_shape, eps=1e-5):
+        super(LayerNorm, self).__init__()
+        if isinstance(normalized_shape, (list, tuple)):
+            if len(normalized_shape) != 1:
+                raise NotImplementedError("LayerNorm: normalized_shape={}, only the last axis"
+                                          .format(tuple(normalized_shape)))
+            normalized_shape = normalized_shape[0]
+        n = int(normalized_shape)
+        ops.layernorm_check(1, n, "LayerNorm")
+        dev = _alloc_device()
+        self.normalized_shape, self.eps = (n,), eps
+        self.weight = nn.Parameter(torch.ones(n, device=dev))
+        self.bias = nn.Parameter(torch.zeros(n, device=dev))
+
+    def forward(self, x, relu=False):
+        n = self.normalized_shape[0]
+        if x.shape[-1] != n:
+            raise NotImplementedError("LayerNorm: input {}, built for a last axis of {}".format(tuple(x.shape), n))
+        lead = x.shape[:-1]
+        y = _LayerNormFn.apply(x.reshape(-1, n), 1, n, self.eps, relu, None, self.weight, self.bias)
+        return y.reshape(*lead, n)
+
+
+class FieldLayerNorm(nn.ModuleList):
+    """MaskNet's `emb_norm` (MaskNet.py:97-99, 116-118): a ModuleList of one LayerNorm(embedding_dim) per field,
+    the reference's keys `<i>.weight` / `<i>.bias` of shape [D].  The 2 F Parameters are views of ONE packed
+    [2, F, D] storage, as the embedding tables are views of their row record: the kernel reads all fields' affine
+    pairs in one grouped launch over the gather record, and state_dict / load_state_dict / the dense optimizer see
+    2 F ordinary Parameters."""
+
+    def __init__(self, num_fields, embedding_dim, eps=1e-5):
+        ops.layernorm_check(num_fields, embedding_dim, "FieldLayerNorm")
+        super(FieldLayerNorm, self).__init__([LayerNorm(embedding_dim, eps) for _ in range(num_fields)])
+        self._shape, self._eps = (num_fields, embedding_dim), eps
+        packed = torch.empty(2, num_fields, embedding_dim, device=_alloc_device())
+        packed[0].fill_(1.0)
+        packed[1].zero_()
+        self._packed = packed
+        self._bind_views()
+
+    def _bind_views(self):
+        for i, mod in enumerate(self):
+            mod.weight.data = self._packed[0, i]
+            mod.bias.data = self._packed[1, i]
+
+    def _apply(self, fn, recurse=True):
+        # nn.Module.to() / cuda(): move the packed storage, then re-point the per-field Parameters at it
+        self._packed = fn(self._packed)
+        self._bind_views()
+        return self
+
+    def forward(self, feature_emb):
+        """[batch, F, D] (the gather record, read in place) -> [batch, F * D]"""
+        F, D = self._shape
+        if feature_emb.dim() != 3 or tuple(feature_emb.shape[1:]) != (F, D):
+            raise NotImplementedError("FieldLayerNorm: input {}, built for [batch, {}, {}]".format(
+                tuple(feature_emb.shape), F, D))
+        x = _field_view(feature_emb)
+        params = [m.weight for m in self] + [m.bias for m in self]
+        return _LayerNormFn.apply(x.reshape(x.shape[0], F * D), F, D, self._eps, False, self._packed, *params)
+
+
+class _MaskStageFn(torch.autograd.Function):
+    """`nb` mask blocks that share V_emb and V_hidden (MaskNet.py:262-274; nb = 1: a block of SerialMaskNet,
+    nb = num_blocks: ParallelMaskNet's stage, MaskNet.py:228-231) as ONE autograd node.  Per block
+        h1 = relu(W0 V_emb + b0);  V_mask = W2 h1 + b2;  M = V_mask * V_hidden;  Z = M Wh^T;  out = relu(LN(Z))
+    The product M rides in the epilogue of the `mask_layer.2` GEMM (zout = V_mask, mul = V_hidden); h1, V_mask, M
+    and Z of all blocks are column ranges of one buffer each, the LayerNorm writes block k at column k * O of the
+    output: no cat.  Forward: three gemm_batch calls + nb LayerNorm launches.  Backward per block: the LayerNorm's
+    three launches, the hidden GEMM's dW and dX in one launch (zout = dM, mul = V_hidden: the dX GEMM leaves
+    dV_mask), the two pairs of `mask_layer` (dV_emb of block k added to that of block k - 1 in the epilogue);
+    then ONE fx_mask_grad for dV_hidden = sum_k dM_k * V_mask_k.
+    ln = False: the node ends at Z (LayerNorm off, another activation or dropout: the caller runs those modules).
+    w: per block W0, b0, W2, b2, Wh (+ gamma, beta with ln)."""
+
+    @staticmethod
+    def forward(ctx, v_emb, v_hid, ln, eps, nb, *w):
+        v_emb, v_hid = _rows_view(v_emb), _rows_view(v_hid)
+        per = 7 if ln else 5
+        blocks = [w[k * per:(k + 1) * per] for k in range(nb)]
+        B, dev = v_emb.shape[0], v_emb.device
+        R, H, O = blocks[0][0].shape[0], blocks[0][2].shape[0], blocks[0][4].shape[0]
+
+        def buf(width):
+            return torch.empty(B, nb * width, dtype=torch.float32, device=dev)
+
+        def cols(t, k, width):
+            return t[:, k * width:(k + 1) * width] if nb > 1 else t
+        h1, vmask, m, z = buf(R), buf(H), buf(H), buf(O)
+        ops.gemm_batch([ops.gemm_problem(v_emb, blk[0], cols(h1, k, R), transb=True, bias=blk[1], act=1)
+                        for k, blk in enumerate(blocks)])
+        ops.gemm_batch([ops.gemm_problem(cols(h1, k, R), blk[2], cols(m, k, H), transb=True, bias=blk[3],
+                                         zout=cols(vmask, k, H), mul=v_hid) for k, blk in enumerate(blocks)])
+        ops.gemm_batch([ops.gemm_problem(cols(m, k, H), blk[4], cols(z, k, O), transb=True)
+                        for k, blk in enumerate(blocks)])
+        out, stats = z, None
+        if ln:
+            out = buf(O)
+            stats = torch.empty(nb, B * 2, dtype=torch.float32, device=dev)
+            for k, blk in enumerate(blocks):
+                ops.layernorm_fwd(cols(z, k, O), 1, O, blk[5], blk[6], eps, True, out, stats[k], y_col=k * O)
+        ctx.kept = (v_emb, v_hid, h1, vmask, m, z, out if ln else None, stats)
+        ctx.cfg, ctx.blocks = (ln, nb, R, H, O), blocks
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        v_emb, v_hid, h1, vmask, m, z, out, stats = ctx.kept
+        (ln, nb, R, H, O), blocks = ctx.cfg, ctx.blocks
+        B, dev = v_emb.shape[0], v_emb.device
+        if dy.stride(-1) != 1:
+            dy = dy.contiguous()
+
+        def cols(t, k, width):
+            return t[:, k * width:(k + 1) * width] if nb > 1 else t
+        dM = torch.empty(B, nb * H, dtype=torch.float32, device=dev)
+        grads, dve = [], None
+        for k, blk in enumerate(blocks):
+            W0, W2, Wh = blk[0], blk[2], blk[4]
+            if ln:
+                dz = torch.empty(B, O, dtype=torch.float32, device=dev)
+                dgb = torch.empty(2, O, dtype=torch.float32, device=dev)
+                ws = _Workspace.get(dev, ops.layernorm_workspace_floats(B, 1, O), tag="layernorm")
+                ops.layernorm_bwd(cols(z, k, O), 1, O, blk[5], True, out, stats[k], dy, dz, dgb[0], dgb[1], ws,
+                                  y_col=k * O, dy_col=k * O)
+            else:
+                dz = cols(dy, k, O)
+            # hidden_layer.0 (no bias): dWh = dz^T M and, in the same launch, dM = dz Wh with dV_mask = dM * V_hidden
+            dWh = torch.empty(O, H, dtype=torch.float32, device=dev)
+            dvm = torch.empty(B, H, dtype=torch.float32, device=dev)
+            sk = max(_split_k_for(O, H, B), 1)
+            ws = _Workspace.get(dev, ops.gemm_workspace_floats(O, H, sk))
+            ops.gemm_batch([ops.gemm_problem(dz, cols(m, k, H), dWh, transa=True, split_k=sk, workspace=ws),
+                            ops.gemm_problem(dz, Wh, dvm, zout=cols(dM, k, H), mul=v_hid)])
+            dW2, db2, dh1 = linear_grads(dvm, cols(h1, k, R), W2, True, mask=cols(h1, k, R))
+            dW0, db0, dve = linear_grads(dh1, v_emb, W0, True, add=dve)
+            grads += [dW0, db0, dW2, db2, dWh]
+            if ln:
+                grads += [dgb[0], dgb[1]]
+        dvh = torch.empty(B, H, dtype=torch.float32, device=dev)
+        ops.mask_grad(dM, vmask, H, nb, dvh)
+        return (dve, dvh, None, None, None) + tuple(grads)
+
+
+class MaskBlock(nn.Module):
+    """MaskNet.py:236-274: same constructor, the same `mask_layer` / `hidden_layer` nn.Sequentials (keys
+    `mask_layer.0.*`, `mask_layer.2.*`, `hidden_layer.0.weight`, `hidden_layer.1.*` the LayerNorm).  forward() is
+    the reference's composition module by module; SerialMaskNet / ParallelMaskNet run their blocks through
+    _MaskStageFn (mask_stage)."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, hidden_activation="ReLU", reduction_ratio=1,
+                 dropout_rate=0, layer_norm=True):
+        super(MaskBlock, self).__init__()
+        dev = _alloc_device()
+        reduced = int(hidden_dim * reduction_ratio)
+        if reduced < 1:
+            raise ValueError("MaskBlock: int(hidden_dim * reduction_ratio) = int({} * {}) = {}".format(
+                hidden_dim, reduction_ratio, reduced))
+        self.mask_layer = nn.Sequential(FxLinear(input_dim, reduced, device=dev), nn.ReLU(),
+                                        FxLinear(reduced, hidden_dim, device=dev))
+        hidden_layers = [FxLinear(hidden_dim, output_dim, bias=False, device=dev)]
+        if layer_norm:
+            hidden_layers.append(LayerNorm(output_dim))
+        hidden_layers.append(get_activation(hidden_activation))
+        if dropout_rate > 0:
+            hidden_layers.append(nn.Dropout(p=dropout_rate))
+        self.hidden_layer = nn.Sequential(*hidden_layers)
+        # LayerNorm + ReLU, nothing behind them: the node's own LayerNorm launch; otherwise the node ends at the
+        # hidden GEMM and hidden_layer[1:] runs module by module
+        self._ln_fused = bool(layer_norm) and len(hidden_layers) == 3 and isinstance(hidden_layers[2], nn.ReLU)
+
+    def forward(self, V_emb, V_hidden):
+        V_mask = self.mask_layer(V_emb)
+        return self.hidden_layer(V_mask * V_hidden)
+
+
+def mask_stage(blocks, V_emb, V_hidden):
+    """The outputs of `blocks` (MaskBlocks of one shape that share V_emb and V_hidden) side by side,
+    [batch, len(blocks) * output_dim]: the fused prefix as one node, whatever it leaves module by module."""
+    first, nb = blocks[0], len(blocks)
+    ln = all(b._ln_fused for b in blocks)
+    w = []
+    for b in blocks:
+        w += [b.mask_layer[0].weight, b.mask_layer[0].bias, b.mask_layer[2].weight, b.mask_layer[2].bias,
+              b.hidden_layer[0].weight]
+        if ln:
+            w += [b.hidden_layer[1].weight, b.hidden_layer[1].bias]
+    eps = first.hidden_layer[1].eps if ln else 0.0
+    out = _MaskStageFn.apply(V_emb, V_hidden, ln, eps, nb, *w)
+    if ln:
+        return out
+    width = out.shape[1] // nb
+    parts = []
+    for k, b in enumerate(blocks):
+        t = out[:, k * width:(k + 1) * width] if nb > 1 else out
+        for mod in list(b.hidden_layer)[1:]:
+            t = mod(t)
+        parts.append(t)
+    return parts[0] if nb == 1 else torch.cat(parts, dim=-1)
+
+
+class SerialMaskNet(nn.Module):
+    """MaskNet.py:126-180: same constructor, `mask_blocks.<i>` and the `fc` nn.Sequential (`fc.0` the head)."""
+
+    def __init__(self, input_dim, output_dim=None, output_activation=None, hidden_units=[],
+                 hidden_activations="ReLU", reduction_ratio=1, dropout_rates=0, layer_norm=True):
+        super(SerialMaskNet, self).__init__()
+        if not isinstance(dropout_rates, list):
+            dropout_rates = [dropout_rates] * len(hidden_units)
+        if not isinstance(hidden_activations, list):
+            hidden_activations = [hidden_activations] * len(hidden_units)
+        self.hidden_units = [input_dim] + list(hidden_units)
+        self.mask_blocks = nn.ModuleList()
+        for idx in range(len(self.hidden_units) - 1):
+            self.mask_blocks.append(MaskBlock(input_dim, self.hidden_units[idx], self.hidden_units[idx + 1],
+                                              hidden_activations[idx], reduction_ratio, dropout_rates[idx],
+                                              layer_norm))
+        fc_layers = []
+        if output_dim is not None:
+            fc_layers.append(FxLinear(self.hidden_units[-1], output_dim, device=_alloc_device()))
+        if output_activation is not None:
+            fc_layers.append(get_activation(output_activation))
+        self.fc = nn.Sequential(*fc_layers) if fc_layers else None
+        self.fused = True
+
+    def forward(self, V_emb, V_hidden):
+        v_out = V_hidden
+        for block in self.mask_blocks:
+            v_out = mask_stage([block], V_emb, v_out) if self.fused else block(V_emb, v_out)
+        if self.fc is not None:
+            v_out = self.fc(v_out)
+        return v_out
+
+
+class ParallelMaskNet(nn.Module):
+    """MaskNet.py:183-233: same constructor, `mask_blocks.<i>` and the `dnn` MLP_Block (`dnn.mlp.*`).  The blocks
+    share both inputs: one stage node, their outputs side by side in one buffer (no cat)."""
+
+    def __init__(self, input_dim, output_dim=None, output_activation=None, num_blocks=1, block_dim=64,
+                 hidden_units=[], hidden_activations="ReLU", reduction_ratio=1, dropout_rates=0, layer_norm=True):
+        super(ParallelMaskNet, self).__init__()
+        self.num_blocks = num_blocks
+        self.mask_blocks = nn.ModuleList([MaskBlock(input_dim, input_dim, block_dim, hidden_activations,
+                                                    reduction_ratio, dropout_rates, layer_norm)
+                                          for _ in range(num_blocks)])
+        self.dnn = MLP_Block(input_dim=block_dim * num_blocks, output_dim=output_dim, hidden_units=hidden_units,
+                             hidden_activations=hidden_activations, output_activation=output_activation,
+                             dropout_rates=dropout_rates)
+        self.fused = True
+
+    def forward(self, V_emb, V_hidden):
+        if self.fused:
+            concat_out = mask_stage(list(self.mask_blocks), V_emb, V_hidden)
+        else:
+            concat_out = torch.cat([block(V_emb, V_hidden) for block in self.mask_blocks], dim=-1)
+        return self.dnn(concat_out)
+
 
 def link_fusion(model):
     """Called by BaseModel.compile(): tell the model's embedding layer which LogisticRegression

@@ -1132,6 +1132,74 @@ def bilinear_bwd(X, W, kind, A, dOut, dX, dA, dW, workspace, dout_col=0, dx_accu
     return dX, dA, dW
 
 
+# ---- MaskNet: grouped LayerNorm (+ ReLU) and the mask's gradient toward V_hidden --------------------
+LAYERNORM_MAX_N = 8192    # elements of one normalised group
+LAYERNORM_MAX_G = 64      # groups per row (fields of emb_norm)
+
+
+def layernorm_check(G, N, who="layernorm"):
+    """The limits of fx_layernorm_*, raised here before anything is launched."""
+    if not 1 <= N <= LAYERNORM_MAX_N:
+        raise NotImplementedError("{}: N={}, the kernel's limit is 1 <= N <= {}".format(who, N, LAYERNORM_MAX_N))
+    if not 1 <= G <= LAYERNORM_MAX_G:
+        raise NotImplementedError("{}: G={}, the kernel's limit is 1 <= G <= {}".format(who, G, LAYERNORM_MAX_G))
+
+
+def layernorm_workspace_floats(rows, G, N):
+    return int(_lib.load().fx_layernorm_workspace_floats(rows, G, N))
+
+
+def _ln_bytes_fwd(X, G, N, *a, **kw):
+    return 4.0 * (2.0 * X.shape[0] * G * N + 2.0 * G * N + 2.0 * X.shape[0] * G)     # x, y; gamma, beta; stats
+
+
+def _ln_bytes_bwd(X, G, N, gamma, relu, *a, **kw):
+    # x and dY twice (dX pass, dgamma / dbeta pass), Y's sign twice with the ReLU, dX once
+    return 4.0 * X.shape[0] * G * N * (5.0 + (2.0 if relu else 0.0) + (1.0 if kw.get("dx_accumulate") else 0.0))
+
+
+@_timed("layernorm_fwd", "layernorm", _ln_bytes_fwd)
+def layernorm_fwd(X, G, N, gamma, beta, eps, relu, Y, stats, y_col=0):
+    """Y[:, y_col : y_col + G*N] = LayerNorm over every one of the G groups of N columns of X[:, :G*N] (+ ReLU);
+    X, Y: [rows, >= ...] with unit column stride and any row stride; gamma, beta: G*N floats; stats: rows*G*2."""
+    _need_cuda(X, "X")
+    layernorm_check(G, N)
+    assert X.shape[1] >= G * N and Y.shape[0] == X.shape[0] and Y.shape[1] >= y_col + G * N
+    assert gamma.is_contiguous() and beta.is_contiguous() and gamma.numel() == G * N == beta.numel()
+    check(_lib.load().fx_layernorm_fwd(ptr(X), _rows(X), X.shape[0], G, N, ptr(gamma), ptr(beta), eps,
+                                       1 if relu else 0, ptr(Y), _rows(Y), y_col, ptr(stats),
+                                       stream_ptr(X.device)), "fx_layernorm_fwd")
+    return Y
+
+
+@_timed("layernorm_bwd", "layernorm", _ln_bytes_bwd)
+def layernorm_bwd(X, G, N, gamma, relu, Y, stats, dY, dX, dgamma, dbeta, workspace, y_col=0, dy_col=0,
+                  dx_accumulate=False):
+    """dY in the layout of the forward's Y (its own column offset); dX [rows, >= G*N] (any row stride, added to
+    when dx_accumulate); dgamma, dbeta: G*N floats.  Y (None without the ReLU) is read for its sign."""
+    _need_cuda(X, "X")
+    layernorm_check(G, N)
+    assert dY.shape[0] == X.shape[0] and dY.shape[1] >= dy_col + G * N and dX.shape[1] >= G * N
+    assert dgamma.is_contiguous() and dbeta.is_contiguous() and gamma.is_contiguous()
+    check(_lib.load().fx_layernorm_bwd(ptr(X), _rows(X), X.shape[0], G, N, ptr(gamma), 1 if relu else 0,
+                                       ptr(Y) if relu else None, _rows(Y) if relu else 0, y_col, ptr(stats),
+                                       ptr(dY), _rows(dY), dy_col, ptr(dX), _rows(dX),
+                                       1 if dx_accumulate else 0, ptr(dgamma), ptr(dbeta), ptr(workspace),
+                                       stream_ptr(X.device)), "fx_layernorm_bwd")
+    return dX, dgamma, dbeta
+
+
+@_timed("mask_grad", "layernorm", lambda dM, Vmask, H, nb, out, **kw: 4.0 * dM.shape[0] * H * (2.0 * nb + 1.0))
+def mask_grad(dM, Vmask, H, nb, out, accumulate=False):
+    """out[:, :H] (+)= sum_k dM[:, k*H:(k+1)*H] * Vmask[:, k*H:(k+1)*H]; every tensor [rows, >= ...] with unit
+    column stride and any row stride."""
+    _need_cuda(dM, "dM")
+    assert dM.shape[1] >= nb * H and Vmask.shape[1] >= nb * H and out.shape[1] >= H
+    check(_lib.load().fx_mask_grad(ptr(dM), _rows(dM), ptr(Vmask), _rows(Vmask), dM.shape[0], H, nb, ptr(out),
+                                   _rows(out), 1 if accumulate else 0, stream_ptr(dM.device)), "fx_mask_grad")
+    return out
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

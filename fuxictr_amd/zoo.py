@@ -1,9 +1,10 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt and FiBiNET, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET and MaskNet, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
-model_zoo/FiBiNET/src/FiBiNET.py:45-104), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/FiBiNET/src/FiBiNET.py:45-104,
+model_zoo/MaskNet/src/MaskNet.py:51-123), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -14,9 +15,9 @@ import torch
 from torch import nn
 
 from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
-                     FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FxLinear,
+                     FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FieldLayerNorm, FxLinear,
                      InnerProductInteraction, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
-                     SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
+                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
 from . import ops
 from .rank_model import BaseModel
 
@@ -391,3 +392,47 @@ class FiBiNET(_ZooModel):
                              dim=1).flatten(start_dim=1)
         # the linear part rides into the tower's head through the last GEMM's epilogue
         return {"y_pred": self.output_activation(self.dnn(comb, out_add=self.lr_layer(X)))}
+
+
+class MaskNet(_ZooModel):
+    def __init__(self, feature_map, model_id="MaskNet", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[64, 64, 64], dnn_hidden_activations="ReLU", model_type="SerialMaskNet",
+                 parallel_num_blocks=1, parallel_block_dim=64, reduction_ratio=1, embedding_regularizer=None,
+                 net_regularizer=None, net_dropout=0, emb_layernorm=True, net_layernorm=True, **kwargs):
+        if model_type not in ("SerialMaskNet", "ParallelMaskNet"):
+            # (the reference leaves `mask_net` unset here and fails at the first forward, MaskNet.py:76-95)
+            raise ValueError("model_type={} not supported: SerialMaskNet or ParallelMaskNet".format(model_type))
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        width = feature_map.num_fields * embedding_dim
+        # the head's sigmoid sits inside `mask_net` as its output activation (MaskNet.py:79, 88), as DIN's does
+        if model_type == "SerialMaskNet":
+            self.mask_net = SerialMaskNet(input_dim=width, output_dim=1, output_activation=self.output_activation,
+                                          hidden_units=dnn_hidden_units, hidden_activations=dnn_hidden_activations,
+                                          reduction_ratio=reduction_ratio, dropout_rates=net_dropout,
+                                          layer_norm=net_layernorm)
+        else:
+            self.mask_net = ParallelMaskNet(input_dim=width, output_dim=1, output_activation=self.output_activation,
+                                            num_blocks=parallel_num_blocks, block_dim=parallel_block_dim,
+                                            hidden_units=dnn_hidden_units, hidden_activations=dnn_hidden_activations,
+                                            reduction_ratio=reduction_ratio, dropout_rates=net_dropout,
+                                            layer_norm=net_layernorm)
+        self.num_fields = feature_map.num_fields
+        self.emb_norm = FieldLayerNorm(self.num_fields, embedding_dim) if emb_layernorm else None
+        # fused=False: module by module, as the reference's class composes them (one LayerNorm launch per field and
+        # their cat, V_mask * V_hidden as a tensor, LayerNorm and ReLU apart): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_MASKNET_FUSED", "1") != "0"))
+        self.mask_net.fused = self._fused
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # [B, F, D]
+        flat = emb.flatten(start_dim=1)
+        if self.emb_norm is None:
+            V_hidden = flat
+        elif self._fused:
+            V_hidden = self.emb_norm(emb)                   # one grouped launch over the gather record
+        else:
+            V_hidden = torch.cat([norm(emb[:, i, :]) for i, norm in enumerate(self.emb_norm)], dim=1)
+        return {"y_pred": self.mask_net(flat, V_hidden)}

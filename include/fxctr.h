@@ -730,6 +730,39 @@ int fx_bilinear_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t 
                     float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MaskNet's LayerNorms (model_zoo/MaskNet/src/MaskNet.py:97-99 and MaskNet.py:116-118: one
+ * nn.LayerNorm(embedding_dim) per field on the gather record; MaskNet.py:254-257: LayerNorm(output_dim) + ReLU
+ * behind a mask block's hidden GEMM), torch.nn.LayerNorm's formulas over G groups of N elements per row:
+ *     x = X[r * x_ld + g * N + n];  mu = mean_n x;  var = mean_n (x - mu)^2;  rstd = 1 / sqrt(var + eps)
+ *     z = (x - mu) * rstd * gamma[g, n] + beta[g, n];   Y[r * y_ld + y_col + g * N + n] = relu ? max(z, 0) : z
+ *     stats[r, g] = (mu, rstd)                          gamma, beta: [G, N]; stats: [rows, G, 2]
+ * The variance is summed from the centred values held in registers.  Y is written at column y_col of rows of
+ * y_ld floats: the blocks of a ParallelMaskNet land in one buffer without the cat of MaskNet.py:231.
+ *   fx_layernorm_bwd : with gh = dY * gamma * [Y > 0 if relu] and xh = (x - mu) * rstd
+ *                          dX (+)= rstd * (gh - mean_n gh - xh * mean_n(gh xh))       (added when dx_accumulate)
+ *                          dgamma[g, n] = sum_r dY' xh,  dbeta[g, n] = sum_r dY'      (dY' = dY * [Y > 0 if relu])
+ *                      Y (the forward's, read for its sign only) may be NULL when relu == 0.  dgamma / dbeta: one
+ *                      partial per slab of rows into workspace, then a fixed-order sum (deterministic, no atomics).
+ * workspace: fx_layernorm_workspace_floats(rows, G, N) floats.   Limits: 1 <= N <= 8192, 1 <= G <= 64.
+ * 16-byte accesses when N % 4 == 0 and every pointer / stride / column offset is 16-byte aligned, scalar otherwise.
+ *
+ * fx_mask_grad: the instance-guided mask V_mask * V_hidden (MaskNet.py:272-273), its gradient toward V_hidden
+ *     out[r, h] (+)= sum_{k < nb} dM[r, k * H + h] * Vmask[r, k * H + h]             (added when accumulate)
+ * nb = 1: a serial block; nb = num_blocks: the blocks of a ParallelMaskNet (MaskNet.py:229-230) share V_hidden and
+ * keep dM / Vmask as column ranges of one buffer each.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fx_layernorm_workspace_floats(int64_t rows, int32_t G, int32_t N);
+int fx_layernorm_fwd(const float* X, int64_t x_ld, int64_t rows, int32_t G, int32_t N, const float* gamma,
+                     const float* beta, float eps, int32_t relu, float* Y, int64_t y_ld, int64_t y_col,
+                     float* stats, fx_stream_t stream);
+int fx_layernorm_bwd(const float* X, int64_t x_ld, int64_t rows, int32_t G, int32_t N, const float* gamma,
+                     int32_t relu, const float* Y, int64_t y_ld, int64_t y_col, const float* stats,
+                     const float* dY, int64_t dy_ld, int64_t dy_col, float* dX, int64_t dx_ld,
+                     int32_t dx_accumulate, float* dgamma, float* dbeta, float* workspace, fx_stream_t stream);
+int fx_mask_grad(const float* dM, int64_t dm_ld, const float* Vmask, int64_t vm_ld, int64_t rows, int32_t H,
+                 int32_t nb, float* out, int64_t out_ld, int32_t accumulate, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
