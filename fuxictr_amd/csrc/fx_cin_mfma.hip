@@ -78,11 +78,20 @@ __global__ __launch_bounds__(256) void k_cin_pack_w(CinPackArgs pa) {      // bl
 
 // Sample rows (X0, Xi, dX0, dXi) are accessed through buffer resources: the address is one VGPR offset
 // per sample and block + an immediate, no per-access 64-bit arithmetic, and a read past the tensor's
-// last valid float returns 0.  Rows past F0 / Mi of any other sample read its neighbour's (finite) data
-// and meet the zero rows / columns of the W image.
+// last valid float returns 0.  The K loops walk whole blocks of rows; a load of a row h >= F0 or m >= Mi
+// is sent out of range and returns 0 too (rows of X0 / dX0: the empty resource below; rows of Xi:
+// FX_CIN_OOB in the lane's offset): what follows a sample's rows in memory (the next sample, the padding
+// of a strided view) is never read, so a NaN or Inf there cannot meet the zero rows / columns of the W
+// image (0 * NaN = NaN).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fx_cin_rsrc(const float* p, int64_t B, int64_t ld, int rows) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0,
                                              (int)(((B - 1) * ld + (int64_t)rows * 16) * 4), 0x00020000);
+}
+
+// the same tensor with no valid bytes: every load through it returns 0.  The K loops pick this resource
+// for a row h >= F0 (wave-uniform: a scalar select of the descriptor, the VGPR offset + immediate stay)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t fx_cin_rsrc_none(const float* p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, 0, 0x00020000);
 }
 
 // the whole byte offset travels in the VGPR + immediate (the part the range check sees)
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_fwd_mfma(CinArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) bias4[i] = (4 * kk + i < O) ? a.bias[4 * kk + i] : 0.f;
     const int64_t stride = (int64_t)gridDim.x * FX_CIN_WAVES * NS;
-    const __amdgpu_buffer_rsrc_t rs0 = fx_cin_rsrc(a.X0, a.B, a.x0_ld, F0);
+    const __amdgpu_buffer_rsrc_t rs0 = fx_cin_rsrc(a.X0, a.B, a.x0_ld, F0), rsz = fx_cin_rsrc_none(a.X0);
     const __amdgpu_buffer_rsrc_t rsi = fx_cin_rsrc(a.Xi, a.B, a.xi_ld, Mi);
     bool staged = false;
     for (int64_t base = ((int64_t)blockIdx.x * FX_CIN_WAVES + wave) * NS; base < a.B; base += stride) {
@@ -142,7 +151,8 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_fwd_mfma(CinArgs a) {
             x0v[s] = (unsigned)((b * a.x0_ld + r) * 4);
             const unsigned xiv = (unsigned)((b * a.xi_ld + kk * 16 + r) * 4);      // row m = 4*mq + kk
 #pragma unroll
-            for (int mq = 0; mq < MQ; ++mq) xi[s][mq] = fx_cin_bload(rsi, xiv + mq * 256);
+            for (int mq = 0; mq < MQ; ++mq)
+                xi[s][mq] = fx_cin_bload(rsi, 4 * mq + kk < Mi ? xiv + mq * 256 : FX_CIN_OOB);
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[s][i] = 0.f;
         }
@@ -152,7 +162,7 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_fwd_mfma(CinArgs a) {
             for (int s = 0; s < NS; ++s) {
                 const unsigned v = x0v[s] + h0 * 64;
 #pragma unroll
-                for (int hh = 0; hh < HB; ++hh) x[s][hh] = fx_cin_bload(rs0, v + hh * 64);
+                for (int hh = 0; hh < HB; ++hh) x[s][hh] = fx_cin_bload(h0 + hh < F0 ? rs0 : rsz, v + hh * 64);
             }
         };
         auto compute = [&](const float (&x)[NS][HB], int h0) {
@@ -225,7 +235,7 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_dx_mfma(CinArgs a) {
     }
     for (int e = nt * 256 + threadIdx.x; e < fx_cin_rows_padded(F0) * MT * 256; e += NT) Wb[e] = 0.f;
     const bool accd = a.acc_dx0 != 0;
-    const __amdgpu_buffer_rsrc_t rs0 = fx_cin_rsrc(a.X0, a.B, a.x0_ld, F0);
+    const __amdgpu_buffer_rsrc_t rs0 = fx_cin_rsrc(a.X0, a.B, a.x0_ld, F0), rsz = fx_cin_rsrc_none(a.X0);
     const __amdgpu_buffer_rsrc_t rsd = fx_cin_rsrc(a.dX0, a.B, a.dx0_ld, F0);
     const __amdgpu_buffer_rsrc_t rsi = fx_cin_rsrc(a.Xi, a.B, a.xi_ld, Mi);
     const __amdgpu_buffer_rsrc_t rsx = fx_cin_rsrc(a.dXi, a.B, a.dxi_ld, Mi);
@@ -256,7 +266,8 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_dx_mfma(CinArgs a) {
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    xi[s][mt][i] = fx_cin_bload(rsi, xiv[s] + mt * 1024 + i * 64);
+                    xi[s][mt][i] = fx_cin_bload(rsi, 16 * mt + 4 * kk + i < Mi ? xiv[s] + mt * 1024 + i * 64
+                                                                              : FX_CIN_OOB);
                     dxi[s][mt][i] = 0.f;
                 }
         }
@@ -268,7 +279,7 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_dx_mfma(CinArgs a) {
             for (int s = 0; s < NS; ++s) {
                 const unsigned vx = x0v[s] + h0 * 64;
 #pragma unroll
-                for (int hh = 0; hh < HB; ++hh) x[s][hh] = fx_cin_bload(rs0, vx + hh * 64);
+                for (int hh = 0; hh < HB; ++hh) x[s][hh] = fx_cin_bload(h0 + hh < F0 ? rs0 : rsz, vx + hh * 64);
             }
         };
         auto compute = [&](const float (&x)[NS][HB], int h0) {
@@ -277,7 +288,8 @@ __global__ __launch_bounds__(64 * FX_CIN_WAVES) void k_cin_dx_mfma(CinArgs a) {
             for (int s = 0; s < NS; ++s) {
                 const unsigned vd = d0v[s] + h0 * 64;
 #pragma unroll
-                for (int hh = 0; hh < HB; ++hh) old[s][hh] = accd ? fx_cin_bload(rsd, vd + hh * 64) : 0.f;
+                for (int hh = 0; hh < HB; ++hh)
+                    old[s][hh] = accd ? fx_cin_bload(h0 + hh < F0 ? rsd : rsz, vd + hh * 64) : 0.f;
             }
 #pragma unroll
             for (int hh = 0; hh < HB; ++hh) {

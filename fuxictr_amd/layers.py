@@ -2497,7 +2497,8 @@ class DIN_Attention(nn.Module):
 class _CINFn(torch.autograd.Function):
     """Whole CIN stack as one autograd node (compressed_interaction_net.py:54-76); returns the
     concatenated pooled outputs [B, sum(O_i)].  args = (X0, W1, b1, W2, b2, ...), W_i = Conv1d
-    weights [O_i, F0*M_i, 1]."""
+    weights [O_i, F0*M_i, 1].  A layer whose W exceeds what one fx_cin_* call keeps in LDS
+    (ops.CIN_MAX_W_FLOATS) runs as several calls over runs of its output maps (ops.cin_chunks)."""
 
     @staticmethod
     def forward(ctx, x0, *wb):
@@ -2506,14 +2507,18 @@ class _CINFn(torch.autograd.Function):
         n = len(wb) // 2
         total = sum(wb[2 * i].shape[0] for i in range(n))
         pooled = torch.empty(B, total, dtype=torch.float32, device=x0.device)
-        # matrix-core shapes: every layer's W laid out once as its kernels' LDS images (one launch per 4)
-        imgs, todo, Mi = [None] * n, [], F0
+        # matrix-core shapes: every call's W laid out once as its kernels' LDS images (one launch per 4)
+        chunks, imgs, todo, Mi = [], [], [], F0
         for i in range(n):
             O = wb[2 * i].shape[0]
-            nimg = ops.cin_wimg_floats(F0, Mi, D, O)
-            if nimg:
-                imgs[i] = torch.empty(nimg, dtype=torch.float32, device=x0.device)
-                todo.append((wb[2 * i].view(O, -1), F0, Mi, imgs[i]))
+            chunks.append(ops.cin_chunks(F0, Mi, O))
+            imgs.append([None] * len(chunks[i]))
+            for c, (o0, o1) in enumerate(chunks[i]):
+                nimg = ops.cin_wimg_floats(F0, Mi, D, o1 - o0)
+                if nimg:
+                    imgs[i][c] = torch.empty(nimg, dtype=torch.float32, device=x0.device)
+                    Wv = wb[2 * i].view(O, -1)
+                    todo.append((Wv if o1 - o0 == O else Wv[o0:o1], F0, Mi, imgs[i][c]))
             Mi = O
         for k in range(0, len(todo), 4):
             ops.cin_pack_w(todo[k:k + 4], D)
@@ -2523,16 +2528,23 @@ class _CINFn(torch.autograd.Function):
             W, b = wb[2 * i], wb[2 * i + 1]
             O = W.shape[0]
             xn = torch.empty(B, O, D, dtype=torch.float32, device=x0.device)
-            ops.cin_fwd(x0, xi, W.view(O, -1), b, xn, pooled[:, off:off + O], imgs[i])
+            if len(chunks[i]) == 1:
+                ops.cin_fwd(x0, xi, W.view(O, -1), b, xn, pooled[:, off:off + O], imgs[i][0])
+            else:
+                for c, (o0, o1) in enumerate(chunks[i]):      # Xn of a call is contiguous: a temporary
+                    part = torch.empty(B, o1 - o0, D, dtype=torch.float32, device=x0.device)
+                    ops.cin_fwd(x0, xi, W.view(O, -1)[o0:o1], b[o0:o1], part,
+                                pooled[:, off + o0:off + o1], imgs[i][c])
+                    xn[:, o0:o1].copy_(part)
             xs.append(xn)
             xi = xn
             off += O
-        ctx.wb, ctx.xs, ctx.imgs = wb, xs, imgs
+        ctx.wb, ctx.xs, ctx.imgs, ctx.chunks = wb, xs, imgs, chunks
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
-        wb, xs = ctx.wb, ctx.xs
+        wb, xs, chunks = ctx.wb, ctx.xs, ctx.chunks
         x0 = xs[0]
         B, F0, D = x0.shape
         n = len(wb) // 2
@@ -2544,18 +2556,28 @@ class _CINFn(torch.autograd.Function):
             W = wb[2 * i]
             offs.append(offs[-1] + W.shape[0])
             cols.append(cols[-1] + W.shape[0] * W.shape[1] + W.shape[0])
-        # the layers' per-workgroup dW / dbias sums are column slices of one buffer: one column sum at
-        # the end finishes all of them
+        # the calls' per-workgroup dW / dbias sums are column slices of one buffer (a layer's calls side
+        # by side, each [its rows of dW | its dbias]): one column sum at the end finishes all of them
         partial = torch.empty(G, cols[-1], dtype=torch.float32, device=x0.device)
-        dxn = None
+        dxn, first = None, True
         for i in range(n - 1, -1, -1):
             W = wb[2 * i]
-            O = W.shape[0]
+            O, C = W.shape[0], W.shape[1]
             xi = xs[i]
             dxi = torch.empty_like(xi)
-            ops.cin_bwd(x0, xi, W.view(O, -1), dxn, dpooled[:, offs[i]:offs[i + 1]], dx0,
-                        accumulate_dx0=(i != n - 1), dXi=dxi, partial=partial[:, cols[i]:cols[i + 1]],
-                        w_img=ctx.imgs[i])
+            col = cols[i]
+            for c, (o0, o1) in enumerate(chunks[i]):
+                whole = len(chunks[i]) == 1
+                g = dxn if (whole or dxn is None) else dxn[:, o0:o1].contiguous()
+                out = dxi if c == 0 else torch.empty_like(xi)
+                width = (o1 - o0) * C + (o1 - o0)
+                ops.cin_bwd(x0, xi, W.view(O, -1) if whole else W.view(O, -1)[o0:o1], g, dpooled[:, offs[i] + o0:offs[i] + o1], dx0,
+                            accumulate_dx0=not first, dXi=out, partial=partial[:, col:col + width],
+                            w_img=ctx.imgs[i][c])
+                if c:
+                    dxi += out
+                col += width
+                first = False
             dxn = dxi
         red = torch.empty(cols[-1], dtype=torch.float32, device=x0.device)
         ws = _Workspace.get(x0.device, _lib.FX_COLSUM_CHUNKS * cols[-1])
@@ -2563,9 +2585,15 @@ class _CINFn(torch.autograd.Function):
         grads = [None] * (2 * n)
         for i in range(n):
             W = wb[2 * i]
-            nw = W.shape[0] * W.shape[1]
-            grads[2 * i] = red[cols[i]:cols[i] + nw].view(W.shape)
-            grads[2 * i + 1] = red[cols[i] + nw:cols[i + 1]]
+            C = W.shape[1]
+            dws, dbs, col = [], [], cols[i]
+            for o0, o1 in chunks[i]:
+                nw = (o1 - o0) * C
+                dws.append(red[col:col + nw].view(o1 - o0, C, 1))
+                dbs.append(red[col + nw:col + nw + o1 - o0])
+                col += nw + o1 - o0
+            grads[2 * i] = dws[0] if len(dws) == 1 else torch.cat(dws)
+            grads[2 * i + 1] = dbs[0] if len(dbs) == 1 else torch.cat(dbs)
         dx0 = dx0 + dxn        # layer 1 reads X0 on both sides of the outer product
         return (dx0,) + tuple(grads)
 

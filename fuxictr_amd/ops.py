@@ -963,6 +963,24 @@ def dot_interact_bwd(emb, g, F, D, demb, tail=0):
 
 
 # ---- CIN ------------------------------------------------------------------------------------------
+# the limits of one fx_cin_fwd / fx_cin_bwd call (include/fxctr.h:640 "Limits", csrc/fx_cin.hip fx_cin_check)
+CIN_MAX_W_FLOATS = 30720     # O*F0*Mi + O: the LDS-resident W
+CIN_MAX_TILE = 4096          # F0*D, Mi*D and O*D of one call (a sample's staged tiles)
+CIN_MAX_D = 256
+
+
+def cin_chunks(F0, Mi, O):
+    """[(o0, o1)]: the output maps of a CIN layer cut into the fewest, equal-as-possible runs whose
+    W fits one call (CIN_MAX_W_FLOATS).  A function of (F0, Mi, O) alone."""
+    per_call = CIN_MAX_W_FLOATS // (F0 * Mi + 1)
+    if per_call < 1:
+        raise ValueError("CIN layer: one output map of F0*Mi = %d weights exceeds the %d floats of a call"
+                         % (F0 * Mi, CIN_MAX_W_FLOATS))
+    n = -(-O // per_call)
+    size = -(-O // n)
+    return [(o0, min(o0 + size, O)) for o0 in range(0, O, size)]
+
+
 def cin_workgroups():
     return int(_lib.load().fx_cin_workgroups())
 

@@ -635,7 +635,10 @@ int fx_din_attn_bwd(const float* q, int64_t q_ld, const float* K, int64_t k_ldb,
  *     dX0 (+)= ..., dXi = ..., partial[G][O*F0*Mi + O] = per-workgroup sums of dW and dbias
  *     (G = fx_cin_workgroups(), row stride partial_ld >= O*F0*Mi + O: the layers of a stack write column
  *     slices of ONE [G, sum] buffer; finish with one fx_colsum over G).
- * Limits: O*F0*Mi + O <= 30720 floats per call (LDS-resident weights), D <= 256.
+ * Only the F0 (Mi) rows of a sample are read or written: with x0_ld > F0*D (xi_ld, dx0_ld, dxi_ld alike) what
+ * lies between two samples may hold anything, NaN included, and a sample never sees another one's values.
+ * Limits: O*F0*Mi + O <= 30720 floats per call (LDS-resident weights), D <= 256; a wider layer is run as
+ * several calls over runs of its output maps (rows of W, bias, Xn and dXn; dX0 accumulates, dXi is summed).
  * D = 16, O <= 16, F0 <= 40, Mi <= 40 (the BASELINE xDeepFM: 39 fields, 16 dims, 16 maps) run on the
  * matrix cores: per sample the compress step is W [16 x F0*Mi] times the outer product [F0*Mi x 16],
  * formed in registers.  For those shapes fx_cin_wimg_floats > 0 and fx_cin_pack_w lays the W of up to 4

@@ -750,7 +750,17 @@ def cin_pack_w(layers, D):
     return None
 
 
+def _cin_limits(F0, Mi, D, O):
+    # fx_cin_check (include/fxctr.h: "Limits" of fx_cin_fwd / fx_cin_bwd): what the device rejects
+    from fuxictr_amd import ops
+    assert O * F0 * Mi + O <= ops.CIN_MAX_W_FLOATS, "fx_cin: O*F0*Mi + O = %d floats exceed %d; split O" % (
+        O * F0 * Mi + O, ops.CIN_MAX_W_FLOATS)
+    assert max(F0, Mi, O) * D <= ops.CIN_MAX_TILE and D <= ops.CIN_MAX_D, "fx_cin: tile too large"
+
+
 def cin_fwd(X0, Xi, W, bias, Xn, pool, w_img=None):
+    _cin_limits(X0.shape[1], Xi.shape[1], X0.shape[2], W.shape[0])
+    assert Xn.is_contiguous() and W.is_contiguous() and bias.is_contiguous()
     had = torch.einsum("bhd,bmd->bhmd", X0, Xi).reshape(X0.shape[0], -1, X0.shape[2])
     out = torch.einsum("oc,bcd->bod", W, had) + bias.view(1, -1, 1)
     Xn.copy_(out)
@@ -761,6 +771,9 @@ def cin_fwd(X0, Xi, W, bias, Xn, pool, w_img=None):
 def cin_bwd(X0, Xi, W, dXn, dpool, dX0, accumulate_dx0, dXi, partial, w_img=None):
     B, F0, D = X0.shape
     Mi, O = Xi.shape[1], W.shape[0]
+    _cin_limits(F0, Mi, D, O)
+    assert (dXn is None or dXn.is_contiguous()) and W.is_contiguous()
+    assert partial.stride(0) >= O * F0 * Mi + O, "fx_cin_bwd: partial_ld < O*F0*Mi + O"
     g = torch.zeros(B, O, D)
     if dXn is not None:
         g = g + dXn

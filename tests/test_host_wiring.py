@@ -722,3 +722,49 @@ def test_row_record_host_logic(tmp_path, monkeypatch):
     for k, v in model.state_dict().items():
         assert v.dtype == torch.float64 or not v.is_floating_point()
         assert torch.equal(v.float(), ref[k].float()), k
+
+
+@pytest.mark.parametrize("F0,units,D,B", [(39, [32, 32, 32], 4, 5), (10, [64, 32], 8, 5)])
+def test_cin_layers_wider_than_one_call_are_split_over_output_maps(F0, units, D, B, monkeypatch):
+    """The reference's default CIN ([32, 32, 32] on 39 fields) holds more weights per layer than one fx_cin_*
+    call keeps in LDS (ops.CIN_MAX_W_FLOATS; the emulation asserts the header's limits like the device does):
+    _CINFn cuts such a layer into runs of output maps.  Its docstring example ([64, 32] on 10 fields) fits and
+    takes one call per layer.  Forward and every gradient against fp64 autograd of the reference formula (compressed_interaction_net.py:54-76)."""
+    _cpu_emul.install(monkeypatch)
+    from fuxictr_amd import layers, ops
+    calls = []
+    real_fwd = ops.cin_fwd
+    monkeypatch.setattr(ops, "cin_fwd", lambda *a, **k: (calls.append(a[2].shape[0]), real_fwd(*a, **k))[1])
+    gen = torch.Generator().manual_seed(F0 + D)
+    cin = layers.CompressedInteractionNet(F0, units)
+    with torch.no_grad():
+        for p_ in cin.parameters():
+            p_.copy_(torch.randn(p_.shape, generator=gen) * (0.5 / max(1, p_[0].numel()) ** 0.5))
+    x = (torch.randn(B, F0, D, generator=gen) * 0.5).requires_grad_(True)
+    gy = torch.randn(B, 1, generator=gen)
+    cin(x).backward(gy)
+    expect = [o1 - o0 for u, m in zip(units, [F0] + units) for o0, o1 in ops.cin_chunks(F0, m, u)]
+    assert calls == expect
+    if F0 == 39:       # 32*39*39 + 32 and 32*39*32 + 32 floats: every layer takes two calls of 16 maps
+        assert calls == [16] * 6
+    else:              # 64*10*10 + 64 and 32*10*64 + 32 floats fit: one call per layer
+        assert calls == [64, 32]
+
+    x64 = x.detach().double().requires_grad_(True)
+    p64 = {k: v.detach().double().requires_grad_(True) for k, v in cin.named_parameters()}
+    xi, pooled = x64, []
+    for i in range(len(units)):
+        had = torch.einsum("bhd,bmd->bhmd", x64, xi).reshape(B, -1, D)
+        xi = torch.einsum("oc,bcd->bod", p64["cin_layer.layer_%d.weight" % (i + 1)][:, :, 0], had) \
+            + p64["cin_layer.layer_%d.bias" % (i + 1)].view(1, -1, 1)
+        pooled.append(xi.sum(-1))
+    ref = torch.cat(pooled, dim=1) @ p64["fc.weight"].t() + p64["fc.bias"]
+    ref.backward(gy.double())
+    with torch.no_grad():
+        out = cin(x)
+    # fp32 einsum of the emulation against fp64: chains of up to F0*Mi + D products of O(1) scale
+    np.testing.assert_allclose(out.numpy(), ref.detach().numpy(), rtol=0, atol=2e-5 * max(1.0, float(ref.detach().abs().max())))
+    for name, got, want in [("x", x.grad, x64.grad)] + [(k, v.grad, p64[k].grad) for k, v in cin.named_parameters()]:
+        assert got is not None and got.shape == want.shape, name
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=0, atol=2e-5 * max(1.0, float(want.abs().max())),
+                                   err_msg=name)
