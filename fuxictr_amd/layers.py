@@ -86,13 +86,40 @@ def get_initializer(initializer):
     return initializer
 
 
+class _BatchState(object):
+    """What the embedding path has already done for ONE batch: its packed input matrices (a captured
+    step keeps them as its static buffers) and the results of the current step's launches."""
+
+    def __init__(self, shared=True):
+        self.shared = shared      # False: the throwaway state of a plain dict batch (_batch_state)
+        self.packed = {}          # plan.pack_sig -> (ids int32 [B, C] | None, dense fp32 [B, Fd] | None)
+        self.keep_only_packs()
+
+    def keep_only_packs(self):
+        self.dedups = {}          # _TableGroup.dedup_key(plan) -> DedupResult
+        self.caught_up = set()    # (id(group), de-dup key): rows brought up to date (exact-mode Adam)
+        self.shards = {}          # de-dup key + (n_shards,) -> _ShardExchange
+        self.lr_out = {}          # id(LogisticRegression) -> its output out of the fused front end
+
+    def packs(self):
+        """-> (key, id_feats ((name, width), ..), num_feats (name, ..), ids, dense) per packed plan."""
+        for key, (ids, dense) in self.packed.items():
+            yield key, key[0], key[1], ids, dense
+
+
 class FeatureDict(dict):
-    """Batch dict with a per-batch cache (packed id matrices, de-dup results) shared by the
+    """Batch dict with a per-batch state (packed id matrices, de-dup results) shared by the
     embedding layers of one model, so the main and the LR tables pack / sort the ids once."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
-        self.cache = {}
+        self.cache = _BatchState()
+
+
+def _batch_state(inputs):
+    """A FeatureDict's state; a plain dict batch gets a throwaway one: nothing is shared between calls."""
+    state = getattr(inputs, "cache", None)
+    return state if state is not None else _BatchState(shared=False)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -189,7 +216,8 @@ class _TableGroup(object):
         self._shard_consts = {}
         self._reduce_scratch = {}
         self._await_exchange = []     # row-gradient buffers waiting for their all-to-all
-        self.dedup_ws = None
+        self._dense_plans = {}        # names -> pack plan of numeric inputs outside this group (pack_dense)
+        self.dedup_ws = None          # (n, de-dup workspace for n keys): _dedup_scratch
         self.opt = None               # the native optimizer this group is attached to
         # row sharding (owner = row % world, local row = row // world)
         self.dist = _DIST
@@ -407,11 +435,10 @@ class _TableGroup(object):
 
     # -- per-batch helpers ------------------------------------------------------------------
     def pack_inputs(self, plan, inputs):
-        """-> (ids int32 [B, C] or None, dense fp32 [B, Fd] or None); cached on a FeatureDict."""
-        cache = getattr(inputs, "cache", None)
-        ckey = ("pack", plan.pack_sig)
-        if cache is not None and ckey in cache:
-            return cache[ckey]
+        """-> (ids int32 [B, C] or None, dense fp32 [B, Fd] or None); kept on a FeatureDict."""
+        state = _batch_state(inputs)
+        if plan.pack_sig in state.packed:
+            return state.packed[plan.pack_sig]
         first = inputs[plan.id_feats[0][0] if plan.id_feats else plan.num_feats[0]]
         B = first.shape[0]
         ids = dense = None
@@ -421,8 +448,7 @@ class _TableGroup(object):
         if plan.Fd:
             dense = torch.empty(B, plan.Fd, dtype=torch.float32, device=self.device)
             ops.pack_columns([inputs[f] for f in plan.num_feats], dense)
-        if cache is not None:
-            cache[ckey] = (ids, dense)
+        state.packed[plan.pack_sig] = (ids, dense)
         return ids, dense
 
     def pack_dense(self, inputs, names):
@@ -430,10 +456,8 @@ class _TableGroup(object):
         through the same cast launch / cache as the group's own inputs (a captured step fills the
         block together with the id matrix, outside the graph).  DLRM's bottom-tower input."""
         key = tuple(names)
-        plan = self._dense_plans.get(key) if hasattr(self, "_dense_plans") else None
+        plan = self._dense_plans.get(key)
         if plan is None:
-            if not hasattr(self, "_dense_plans"):
-                self._dense_plans = {}
             plan = _Plan()
             plan.id_feats, plan.num_feats, plan.C, plan.Fd = [], list(names), 0, len(names)
             plan.pack_sig = ((), key)
@@ -456,24 +480,41 @@ class _TableGroup(object):
         rows received from their owners (slot matrix instead of ids)."""
         return plan.n_seq == 0 and _lib.row_lanes(self.D) <= 64
 
-    def dedup(self, plan, ids, inputs):
-        cache = getattr(inputs, "cache", None)
-        ckey = ("dedup", plan.sig, self.total_rows)
-        if cache is not None and ckey in cache:
-            return cache[ckey]
-        n = ids.shape[0] * ids.shape[1]
-        if self.dedup_ws is None or self.dedup_ws[0] != n:
-            self.dedup_ws = (n, torch.empty(ops.dedup_workspace_bytes(n), dtype=torch.uint8,
-                                            device=self.device))
-        # (the optimizer step's device-side opening rides in the de-dup's first launch)
+    def dedup_key(self, plan):
+        return (plan.sig, self.total_rows)
+
+    def _dedup_scratch(self, name, n):
+        """The de-dup workspace for n keys kept as self.<name> (dedup_ws / owner_ws)."""
+        ws = getattr(self, name)
+        if ws is None or ws[0] != n:
+            ws = (n, torch.empty(ops.dedup_workspace_bytes(n), dtype=torch.uint8, device=self.device))
+            setattr(self, name, ws)
+        return ws[1]
+
+    def _launch_dedup(self, plan, ids, state, catchup=None, owner_major=False):
+        """Workspace, the optimizer step's device-side opening (it rides in the de-dup's first launch), the
+        launch, the result into the batch state.  catchup: table groups whose rows the column fast path
+        (fx_dedup_catchup) brings up to date on the way.  owner_major: the sharded exchange needs
+        ascending global rows and keeps the result in its _ShardExchange."""
+        ws = self._dedup_scratch("dedup_ws", ids.shape[0] * ids.shape[1])
         begin = self.opt.take_begin() if self.opt is not None else None
-        # (unsharded: nothing downstream needs ascending rows — sequence schemas take the bucketed in-LDS path)
-        dd = ops.dedup(ids, plan.col_row_base, plan.col_vocab, plan.col_pad, self.total_rows,
-                       self.dedup_ws[1], columns_sorted=plan.columns_sorted, want_uid=True,
-                       begin_scal=begin, grouped=not self.sharded)
-        if cache is not None:
-            cache[ckey] = dd
+        if catchup is not None:
+            dd = ops.dedup_catchup(ids, plan.col_row_base, plan.col_vocab, plan.col_pad, ws,
+                                   [g.row_state() for g in catchup], self.scal, begin_scal=begin,
+                                   want_uid=True)
+        else:
+            # (unsharded: nothing downstream needs ascending rows — sequence schemas take the bucketed in-LDS path)
+            dd = ops.dedup(ids, plan.col_row_base, plan.col_vocab, plan.col_pad, self.total_rows, ws,
+                           columns_sorted=plan.columns_sorted, want_uid=True, begin_scal=begin,
+                           grouped=not (self.sharded or owner_major))
+        if not owner_major:
+            state.dedups[self.dedup_key(plan)] = dd
         return dd
+
+    def dedup(self, plan, ids, inputs):
+        state = _batch_state(inputs)
+        dd = state.dedups.get(self.dedup_key(plan))
+        return dd if dd is not None else self._launch_dedup(plan, ids, state)
 
     def select_num_w(self, plan):
         if plan.Fd == 0:
@@ -483,46 +524,33 @@ class _TableGroup(object):
         idx = torch.tensor(plan.num_rows, dtype=torch.int64, device=self.device)
         return self.num_w.index_select(0, idx)
 
-    def prepare_train(self, plan, ids, inputs, peers=()):
-        """De-dup the batch's rows; in exact mode bring them up to date before they are read.
+    def prepare_train(self, plan, ids, inputs, track, peers=()):
+        """Training forward (`track`) of an unsharded group (a sharded one de-dups in its exchange):
+        de-dup the batch's rows; in exact mode bring them up to date before they are read.
         peers: other table groups that are looked up with the SAME id plan in this step (the D=1
         tables of LogisticRegression): their rows are caught up in the same launch."""
-        if plan.C == 0 or self.opt_kind is None:
+        if not track or self.sharded or plan.C == 0 or self.opt_kind is None:
             return None
         if self.opt is not None:
             self.opt.ensure_begun()     # forward; backward; step(); zero_grad() loops: see optim.py
-        cache = getattr(inputs, "cache", None)
-        ckey = ("dedup", plan.sig, self.total_rows)
+        state = _batch_state(inputs)
+        key = self.dedup_key(plan)
         todo = [g for g in (self,) + tuple(peers)
-                if g.exact and g.opt_kind == "adam"
-                and not (cache is not None and ("caughtup", id(g), ckey) in cache)]
-        dd = cache.get(ckey) if cache is not None else None
+                if g.exact and g.opt_kind == "adam" and (id(g), key) not in state.caught_up]
+        dd = state.dedups.get(key)
         if dd is None and self.fast_columns(plan, ids.shape[0]):
-            n = ids.shape[0] * ids.shape[1]
-            if self.dedup_ws is None or self.dedup_ws[0] != n:
-                self.dedup_ws = (n, torch.empty(ops.dedup_workspace_bytes(n), dtype=torch.uint8,
-                                                device=self.device))
-            begin = self.opt.take_begin() if self.opt is not None else None
-            dd = ops.dedup_catchup(ids, plan.col_row_base, plan.col_vocab, plan.col_pad,
-                                   self.dedup_ws[1], [g.row_state() for g in todo], self.scal,
-                                   begin_scal=begin, want_uid=True)
-            if cache is not None:
-                cache[ckey] = dd
-                for g in todo:
-                    cache[("caughtup", id(g), ckey)] = True
-            return dd
-        if dd is None:
-            dd = self.dedup(plan, ids, inputs)
-        if todo:
-            # generic de-dup (sequence columns that alias a table, B > 8192): one launch for every table
-            # group of the id plan
-            ops.adam_catchup_rows([g.row_state() for g in todo], dd, -1, self.scal)
-            if cache is not None:
-                for g in todo:
-                    cache[("caughtup", id(g), ckey)] = True
+            dd = self._launch_dedup(plan, ids, state, catchup=todo)
+        else:
+            if dd is None:
+                dd = self._launch_dedup(plan, ids, state)
+            if todo:
+                # generic de-dup (sequence columns that alias a table, B > 8192): one launch for every table
+                # group of the id plan
+                ops.adam_catchup_rows([g.row_state() for g in todo], dd, -1, self.scal)
+        state.caught_up.update((id(g), key) for g in todo)
         return dd
 
-    def backward(self, plan, ids, dense, dout, dout_ld, col_off, num_off, dd, inputs_cache,
+    def backward(self, plan, ids, dense, dout, dout_ld, col_off, num_off, dd, inputs,
                  sx=None, denom=None):
         """Sparse + numeric gradients of one forward call (dout: grad of the output record)."""
         D = self.D
@@ -535,7 +563,7 @@ class _TableGroup(object):
             self.shard_backward(plan, sx, dout, dout_ld, col_off, col_denom, denom)
         elif plan.C:
             if dd is None:
-                dd = self.dedup(plan, ids, inputs_cache)
+                dd = self.dedup(plan, ids, inputs)
             G = torch.empty(dd.n_max, D, dtype=torch.float32, device=self.device)
             sq = torch.empty(ops.emb_grad_reduce_partials(dd.n_max, D), dtype=torch.float32,
                              device=self.device)
@@ -570,30 +598,24 @@ class _TableGroup(object):
         """De-dup the local lookups owner-major, route the unique keys to their owners (one
         all-to-all) and de-dup what this rank received as an owner.  Shared by table groups with
         the same id columns / row bases (the D=16 and the D=1 LR tables)."""
-        cache = getattr(inputs, "cache", None)
-        ckey = ("shard", plan.sig, self.total_rows, self.n_shards)
-        peers = _SHARD_PEERS.setdefault((plan.sig, self.total_rows, self.n_shards, id(self.dist)), [])
+        state = _batch_state(inputs)
+        ckey = self.dedup_key(plan) + (self.n_shards,)
+        peers = _SHARD_PEERS.setdefault(ckey + (id(self.dist),), [])
         if not any(p is self for p in peers):
             peers.append(self)
-        if cache is not None and ckey in cache:
-            return cache[ckey]
+        if ckey in state.shards:
+            return state.shards[ckey]
         if self.opt is not None and track:
             self.opt.ensure_begun()
         dev, N = self.device, self.n_shards
         n = ids.shape[0] * ids.shape[1]
-        if self.dedup_ws is None or self.dedup_ws[0] != n:
-            self.dedup_ws = (n, torch.empty(ops.dedup_workspace_bytes(n), dtype=torch.uint8,
-                                            device=dev))
         # unique GLOBAL rows in ascending order (the column fast path applies); owners and slots are
         # derived by counting in fx_shard_plan(global_keys), no owner-major device sort
-        begin = self.opt.take_begin() if self.opt is not None else None
-        dd = ops.dedup(ids, plan.col_row_base, plan.col_vocab, plan.col_pad, self.total_rows,
-                       self.dedup_ws[1], want_uid=True, columns_sorted=plan.columns_sorted,
-                       begin_scal=begin)
+        dd = self._launch_dedup(plan, ids, state, owner_major=True)
         cap = self.a2a_cap(n)
         sx = _ShardExchange()
         sx.dd, sx.cap = dd, cap
-        sx.key = (plan.sig, self.total_rows, N, id(self.dist))
+        sx.key = ckey + (id(self.dist),)
         sx.rows = {}                                  # id(group) -> fetched rows of this batch
         sx.send_idx = torch.empty(N * cap, dtype=torch.int32, device=dev)
         sx.uniq_slot = torch.empty(n, dtype=torch.int32, device=dev)
@@ -615,9 +637,7 @@ class _TableGroup(object):
             A2A_FILL_PROBE["even_share"] = -(-n // N)
         sx.recv_idx = self.dist.all_to_all(sx.send_idx).view(N * cap, 1)
         sx.grads = {}                                 # id(group) -> per-unique-key gradient (backward)
-        if self.owner_ws is None or self.owner_ws[0] != N * cap:
-            self.owner_ws = (N * cap, torch.empty(ops.dedup_workspace_bytes(N * cap),
-                                                  dtype=torch.uint8, device=dev))
+        owner_ws = self._dedup_scratch("owner_ws", N * cap)
         rps = self.rows_per_shard
         C = ids.shape[1]
         consts = self._shard_consts.get((C, cap))
@@ -632,10 +652,24 @@ class _TableGroup(object):
         sx.own_base, sx.own_vocab, sx.own_pad, sx.slot_base, sx.slot_vocab = consts
         # what arrived is N ascending runs (each peer's unique rows of this shard, pad rows at the
         # tail): merged by rank counting, no device sort
-        sx.owner_dd = ops.dedup_sorted_runs(sx.recv_idx, N, rps + 1, rps, self.owner_ws[1])
-        if cache is not None:
-            cache[ckey] = sx
+        sx.owner_dd = ops.dedup_sorted_runs(sx.recv_idx, N, rps + 1, rps, owner_ws)
+        state.shards[ckey] = sx
         return sx
+
+    def lookup_source(self, plan, ids, inputs, track, in_place=False, join=None):
+        """-> (table, src_ids, base, vocab, sx): what the gather kernels read.  Local: the table, the packed
+        ids, the plan's bases (sx None).  Row-sharded: ids -> owners, rows <- owners, then the same kernels
+        read the received rows through the per-lookup slot matrix; kernels that read packed [rows, D]
+        tables get this group's columns of the received block copied out, the fused front end reads them
+        `in_place`.  join: (group, plan) of the D=1 LR tables, routed by the same ids — it joins the
+        exchange before the rows are fetched: ONE all-to-all for both."""
+        if not (self.sharded and plan.C):
+            return self.table, ids, plan.col_row_base, plan.col_vocab, None
+        sx = self.shard_exchange_ids(plan, ids, inputs, track)
+        if join is not None:
+            join[0].shard_exchange_ids(join[1], ids, inputs, track)
+        rows = self.shard_fetch_rows(sx, track)
+        return (rows if in_place else rows.contiguous()), sx.lookup_slot, sx.slot_base, sx.slot_vocab, sx
 
     def shard_fetch_rows(self, sx, track):
         """Owner side: bring the requested rows up to date (exact mode) and gather them — every table
@@ -749,17 +783,7 @@ class _EmbGatherFn(torch.autograd.Function):
         B = (ids if ids is not None else dense).shape[0]
         D = group.D
         out = torch.empty(B, plan.n_slots * D, dtype=torch.float32, device=group.device)
-        sx = None
-        if group.sharded and plan.C:
-            # row-sharded: ids -> owners, rows <- owners, then the same kernels read the received
-            # rows through the per-lookup slot matrix
-            sx = group.shard_exchange_ids(plan, ids, inputs, track)
-            # (these kernels read packed [rows, D] tables: this group's columns of the received block
-            # are copied out; the fused front end — _EmbFMFn — reads the block in place)
-            table = group.shard_fetch_rows(sx, track).contiguous()
-            src, base, vocab = sx.lookup_slot, sx.slot_base, sx.slot_vocab
-        else:
-            table, src, base, vocab = group.table, ids, plan.col_row_base, plan.col_vocab
+        table, src, base, vocab, sx = group.lookup_source(plan, ids, inputs, track)
         ops.emb_gather_fwd(table, D, src, base, vocab, plan.col_out_off, dense,
                            group.select_num_w(plan), plan.num_out_off, out, group.ensure_scal(),
                            n_cols=plan.C_main if plan.n_seq else None)
@@ -770,7 +794,7 @@ class _EmbGatherFn(torch.autograd.Function):
                                  plan.seq_mode, plan.seq_out_off, out, denom, group.ensure_scal())
         ctx.group, ctx.plan, ctx.ids, ctx.dense, ctx.dd, ctx.sx = group, plan, ids, dense, dd, sx
         ctx.denom = denom if plan.col_denom is not None else None
-        ctx.inputs = inputs if hasattr(inputs, "cache") else None
+        ctx.inputs = inputs
         return out
 
     @staticmethod
@@ -799,21 +823,11 @@ class _EmbFMFn(torch.autograd.Function):
         dev = group.device
         out = torch.empty(B, plan.n_slots * D, dtype=torch.float32, device=dev)
         want_lr = lr_group is not None
-        sx = None
-        table, table1 = group.table, (lr_group.table if want_lr else None)
-        g_ids, g_base, g_vocab = ids, plan.col_row_base, plan.col_vocab
-        if group.sharded and plan.C:
-            # row-sharded tables: ids -> owners, rows back (ONE all-to-all for the D-float and the
-            # D=1 rows), then the same kernel reads the received rows through the slot matrix
-            sx = group.shard_exchange_ids(plan, ids, inputs, track)
-            if want_lr:
-                lr_group.shard_exchange_ids(lr_plan, ids, inputs, track)     # joins the row exchange
-            table = group.shard_fetch_rows(sx, track)
-            table1 = lr_group.shard_fetch_rows(sx, track) if want_lr else None
-            g_ids, g_base, g_vocab = sx.lookup_slot, sx.slot_base, sx.slot_vocab
-            if os.environ.get("FX_DEBUG_FUSED_SHARD") == "1":
-                print("[fx] fused front end on row-sharded tables (lr=%s fm=%s)" % (want_lr, want_fm),
-                      flush=True)
+        table, g_ids, g_base, g_vocab, sx = group.lookup_source(
+            plan, ids, inputs, track, in_place=True, join=(lr_group, lr_plan) if want_lr else None)
+        table1 = None
+        if want_lr:     # (sharded: fetched together with `table`, ONE all-to-all for the D-float and the D=1 rows)
+            table1 = lr_group.shard_fetch_rows(sx, track) if sx is not None else lr_group.table
         lr_out = torch.empty(B, 1, dtype=torch.float32, device=dev) if want_lr else None
         fm_out = torch.empty(B, 1, dtype=torch.float32, device=dev) if want_fm else None
         fm_lr = torch.empty(B, 1, dtype=torch.float32, device=dev) if (want_fm and want_lr) else None
@@ -827,7 +841,7 @@ class _EmbFMFn(torch.autograd.Function):
         ctx.group, ctx.plan, ctx.lr_group, ctx.lr_plan = group, plan, lr_group, lr_plan
         ctx.ids, ctx.dense, ctx.dd, ctx.out, ctx.S = ids, dense, dd, out, S
         ctx.sx = sx
-        ctx.inputs = inputs if hasattr(inputs, "cache") else None
+        ctx.inputs = inputs
         ctx.has_bias = lr_bias is not None
         return out, lr_out, fm_out, fm_lr
 
@@ -1163,8 +1177,7 @@ class FeatureEmbeddingDict(nn.Module):
                 # the fused front end: gather (+ first-order term + FM term), one launch
                 lr_mod, lr_grp, lr_plan = self._lr_peer_for(plan, feats, inputs)
                 peers = (lr_grp,) if lr_grp is not None else ()
-                dd = grp.prepare_train(plan, ids, inputs, peers) \
-                    if (track and not grp.sharded) else None
+                dd = grp.prepare_train(plan, ids, inputs, track, peers)
                 want_fm = bool(self._fuse_fm) and plan.n_slots == plan.C + plan.Fd \
                     and not (self._torch_feats or self._stock_feats)
                 out, lr_out, fm_out, fm_lr = _EmbFMFn.apply(
@@ -1173,14 +1186,14 @@ class FeatureEmbeddingDict(nn.Module):
                     lr_mod.bias if lr_grp is not None else None, grp, plan, lr_grp, lr_plan, ids,
                     dense, dd, inputs, want_fm, track)
                 front = {"lr_mod": lr_mod, "lr": lr_out, "fm": fm_out, "fm_lr": fm_lr}
-                if lr_grp is not None and hasattr(inputs, "cache"):
-                    inputs.cache[("lr_out", id(lr_mod))] = lr_out
+                if lr_grp is not None:
+                    _batch_state(inputs).lr_out[id(lr_mod)] = lr_out
             else:
                 if grp.table is not None and grp.table.dtype != torch.float32:
                     raise NotImplementedError(
                         "emb_dtype=bf16 is implemented for the fused column path only (every id "
                         "feature categorical with its own table, one embedding dim, batch <= 8192)")
-                dd = grp.prepare_train(plan, ids, inputs) if (track and not grp.sharded) else None
+                dd = grp.prepare_train(plan, ids, inputs, track)
                 out = _EmbGatherFn.apply(anchor, grp, plan, ids, dense, dd, inputs, track)
             rec = out.view(out.shape[0], plan.n_slots, D)
             if front is not None:
@@ -1239,7 +1252,7 @@ class FeatureEmbeddingDict(nn.Module):
         layer looks up the SAME id columns / numeric columns as `plan` (then both share one de-dup
         and one launch), else (None, None, None)."""
         lr = self._lr_peer
-        if lr is None or not hasattr(inputs, "cache"):
+        if lr is None or not _batch_state(inputs).shared:
             return None, None, None
         layer = lr.embedding_layer.embedding_layer
         groups = layer.table_groups()
@@ -1284,14 +1297,12 @@ class FeatureEmbeddingDict(nn.Module):
         """int32 view [B, width] of `feature`'s id columns in the packed id matrix of this batch (the
         forward packs it once, FeatureDict.cache), or None.  Lets a model use the raw ids as a
         padding mask (`X[f].long() != 0`, DIN.py:125) without cast / compare launches."""
-        cache = getattr(inputs, "cache", None) or {}
-        for key, val in cache.items():
-            if isinstance(key, tuple) and key and key[0] == "pack" and val[0] is not None:
-                col = 0
-                for name, width in key[1][0]:
-                    if name == feature:
-                        return val[0][:, col:col + width]
-                    col += width
+        for _, id_feats, _, ids, _ in _batch_state(inputs).packs():
+            col = 0
+            for name, width in id_feats if ids is not None else ():
+                if name == feature:
+                    return ids[:, col:col + width]
+                col += width
         return None
 
     def dict2tensor(self, embedding_dict, flatten_emb=False, feature_list=[], feature_source=[],
@@ -1467,17 +1478,10 @@ class _LRFn(torch.autograd.Function):
         B = (ids if ids is not None else dense).shape[0]
         out = torch.empty(B, 1, dtype=torch.float32, device=group.device)
         num_w1 = group.select_num_w(plan)
-        sx = None
-        if group.sharded and plan.C:
-            sx = group.shard_exchange_ids(plan, ids, inputs, track)
-            rows = group.shard_fetch_rows(sx, track).contiguous()
-            ops.lr_fwd(rows, sx.lookup_slot, sx.slot_base, sx.slot_vocab, dense, num_w1, bias,
-                       out, group.ensure_scal())
-        else:
-            ops.lr_fwd(group.table, ids, plan.col_row_base, plan.col_vocab, dense, num_w1, bias,
-                       out, group.ensure_scal())
+        table, src, base, vocab, sx = group.lookup_source(plan, ids, inputs, track)
+        ops.lr_fwd(table, src, base, vocab, dense, num_w1, bias, out, group.ensure_scal())
         ctx.group, ctx.plan, ctx.ids, ctx.dense, ctx.dd, ctx.sx = group, plan, ids, dense, dd, sx
-        ctx.inputs = inputs if hasattr(inputs, "cache") else None
+        ctx.inputs = inputs
         ctx.has_bias = bias is not None
         return out
 
@@ -1502,7 +1506,7 @@ class LogisticRegression(nn.Module):
                                                 use_sharing=False)
 
     def forward(self, X):
-        cached = X.cache.pop(("lr_out", id(self)), None) if hasattr(X, "cache") else None
+        cached = _batch_state(X).lr_out.pop(id(self), None)
         if cached is not None:
             return cached        # computed by the embedding layer's fused launch (_EmbFMFn)
         layer = self.embedding_layer.embedding_layer
@@ -1523,7 +1527,7 @@ class LogisticRegression(nn.Module):
         plan = grp.plan_for(feats, tail=[f for f in feats if fmap[f]["type"] == "sequence"])
         ids, dense = grp.pack_inputs(plan, X)
         track = torch.is_grad_enabled() and self.training
-        dd = grp.prepare_train(plan, ids, X) if (track and not grp.sharded) else None
+        dd = grp.prepare_train(plan, ids, X, track)
         return _LRFn.apply(layer._anchor(grp), self.bias, grp, plan, ids, dense, dd, X, track)
 
 
@@ -1656,8 +1660,7 @@ class FactorizationMachine(nn.Module):
     def forward(self, X, feature_emb):
         fused = getattr(feature_emb, "_fx_fused", None)
         if fused is not None and fused["lr_mod"] is self.lr_layer and fused["fm_lr"] is not None:
-            if hasattr(X, "cache"):
-                X.cache.pop(("lr_out", id(self.lr_layer)), None)
+            _batch_state(X).lr_out.pop(id(self.lr_layer), None)
             return fused["fm_lr"]        # gather + LR + FM came out of ONE launch (_EmbFMFn)
         lr_out = self.lr_layer(X)
         return _FMFn.apply(feature_emb, lr_out)

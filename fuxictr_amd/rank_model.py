@@ -312,23 +312,19 @@ class _GraphStep(object):
         self.label = label
         self.B = batch[label].shape[0]
         # which packed id / dense matrices the model's embedding layers ask for: run one eager
-        # step on a FeatureDict and read its cache
+        # step on a FeatureDict and read its packs
         probe = model.get_inputs(batch)
         probe._fx_ready = True
         probe[label] = batch[label].to(dev)
         self.probe_loss = model._side_stream_step(probe)
-        self.packs = []      # (sig, id feature names, numeric feature names, ids, dense)
+        self.packs = []      # (id feature names, numeric feature names, ids, dense)
         static = FeatureDict()
         static._fx_ready = True
-        for key, val in probe.cache.items():
-            if key[0] != "pack":
-                continue
-            ids, dense = val
-            id_feats, num_feats = key[1]
+        for key, id_feats, num_feats, ids, dense in probe.cache.packs():
             s_ids = torch.zeros_like(ids) if ids is not None else None
             s_dense = torch.zeros_like(dense) if dense is not None else None
-            self.packs.append((key, [f for f, _ in id_feats], list(num_feats), s_ids, s_dense))
-            static.cache[key] = (s_ids, s_dense)
+            self.packs.append(([f for f, _ in id_feats], list(num_feats), s_ids, s_dense))
+            static.cache.packed[key] = (s_ids, s_dense)
             col = 0
             for f, w in id_feats:
                 static[f] = s_ids[:, col] if w == 1 else s_ids[:, col:col + w]
@@ -341,8 +337,7 @@ class _GraphStep(object):
         self.y = torch.zeros(self.B, 1, dtype=torch.float32, device=dev)
         static[label] = self.y.view(-1)
         self.static = static
-        self._pack_keys = {k for k, *_ in self.packs}
-        self._fill_names = sorted({f for _, ids_n, num_n, _, _ in self.packs for f in ids_n + num_n})
+        self._fill_names = sorted({f for ids_n, num_n, _, _ in self.packs for f in ids_n + num_n})
         self._fill_cache = {}
         self._fill_stream = []       # ids of the cache entries that came in through train_step, oldest first
         self.fill(batch)
@@ -389,7 +384,7 @@ class _GraphStep(object):
                                 type(exc).__name__, exc)
                 model._dist.capture_collectives = False
                 # per-batch entries the aborted recording left in the static batch's cache
-                static.cache = {k: v for k, v in static.cache.items() if k in self._pack_keys}
+                static.cache.keep_only_packs()
                 model.optimizer._begun = False
                 model.optimizer._begin_pending = False
                 for grp in model.optimizer._groups:
@@ -400,7 +395,7 @@ class _GraphStep(object):
                                       if model._dist.capture_collectives else
                                       "hipGraph segments with the collectives launched between them")
         # the capture only recorded the step; drop per-batch caches created while recording
-        static.cache = {k: v for k, v in static.cache.items() if k in self._pack_keys}
+        static.cache.keep_only_packs()
 
     FILL_CACHE_MAX = 512       # batches registered through BaseModel.prepare_batch (bench.py's pool, epochs
     #                            over device-resident batches): the caller keeps those alive anyway
@@ -430,7 +425,7 @@ class _GraphStep(object):
         def col(f):
             return staged[f] if f in staged else batch[f].to(dev)
         items, srcs = [], []
-        for _, id_names, num_names, s_ids, s_dense in self.packs:
+        for id_names, num_names, s_ids, s_dense in self.packs:
             for dst, cols_ in ((s_ids, id_names), (s_dense, num_names)):
                 c0 = 0
                 for f in cols_ if dst is not None else ():
