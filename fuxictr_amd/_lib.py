@@ -142,6 +142,15 @@ SIGNATURES = {
     "fx_layernorm_bwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, i64, i64, vp, vp, i64, i64, vp, i64, i32,
                                vp, vp, vp, vp]),
     "fx_mask_grad": (i32, [vp, i64, vp, i64, i64, i32, i32, vp, i64, i32, vp]),
+    "fx_finalmlp_slab_rows": (i64, [i64]),
+    "fx_gate2_workspace_floats": (i64, [i64, i32]),
+    "fx_gate2_fwd": (i32, [vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+    "fx_gate2_bwd": (i32, [vp, i64, vp, i64, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, vp, i64, vp, i64,
+                           vp, vp]),
+    "fx_biagg_workspace_floats": (i64, [i64, i32, i32]),
+    "fx_biagg_fwd": (i32, [vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "fx_biagg_bwd": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp,
+                           vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

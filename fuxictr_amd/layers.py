@@ -3422,6 +3422,211 @@ class ParallelMaskNet(nn.Module):
         return self.dnn(concat_out)
 
 
+# ------------------------------------------------------------------------------------------------
+# FinalMLP: feature selection gates and the two-stream aggregation head
+# ------------------------------------------------------------------------------------------------
+# Rows that the gate tower of a FeatureSelection without context features runs on: row 0 is the `ctx_bias`, the rest
+# are zeros.  One row would do; the weight-gradient GEMM sums its bias gradient in the epilogue only when it
+# contracts over more than 8 rows (fx_gemm_f32: "rowsum is not available on the K<=8 / N<=4 skinny paths"), and 9 is
+# the smallest count that does.
+_GATE_ROWS = 9
+
+
+def _unit_cols(x):
+    """[rows, n] with unit column stride as fx_gate2_* / fx_biagg_* read it (any row stride, any alignment)."""
+    return x if x.stride(-1) == 1 else x.contiguous()
+
+
+class _FeatureGateFn(torch.autograd.Function):
+    """F1 = E * 2 sigmoid(Z1), F2 = E * 2 sigmoid(Z2) (FinalMLP.py:183-192) as ONE autograd node: one launch
+    forward; backward one launch, and the fixed-order sum of a [1, W] gate's dZ over the batch.  Z: the gate towers'
+    outputs before their Sigmoid, [B, W] or [1, W].  Z2 None: one gate.  Nothing but E and Z is kept."""
+
+    @staticmethod
+    def forward(ctx, e, z1, z2):
+        e, z1 = _unit_cols(e), z1.contiguous()
+        z2 = z2.contiguous() if z2 is not None else None
+        f1 = torch.empty(e.shape[0], e.shape[1], dtype=torch.float32, device=e.device)
+        f2 = torch.empty_like(f1) if z2 is not None else None
+        ops.gate2_fwd(e, z1, z2, f1, f2)
+        ctx.kept = (e, z1, z2)
+        if z2 is None:
+            return f1
+        return f1, f2
+
+    @staticmethod
+    def backward(ctx, df1, df2=None):
+        e, z1, z2 = ctx.kept
+        B, W = e.shape
+        dev = e.device
+
+        def grad(d):        # (an output that nothing consumed)
+            return _unit_cols(d) if d is not None else _zero_cols(B, W, dev)
+        df1 = grad(df1)
+        df2 = grad(df2) if z2 is not None else None
+        de = torch.empty(B, W, dtype=torch.float32, device=dev)
+        dz1 = torch.empty_like(z1)
+        dz2 = torch.empty_like(z2) if z2 is not None else None
+        ws = _Workspace.get(dev, ops.gate2_workspace_floats(B, W), tag="gate2")
+        ops.gate2_bwd(df1, df2, e, z1, z2, de, dz1, dz2, ws)
+        return de, dz1, dz2
+
+
+class FeatureSelection(nn.Module):
+    """FinalMLP.py:130-192: same constructor, the same attributes (keys `fsN_ctx_bias` or `fsN_ctx_emb.*`, and
+    `fsN_gate.mlp.*`).  Fused: each gate tower's Linear / ReLU prefix runs as its one node, the tower's own Sigmoid
+    module is skipped and both pre-activations go to _FeatureGateFn.  A gate without context features runs its tower
+    on the `ctx_bias` row alone (_GATE_ROWS rows, the rest zeros), not on B copies of it (FinalMLP.py:180).
+    fused = False: the reference's composition module by module."""
+
+    def __init__(self, feature_map, feature_dim, embedding_dim, fs_hidden_units=[], fs1_context=[], fs2_context=[]):
+        super(FeatureSelection, self).__init__()
+        dev = _alloc_device()
+        self.fs1_context, self.fs2_context = fs1_context, fs2_context
+        self._dim = embedding_dim
+        for n, context in ((1, fs1_context), (2, fs2_context)):
+            if len(context) == 0:
+                setattr(self, "fs%d_ctx_bias" % n, nn.Parameter(torch.zeros(1, embedding_dim, device=dev)))
+            else:
+                setattr(self, "fs%d_ctx_emb" % n, FeatureEmbedding(feature_map, embedding_dim,
+                                                                   required_feature_columns=context))
+        for n, context in ((1, fs1_context), (2, fs2_context)):      # (the reference's order of registration)
+            setattr(self, "fs%d_gate" % n, MLP_Block(input_dim=embedding_dim * max(1, len(context)),
+                                                     output_dim=feature_dim, hidden_units=fs_hidden_units,
+                                                     hidden_activations="ReLU", output_activation="Sigmoid",
+                                                     batch_norm=False))
+        self.fused = True
+
+    def _gate_input(self, n, X, rows):
+        context = self.fs1_context if n == 1 else self.fs2_context
+        if len(context) == 0:
+            return getattr(self, "fs%d_ctx_bias" % n).repeat(rows, 1)
+        return getattr(self, "fs%d_ctx_emb" % n)(X).flatten(start_dim=1)
+
+    def _gate_z(self, n, X):
+        """The gate tower's output before its Sigmoid: [B, W] with context features, [1, W] without."""
+        context = self.fs1_context if n == 1 else self.fs2_context
+        gate = getattr(self, "fs%d_gate" % n)
+        stack, tail = gate._fused
+        assert len(tail) == 1 and isinstance(tail[0], nn.Sigmoid)
+        wb = []
+        for lin, _ in stack:
+            wb += [lin.weight, lin.bias]
+        acts = tuple(r for _, r in stack)
+        if len(context) == 0:
+            bias = getattr(self, "fs%d_ctx_bias" % n)
+            inp = torch.cat([bias, _zero_cols(_GATE_ROWS - 1, bias.shape[1], bias.device)], dim=0)
+            return _MLPFn.apply(inp, acts, None, None, None, None, *wb)[:1]
+        inp = getattr(self, "fs%d_ctx_emb" % n)(X).flatten(start_dim=1)
+        return _MLPFn.apply(inp, acts, None, None, None, None, *wb)
+
+    def forward(self, X, flat_emb):
+        if self.fused:
+            return _FeatureGateFn.apply(flat_emb, self._gate_z(1, X), self._gate_z(2, X))
+        rows = flat_emb.size(0)
+        gt1 = self.fs1_gate(self._gate_input(1, X, rows)) * 2
+        feature1 = flat_emb * gt1
+        gt2 = self.fs2_gate(self._gate_input(2, X, rows)) * 2
+        feature2 = flat_emb * gt2
+        return feature1, feature2
+
+
+def _round_up(n, k):
+    return (n + k - 1) // k * k
+
+
+class _AggregationFn(torch.autograd.Function):
+    """out = w_x x + w_y y + sum_h x_h^T W_h y_h (FinalMLP.py:227-235, output_dim 1) as ONE autograd node.
+    Forward: T[:, h] = x_h W_h, the H per-head GEMMs on column slices in one gemm_batch call, then fx_biagg_fwd's one
+    pass over x, y, T (+ out_add).  Backward: fx_biagg_bwd (dT = g y, dY = g (w_y + T), g w_x^T, dw_x, dw_y, db and
+    their fixed-order sums), then one gemm_batch call with dW_h = x_h^T dT_h (split-K) and dX_h = dT_h W_h^T with
+    g w_x^T as the `add` of its epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, y, out_add, H, w_x, b_x, w_y, b_y, w_xy):
+        x, y = _unit_cols(x), _unit_cols(y)
+        B, dx = x.shape
+        dy = y.shape[1]
+        dxh, dyh = dx // H, dy // H
+        Wv = w_xy.view(H, dxh, dyh)
+        T = torch.empty(B, dy, dtype=torch.float32, device=x.device)
+        ops.gemm_batch([ops.gemm_problem(x[:, h * dxh:(h + 1) * dxh], Wv[h], T[:, h * dyh:(h + 1) * dyh])
+                        for h in range(H)])
+        out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
+        if out_add is not None:
+            out_add = out_add.contiguous()
+        ops.biagg_fwd(x, y, T, w_x, w_y, b_x, b_y, out_add, out)
+        ctx.kept = (x, y, T, w_x, w_y, Wv)
+        ctx.cfg = (H, dxh, dyh, out_add is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, y, T, w_x, w_y, Wv = ctx.kept
+        H, dxh, dyh, has_add = ctx.cfg
+        B, dx = x.shape
+        dy = y.shape[1]
+        dev = x.device
+        g = dout.contiguous()
+
+        def buf(*shape):
+            return torch.empty(*shape, dtype=torch.float32, device=dev)
+        dT, dY, dXr, dX = buf(B, dy), buf(B, dy), buf(B, dx), buf(B, dx)
+        dwx, dwy, db, dW = buf(1, dx), buf(1, dy), buf(2), buf(H, dxh, dyh)
+        ws = _Workspace.get(dev, ops.biagg_workspace_floats(B, dx, dy), tag="biagg")
+        ops.biagg_bwd(g, x, y, T, w_x, w_y, dT, dY, dXr, dwx, dwy, db, ws)
+        sk = max(_split_k_for(dxh, dyh, B), 1)
+        per = _round_up(ops.gemm_workspace_floats(dxh, dyh, sk), 64)     # every head its own split-K slabs
+        gws = _Workspace.get(dev, H * per, tag="biagg_dw")
+        problems = []
+        for h in range(H):
+            xs, ys = slice(h * dxh, (h + 1) * dxh), slice(h * dyh, (h + 1) * dyh)
+            problems.append(ops.gemm_problem(x[:, xs], dT[:, ys], dW[h], transa=True, split_k=sk,
+                                             workspace=gws[h * per:(h + 1) * per]))
+            problems.append(ops.gemm_problem(dT[:, ys], Wv[h], dX[:, xs], transb=True, add=dXr[:, xs]))
+        ops.gemm_batch(problems)
+        return dX, dY, (g if has_add else None), None, dwx, db[0:1], dwy, db[1:2], dW.view(-1, 1)
+
+
+class InteractionAggregation(nn.Module):
+    """FinalMLP.py:194-235: same constructor, the same keys (`w_x.*`, `w_y.*`, `w_xy`).  output_dim 1 only (what
+    FinalMLP builds, FinalMLP.py:101-104).  fused = False: the reference's composition from torch ops."""
+
+    def __init__(self, x_dim, y_dim, output_dim=1, num_heads=1):
+        super(InteractionAggregation, self).__init__()
+        assert x_dim % num_heads == 0 and y_dim % num_heads == 0, "Input dim must be divisible by num_heads!"
+        if output_dim != 1:
+            raise NotImplementedError("InteractionAggregation: output_dim={}, the fused head (fx_biagg_*) reduces "
+                                      "every sample to one logit: output_dim 1 only".format(output_dim))
+        dev = _alloc_device()
+        self.num_heads, self.output_dim = num_heads, output_dim
+        self.head_x_dim, self.head_y_dim = x_dim // num_heads, y_dim // num_heads
+        self.w_x = FxLinear(x_dim, output_dim, device=dev)
+        self.w_y = FxLinear(y_dim, output_dim, device=dev)
+        self.w_xy = nn.Parameter(torch.empty(num_heads * self.head_x_dim * self.head_y_dim, output_dim, device=dev))
+        nn.init.xavier_normal_(self.w_xy)
+        self.fused = True
+
+    def forward(self, x, y, out_add=None):
+        """out_add (native extension): a [batch, 1] tensor added to the result in the head kernel."""
+        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != self.num_heads * self.head_x_dim \
+                or y.shape[1] != self.num_heads * self.head_y_dim or x.shape[0] != y.shape[0]:
+            raise NotImplementedError("InteractionAggregation: inputs {} / {}, built for [batch, {}] / [batch, {}]"
+                                      .format(tuple(x.shape), tuple(y.shape), self.num_heads * self.head_x_dim,
+                                              self.num_heads * self.head_y_dim))
+        if self.fused:
+            return _AggregationFn.apply(x, y, out_add, self.num_heads, self.w_x.weight, self.w_x.bias,
+                                        self.w_y.weight, self.w_y.bias, self.w_xy)
+        output = self.w_x(x) + self.w_y(y)
+        head_x = x.view(-1, self.num_heads, self.head_x_dim)
+        head_y = y.view(-1, self.num_heads, self.head_y_dim)
+        xy = torch.matmul(torch.matmul(head_x.unsqueeze(2), self.w_xy.view(self.num_heads, self.head_x_dim, -1))
+                          .view(-1, self.num_heads, self.output_dim, self.head_y_dim),
+                          head_y.unsqueeze(-1)).squeeze(-1)
+        output = output + xy.sum(dim=1)
+        return output if out_add is None else output + out_add
+
+
 def link_fusion(model):
     """Called by BaseModel.compile(): tell the model's embedding layer which LogisticRegression
     and which FM-style interaction read the same batch, so that their work rides along in the

@@ -1218,6 +1218,109 @@ def mask_grad(dM, Vmask, H, nb, out, accumulate=False):
     return out
 
 
+# ---- FinalMLP: the two feature gates and the aggregation head ---------------------------------------
+def finalmlp_slab_rows(B):
+    """Rows of one slab of the backward kernels' sums over the batch."""
+    return int(_lib.load().fx_finalmlp_slab_rows(B))
+
+
+def gate2_workspace_floats(B, W):
+    return int(_lib.load().fx_gate2_workspace_floats(B, W))
+
+
+def biagg_workspace_floats(B, dx, dy):
+    return int(_lib.load().fx_biagg_workspace_floats(B, dx, dy))
+
+
+def _gate_ld(Z, B):
+    """Row stride of a gate's Z / dZ: 0 for the one row of a gate without context features."""
+    assert Z.dim() == 2 and Z.stride(1) == 1 and Z.shape[0] in (1, B)
+    return 0 if (Z.shape[0] == 1 and B > 1) else _rows(Z)
+
+
+def _gate_bytes_fwd(E, Z1, Z2, *a, **kw):
+    B, W = E.shape
+    n = 1 if Z2 is None else 2
+    return 4.0 * (B * W * (1.0 + n) + sum(z.numel() for z in (Z1, Z2) if z is not None))     # E, F; Z
+
+
+def _gate_bytes_bwd(dF1, dF2, E, Z1, Z2, *a, **kw):
+    B, W = E.shape
+    n = 1 if Z2 is None else 2
+    per = sum(z.shape[0] == B and B > 1 for z in (Z1, Z2) if z is not None)     # Z read, dZ written
+    return 4.0 * B * W * (2.0 + n + 2.0 * per + (1.0 if kw.get("de_accumulate") else 0.0))   # E, dE; dF
+
+
+@_timed("gate2_fwd", "finalmlp", _gate_bytes_fwd)
+def gate2_fwd(E, Z1, Z2, F1, F2):
+    """F1 = E * 2 sigmoid(Z1), F2 = E * 2 sigmoid(Z2) (Z2 None: one gate).  E, F: [B, W] with unit column stride
+    and any row stride; Z: [B, W] or [1, W] (one row for every sample)."""
+    _need_cuda(E, "E")
+    B, W = E.shape
+    assert Z1.shape[1] == W and tuple(F1.shape) == (B, W)
+    assert Z2 is None or (Z2.shape[1] == W and tuple(F2.shape) == (B, W))
+    two = Z2 is not None
+    check(_lib.load().fx_gate2_fwd(ptr(E), _rows(E), B, W, ptr(Z1), _gate_ld(Z1, B), ptr(Z2) if two else None,
+                                   _gate_ld(Z2, B) if two else 0, ptr(F1), _rows(F1), ptr(F2) if two else None,
+                                   _rows(F2) if two else 0, stream_ptr(E.device)), "fx_gate2_fwd")
+    return F1, F2
+
+
+@_timed("gate2_bwd", "finalmlp", _gate_bytes_bwd)
+def gate2_bwd(dF1, dF2, E, Z1, Z2, dE, dZ1, dZ2, workspace, de_accumulate=False):
+    """dE (+)= dF1 * 2 sigma(Z1) + dF2 * 2 sigma(Z2); dZi in the shape of Zi (a [1, W] gate's summed over the
+    batch through `workspace`, gate2_workspace_floats(B, W) floats)."""
+    _need_cuda(E, "E")
+    B, W = E.shape
+    two = Z2 is not None
+    assert tuple(dF1.shape) == (B, W) and tuple(dE.shape) == (B, W) and dZ1.shape == Z1.shape
+    assert not two or (tuple(dF2.shape) == (B, W) and dZ2.shape == Z2.shape)
+    check(_lib.load().fx_gate2_bwd(ptr(dF1), _rows(dF1), ptr(dF2) if two else None, _rows(dF2) if two else 0,
+                                   ptr(E), _rows(E), B, W, ptr(Z1), _gate_ld(Z1, B), ptr(Z2) if two else None,
+                                   _gate_ld(Z2, B) if two else 0, ptr(dE), _rows(dE), 1 if de_accumulate else 0,
+                                   ptr(dZ1), _gate_ld(dZ1, B), ptr(dZ2) if two else None,
+                                   _gate_ld(dZ2, B) if two else 0, ptr(workspace), stream_ptr(E.device)),
+          "fx_gate2_bwd")
+    return dE, dZ1, dZ2
+
+
+@_timed("biagg_fwd", "finalmlp", lambda X, Y, *a, **kw: 4.0 * X.shape[0] * (X.shape[1] + 2.0 * Y.shape[1] + 1.0))
+def biagg_fwd(X, Y, T, w_x, w_y, b_x, b_y, out_add, out):
+    """out[b] = b_x + b_y + X[b] . w_x + Y[b] . (w_y + T[b]) (+ out_add[b]).  X [B, dx], Y and T [B, dy] with unit
+    column stride and any row stride; w_x, w_y contiguous; b_x, b_y one float each or None; out, out_add: B
+    contiguous floats."""
+    _need_cuda(X, "X")
+    B, dx = X.shape
+    dy = Y.shape[1]
+    assert Y.shape[0] == B and tuple(T.shape) == (B, dy) and out.numel() == B and out.is_contiguous()
+    assert w_x.is_contiguous() and w_y.is_contiguous() and w_x.numel() == dx and w_y.numel() == dy
+    assert out_add is None or (out_add.numel() == B and out_add.is_contiguous())
+    check(_lib.load().fx_biagg_fwd(ptr(X), _rows(X), ptr(Y), _rows(Y), ptr(T), _rows(T), B, dx, dy, ptr(w_x),
+                                   ptr(w_y), ptr(b_x), ptr(b_y), ptr(out_add), ptr(out), stream_ptr(X.device)),
+          "fx_biagg_fwd")
+    return out
+
+
+@_timed("biagg_bwd", "finalmlp",
+        lambda g, X, Y, T, w_x, w_y, dT, dY, dXr, *a, **kw:
+        4.0 * X.shape[0] * (X.shape[1] * (1.0 if dXr is None else 2.0) + 4.0 * Y.shape[1] + 1.0))
+def biagg_bwd(g, X, Y, T, w_x, w_y, dT, dY, dXr, dw_x, dw_y, db, workspace):
+    """From g = dout [B]: dT = g * Y, dY = g * (w_y + T), dXr = g w_x^T (None: not wanted), dw_x = X^T g,
+    dw_y = Y^T g, db[0] = db[1] = sum g.  workspace: biagg_workspace_floats(B, dx, dy) floats."""
+    _need_cuda(X, "X")
+    B, dx = X.shape
+    dy = Y.shape[1]
+    assert g.numel() == B and g.is_contiguous() and tuple(dT.shape) == (B, dy) and tuple(dY.shape) == (B, dy)
+    assert dXr is None or tuple(dXr.shape) == (B, dx)
+    assert dw_x.is_contiguous() and dw_y.is_contiguous() and dw_x.numel() == dx and dw_y.numel() == dy
+    assert db.is_contiguous() and db.numel() == 2
+    check(_lib.load().fx_biagg_bwd(ptr(g), ptr(X), _rows(X), ptr(Y), _rows(Y), ptr(T), _rows(T), B, dx, dy,
+                                   ptr(w_x), ptr(w_y), ptr(dT), _rows(dT), ptr(dY), _rows(dY), ptr(dXr),
+                                   _rows(dXr) if dXr is not None else 0, ptr(dw_x), ptr(dw_y), ptr(db),
+                                   ptr(workspace), stream_ptr(X.device)), "fx_biagg_bwd")
+    return dT, dY, dXr, dw_x, dw_y, db
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

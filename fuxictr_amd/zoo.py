@@ -1,10 +1,11 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET and MaskNet, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP and DualMLP, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
 model_zoo/FiBiNET/src/FiBiNET.py:45-104,
-model_zoo/MaskNet/src/MaskNet.py:51-123), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/MaskNet/src/MaskNet.py:51-123,
+model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -15,8 +16,8 @@ import torch
 from torch import nn
 
 from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
-                     FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FieldLayerNorm, FxLinear,
-                     InnerProductInteraction, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
+                     FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
+                     FxLinear, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
 from . import ops
 from .rank_model import BaseModel
@@ -436,3 +437,64 @@ class MaskNet(_ZooModel):
         else:
             V_hidden = torch.cat([norm(emb[:, i, :]) for i, norm in enumerate(self.emb_norm)], dim=1)
         return {"y_pred": self.mask_net(flat, V_hidden)}
+
+
+class FinalMLP(_ZooModel):
+    def __init__(self, feature_map, model_id="FinalMLP", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 mlp1_hidden_units=[64, 64, 64], mlp1_hidden_activations="ReLU", mlp1_dropout=0,
+                 mlp1_batch_norm=False, mlp2_hidden_units=[64, 64, 64], mlp2_hidden_activations="ReLU",
+                 mlp2_dropout=0, mlp2_batch_norm=False, use_fs=True, fs_hidden_units=[64], fs1_context=[],
+                 fs2_context=[], num_heads=1, embedding_regularizer=None, net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        feature_dim = embedding_dim * feature_map.num_fields
+        self.mlp1 = self._tower(feature_dim, mlp1_hidden_units, mlp1_hidden_activations, mlp1_dropout,
+                                mlp1_batch_norm, output_dim=None)
+        self.mlp2 = self._tower(feature_dim, mlp2_hidden_units, mlp2_hidden_activations, mlp2_dropout,
+                                mlp2_batch_norm, output_dim=None)
+        self.use_fs = use_fs
+        if self.use_fs:
+            self.fs_module = FeatureSelection(feature_map, feature_dim, embedding_dim, fs_hidden_units, fs1_context,
+                                              fs2_context)
+        self.fusion_module = InteractionAggregation(mlp1_hidden_units[-1], mlp2_hidden_units[-1], output_dim=1,
+                                                    num_heads=num_heads)
+        # fused=False: module by module, as the reference's class composes them (the gate towers on B rows with their
+        # Sigmoid, the gates and the gated records as tensors, the head from two Linears and broadcast matmuls): the
+        # same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_FINALMLP_FUSED", "1") != "0"))
+        self.fusion_module.fused = self._fused
+        if self.use_fs:
+            self.fs_module.fused = self._fused
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        flat_emb = self.embedding_layer(X).flatten(start_dim=1)
+        if self.use_fs:
+            feat1, feat2 = self.fs_module(X, flat_emb)      # fused: both gates in one launch
+        else:
+            feat1, feat2 = flat_emb, flat_emb               # (no gate launch)
+        y_pred = self.fusion_module(self.mlp1(feat1), self.mlp2(feat2))
+        return {"y_pred": self.output_activation(y_pred)}
+
+
+class DualMLP(_ZooModel):
+    def __init__(self, feature_map, model_id="DualMLP", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 mlp1_hidden_units=[64, 64, 64], mlp1_hidden_activations="ReLU", mlp1_dropout=0,
+                 mlp1_batch_norm=False, mlp2_hidden_units=[64, 64, 64], mlp2_hidden_activations="ReLU",
+                 mlp2_dropout=0, mlp2_batch_norm=False, embedding_regularizer=None, net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        feature_dim = embedding_dim * feature_map.num_fields
+        self.mlp1 = self._tower(feature_dim, mlp1_hidden_units, mlp1_hidden_activations, mlp1_dropout,
+                                mlp1_batch_norm)
+        self.mlp2 = self._tower(feature_dim, mlp2_hidden_units, mlp2_hidden_activations, mlp2_dropout,
+                                mlp2_batch_norm)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        flat_emb = self.embedding_layer(X).flatten(start_dim=1)
+        # the second tower's logit rides into the first's head through the last GEMM's epilogue
+        y_pred = self.mlp1(flat_emb, out_add=self.mlp2(flat_emb))
+        return {"y_pred": self.output_activation(y_pred)}

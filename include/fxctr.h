@@ -766,6 +766,52 @@ int fx_mask_grad(const float* dM, int64_t dm_ld, const float* Vmask, int64_t vm_
                  int32_t nb, float* out, int64_t out_ld, int32_t accumulate, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FinalMLP's two non-tower stages (model_zoo/FinalMLP/src/FinalMLP.py), fp32, every matrix with its own row
+ * stride in floats (column slices and the gather record are read in place), 16-byte accesses when the widths
+ * are multiples of 4 and every base pointer and row stride is 16-byte aligned, scalar otherwise.  No atomics:
+ * sums over the batch are formed per slab of fx_finalmlp_slab_rows(B) rows into caller workspace and then in a
+ * fixed order (two runs give the same bits).
+ *
+ * The feature gates of FeatureSelection.forward (FinalMLP.py:179-192), both in one launch:
+ *     F1[b, c] = E[b, c] * 2 sigmoid(Z1[b, c]),   F2[b, c] = E[b, c] * 2 sigmoid(Z2[b, c])      c < W
+ * Z is the gate tower's output BEFORE its Sigmoid: [B, W] with row stride z_ld, or, with z_ld == 0, one row for
+ * every sample: a gate without context features, whose tower input the reference repeats B times
+ * (FinalMLP.py:180, FinalMLP.py:186).  The two gates choose independently.  Z2 == NULL: one gate, the arguments
+ * of the second are ignored.
+ *   fx_gate2_bwd : dE (+)= dF1 * 2 sigma(Z1) + dF2 * 2 sigma(Z2)                  (added when de_accumulate)
+ *                  dZi = dFi * E * 2 sigma(Zi) (1 - sigma(Zi))      [B, W] rows of dzi_ld for a per-sample gate,
+ *                  summed over the batch into W floats for a broadcast one (dzi_ld ignored).  The sigmoid is
+ *                  recomputed from Z.  workspace: fx_gate2_workspace_floats(B, W) floats, needed when a gate is
+ *                  broadcast.
+ *
+ * The head InteractionAggregation.forward with output_dim == 1 (FinalMLP.py:227-235):
+ *     out[b] = b_x + b_y + sum_j X[b, j] w_x[j] + sum_k Y[b, k] (w_y[k] + T[b, k])  (+ out_add[b])
+ * with T[:, h dyh : (h + 1) dyh] = X[:, h dxh : (h + 1) dxh] W_h, W_h = w_xy.view(H, dxh, dyh)[h], formed by the
+ * caller (fx_gemm_f32_batch on column slices).  b_x, b_y: one float each on the device (NULL: 0); out_add: B floats
+ * or NULL.  No width limit.
+ *   fx_biagg_bwd : from g[b] = dout[b]:  dT = g * Y,  dY = g * (w_y + T),  dXr = g w_x^T (NULL: not wanted; the
+ *                  caller's dX GEMM takes it as its `add`),  dw_x = X^T g,  dw_y = Y^T g,  db[0] = db[1] = sum g
+ *                  (one for each Linear's bias).  workspace: fx_biagg_workspace_floats(B, dx, dy) floats.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fx_finalmlp_slab_rows(int64_t B);
+int64_t fx_gate2_workspace_floats(int64_t B, int32_t W);
+int fx_gate2_fwd(const float* E, int64_t e_ld, int64_t B, int32_t W, const float* Z1, int64_t z1_ld,
+                 const float* Z2, int64_t z2_ld, float* F1, int64_t f1_ld, float* F2, int64_t f2_ld,
+                 fx_stream_t stream);
+int fx_gate2_bwd(const float* dF1, int64_t df1_ld, const float* dF2, int64_t df2_ld, const float* E, int64_t e_ld,
+                 int64_t B, int32_t W, const float* Z1, int64_t z1_ld, const float* Z2, int64_t z2_ld, float* dE,
+                 int64_t de_ld, int32_t de_accumulate, float* dZ1, int64_t dz1_ld, float* dZ2, int64_t dz2_ld,
+                 float* workspace, fx_stream_t stream);
+int64_t fx_biagg_workspace_floats(int64_t B, int32_t dx, int32_t dy);
+int fx_biagg_fwd(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, const float* T, int64_t t_ld,
+                 int64_t B, int32_t dx, int32_t dy, const float* w_x, const float* w_y, const float* b_x,
+                 const float* b_y, const float* out_add, float* out, fx_stream_t stream);
+int fx_biagg_bwd(const float* g, const float* X, int64_t x_ld, const float* Y, int64_t y_ld, const float* T,
+                 int64_t t_ld, int64_t B, int32_t dx, int32_t dy, const float* w_x, const float* w_y, float* dT,
+                 int64_t dt_ld, float* dY, int64_t dy_ld, float* dXr, int64_t dxr_ld, float* dw_x, float* dw_y,
+                 float* db, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
