@@ -3627,6 +3627,130 @@ class InteractionAggregation(nn.Module):
         return output if out_add is None else output + out_add
 
 
+class _GateCrossFn(torch.autograd.Function):
+    """GDCN's whole gated cross stack (GDCN.py:197-211) as ONE autograd node:
+        x_{i+1} = x_0 * (W_i x_i + b_i) * sigmoid(Wg_i x_i) + x_i.
+    Forward, per layer: one GEMM of x_i against the packed [2D, D] weight into h = [W x_i | Wg x_i], then
+    ops.gate_cross_fwd.  Backward, per layer: ops.gate_cross_bwd (dh, and dx_0's share), then the dW + dX pair of
+    linear_grads on dh with the residual gradient in the dX epilogue; at layer 0 that residual is dx_0, as in
+    _CrossNetV2Fn.  Kept for the backward: h and x_i of every layer; u and the gate are recomputed from h.
+    out_into: an optional [B, D] view (unit column stride) that the LAST layer writes x_n into and that is returned.
+    args = (x0, out_into, packed, w_0, wg_0, b_0, w_1, ...): `packed` the tuple of the [2D, D] storages that w_i and
+    wg_i are views of."""
+
+    @staticmethod
+    def forward(ctx, x0, out_into, packed, *params):
+        x0 = _rows_view(x0)
+        n = len(packed)
+        B, D = x0.shape
+        xs, hs = [x0], []
+        xi = x0
+        for i in range(n):
+            h = torch.empty(B, 2 * D, dtype=torch.float32, device=x0.device)
+            ops.gemm(xi, packed[i], h, transa=False, transb=True)
+            xn = out_into if (i == n - 1 and out_into is not None) else torch.empty_like(x0)
+            ops.gate_cross_fwd(h, x0, xi, params[3 * i + 2], xn)
+            hs.append(h)
+            if i < n - 1:
+                xs.append(xn)
+            xi = xn
+        ctx.packed, ctx.bs, ctx.xs, ctx.hs = packed, tuple(params[2::3]), xs, hs
+        return xi
+
+    @staticmethod
+    def backward(ctx, dxn):
+        packed, bs, xs, hs = ctx.packed, ctx.bs, ctx.xs, ctx.hs
+        n = len(packed)
+        x0 = xs[0]
+        D = x0.shape[1]
+        if dxn.stride(-1) != 1:
+            dxn = dxn.contiguous()         # (a row-strided slice of the head's gradient is read in place)
+        dx0 = torch.empty_like(x0)
+        dh = torch.empty_like(hs[0])       # one buffer: layer i's GEMMs have read it before layer i - 1 writes it
+        grads = [None] * (3 * n)
+        for i in range(n - 1, -1, -1):
+            ops.gate_cross_bwd(dxn, hs[i], x0, bs[i], dh, dx0, init=(i == n - 1), add_dxn=(i == 0))
+            # dW [2D, D]: the gradients of w_i and wg_i; the fused row sums [2D]: db_i and the (unused) sums of dv
+            dW, db, dxn = linear_grads(dh, xs[i], packed[i], True, add=(dx0 if i == 0 else dxn))
+            grads[3 * i], grads[3 * i + 1], grads[3 * i + 2] = dW[:D], dW[D:], db[:D]
+        return (dxn, None, None) + tuple(grads)
+
+
+class GateCrossLayer(nn.Module):
+    """GDCN.py:175-211 (`GateCorssLayer` there; the alias below keeps that spelling): the reference's keys
+    `w.<i>.weight` [D, D], `wg.<i>.weight` [D, D] (neither Linear has a bias) and `b.<i>` [D], b uniform(0, 1).
+    w_i and wg_i are views of ONE packed [2D, D] storage per layer (w on top of wg), as FieldLayerNorm's pairs
+    are of theirs: one GEMM gives both products, and state_dict / load_state_dict / the dense optimizer see
+    ordinary Parameters.  fused=False: module by module as the reference composes it (two FxLinear, torch
+    element-wise): the same numbers."""
+
+    def __init__(self, input_dim, cn_layers=3):
+        super(GateCrossLayer, self).__init__()
+        dev = _alloc_device()
+        self.cn_layers = cn_layers
+        self.w = nn.ModuleList(FxLinear(input_dim, input_dim, bias=False, device=dev) for _ in range(cn_layers))
+        self.wg = nn.ModuleList(FxLinear(input_dim, input_dim, bias=False, device=dev) for _ in range(cn_layers))
+        self.b = nn.ParameterList(nn.Parameter(torch.zeros(input_dim, device=dev)) for _ in range(cn_layers))
+        for i in range(cn_layers):
+            nn.init.uniform_(self.b[i].data)
+        self.activation = nn.Sigmoid()
+        self.fused = True
+        packed = []
+        for i in range(cn_layers):
+            p = torch.empty(2 * input_dim, input_dim, device=dev)
+            p[:input_dim].copy_(self.w[i].weight.data)
+            p[input_dim:].copy_(self.wg[i].weight.data)
+            packed.append(p)
+        self._packed = packed
+        self._bind_views()
+
+    def _bind_views(self):
+        for i, p in enumerate(self._packed):
+            D = p.shape[1]
+            self.w[i].weight.data = p[:D]
+            self.wg[i].weight.data = p[D:]
+
+    def _apply(self, fn, recurse=True):
+        # nn.Module.to() / cuda(): b and the buffers as always; the packed storages move once and the 2 n weight
+        # Parameters are re-pointed at them
+        super(GateCrossLayer, self)._apply(fn, recurse)
+        self._packed = [fn(p) for p in self._packed]
+        self._bind_views()
+        return self
+
+    def forward(self, x, out_into=None):
+        """out_into (native extension): see _GateCrossFn; ignored on the module-by-module route."""
+        if not self.fused or x.dim() != 2 or self.cn_layers < 1:
+            x0 = x
+            for i in range(self.cn_layers):
+                xw = self.w[i](x)                               # feature crossing
+                xg = self.activation(self.wg[i](x))             # information gate
+                x = x0 * (xw + self.b[i]) * xg + x
+            return x
+        params = []
+        for i in range(self.cn_layers):
+            params += [self.w[i].weight, self.wg[i].weight, self.b[i]]
+        return _GateCrossFn.apply(x, out_into, tuple(self._packed), *params)
+
+
+GateCorssLayer = GateCrossLayer          # the reference's spelling (GDCN.py:175)
+
+
+class _SideBySideFn(torch.autograd.Function):
+    """`buf` [B, Da + Db] already holds a in its first Da columns and b in the rest (both were written in place):
+    hand it on as the concatenation of the two, with the gradient's two column slices (row-strided views, read in
+    place by the producers' backward kernels) going back to a and b.  No launch either way."""
+
+    @staticmethod
+    def forward(ctx, buf, a, b):
+        ctx.Da = a.shape[1]
+        return buf
+
+    @staticmethod
+    def backward(ctx, dout):
+        return None, dout[:, :ctx.Da], dout[:, ctx.Da:]
+
+
 def link_fusion(model):
     """Called by BaseModel.compile(): tell the model's embedding layer which LogisticRegression
     and which FM-style interaction read the same batch, so that their work rides along in the

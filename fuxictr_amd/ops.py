@@ -1321,6 +1321,43 @@ def biagg_bwd(g, X, Y, T, w_x, w_y, dT, dY, dXr, dw_x, dw_y, db, workspace):
     return dT, dY, dXr, dw_x, dw_y, db
 
 
+# ---- GDCN: the element-wise half of the gated cross layer ----------------------------------------------
+def gate_cross_tile_rows():
+    """Rows of one workgroup's tile in the two kernels."""
+    return int(_lib.load().fx_gate_cross_tile_rows())
+
+
+@_timed("gate_cross_fwd", "gatecross", lambda h, *a, **kw: 4.0 * h.shape[0] * (h.shape[1] // 2) * 5.0)   # h, x0, xi; xn
+def gate_cross_fwd(h, x0, xi, b, xn):
+    """xn = x0 * (h[:, :cols] + b) * sigmoid(h[:, cols:]) + xi.  h: [rows, 2 cols]; x0, xi, xn: [rows, cols]; unit
+    column stride and any row stride each (xn may be a column range of a wider buffer)."""
+    _need_cuda(h, "h")
+    rows, cols = x0.shape
+    assert tuple(h.shape) == (rows, 2 * cols) and tuple(xi.shape) == (rows, cols) and tuple(xn.shape) == (rows, cols)
+    assert b.numel() == cols and b.is_contiguous()
+    check(_lib.load().fx_gate_cross_fwd(ptr(h), _rows(h), ptr(x0), _rows(x0), ptr(xi), _rows(xi), ptr(b), ptr(xn),
+                                        _rows(xn), rows, cols, stream_ptr(h.device)), "fx_gate_cross_fwd")
+    return xn
+
+
+@_timed("gate_cross_bwd", "gatecross",
+        lambda dxn, h, x0, b, dh, dx0, init, add_dxn:                       # dxn, h, x0; dh, dx0 (read when added to)
+        4.0 * h.shape[0] * (h.shape[1] // 2) * (7.0 if init else 8.0))
+def gate_cross_bwd(dxn, h, x0, b, dh, dx0, init, add_dxn):
+    """With u = h[:, :cols] + b and g = sigmoid(h[:, cols:]): dh[:, :cols] = dxn * x0 * g, dh[:, cols:] =
+    dxn * x0 * u * g * (1 - g), dx0 (= when init, += otherwise) dxn * u * g (+ dxn when add_dxn).  dxn is read in
+    place through its row stride (a column slice of a wider gradient)."""
+    _need_cuda(h, "h")
+    rows, cols = x0.shape
+    assert tuple(h.shape) == (rows, 2 * cols) and tuple(dh.shape) == (rows, 2 * cols)
+    assert tuple(dxn.shape) == (rows, cols) and tuple(dx0.shape) == (rows, cols)
+    assert b.numel() == cols and b.is_contiguous()
+    check(_lib.load().fx_gate_cross_bwd(ptr(dxn), _rows(dxn), ptr(h), _rows(h), ptr(x0), _rows(x0), ptr(b), ptr(dh),
+                                        _rows(dh), ptr(dx0), _rows(dx0), rows, cols, 1 if init else 0,
+                                        1 if add_dxn else 0, stream_ptr(h.device)), "fx_gate_cross_bwd")
+    return dh, dx0
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

@@ -1,11 +1,12 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP and DualMLP, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN and GDCNP, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
 model_zoo/FiBiNET/src/FiBiNET.py:45-104,
 model_zoo/MaskNet/src/MaskNet.py:51-123,
-model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101,
+model_zoo/GDCN/src/GDCN.py:24-172), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -17,8 +18,8 @@ from torch import nn
 
 from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
-                     FxLinear, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
-                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, din_record_layout)
+                     FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
+                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout)
 from . import ops
 from .rank_model import BaseModel
 
@@ -498,3 +499,75 @@ class DualMLP(_ZooModel):
         # the second tower's logit rides into the first's head through the last GEMM's epilogue
         y_pred = self.mlp1(flat_emb, out_add=self.mlp2(flat_emb))
         return {"y_pred": self.output_activation(y_pred)}
+
+
+def _gdcn_tower_units(name, dnn_hidden_units):
+    if not dnn_hidden_units:
+        # (the reference fails here too, but later and less clearly: GDCN leaves `dnn` None and its forward calls it,
+        # GDCN.py:139-146, 165; GDCNP reads dnn_hidden_units[-1] for `fc`, GDCN.py:74: an IndexError)
+        raise ValueError("{}: dnn_hidden_units is empty: the model needs its deep tower".format(name))
+    return list(dnn_hidden_units)
+
+
+class GDCN(_ZooModel):
+    """The stacked form (GDCN.py:104-172): the deep tower, ending in the logit, over the gated cross network."""
+
+    def __init__(self, feature_map, model_id="GDCN", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[], dnn_activations="ReLU", num_cross_layers=3, net_dropout=0, batch_norm=False,
+                 embedding_regularizer=None, net_regularizer=None, **kwargs):
+        units = _gdcn_tower_units("GDCN", dnn_hidden_units)
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        width = feature_map.sum_emb_out_dim()
+        self.dnn = self._tower(width, units, dnn_activations, net_dropout, batch_norm, output_dim=1)
+        self.cross_net = GateCrossLayer(width, num_cross_layers)
+        # fused=False: module by module, as the reference's class composes it (two Linears per layer, the sigmoid, the
+        # products and the sums as tensors): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_GDCN_FUSED", "1") != "0"))
+        self.cross_net.fused = self._fused
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        flat = self.embedding_layer(X, flatten_emb=True)    # [B, F*D]
+        return {"y_pred": self.output_activation(self.dnn(self.cross_net(flat)))}
+
+
+class GDCNP(_ZooModel):
+    """The parallel form (GDCN.py:24-101): the gated cross network and the deep tower side by side, `fc` over both."""
+
+    def __init__(self, feature_map, model_id="GDCNP", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[], dnn_activations="ReLU", num_cross_layers=3, net_dropout=0, batch_norm=False,
+                 embedding_regularizer=None, net_regularizer=None, **kwargs):
+        units = _gdcn_tower_units("GDCNP", dnn_hidden_units)
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        width = feature_map.sum_emb_out_dim()
+        self.dnn = self._tower(width, units, dnn_activations, net_dropout, batch_norm, output_dim=None)
+        self.cross_net = GateCrossLayer(width, num_cross_layers)
+        self.fc = FxLinear(units[-1] + width, 1, device=self.device)
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_GDCN_FUSED", "1") != "0"))
+        self.cross_net.fused = self._fused
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        flat = self.embedding_layer(X, flatten_emb=True)    # [B, F*D]
+        if not self._fused or self.cross_net.cn_layers < 1:
+            both = torch.cat([self.cross_net(flat), self.dnn(flat)], dim=1)
+        else:
+            # the last cross layer and the tower's last layer write side by side into one [B, D0 + H] buffer
+            D0, H = flat.shape[1], self.fc.in_features - flat.shape[1]
+            buf = torch.empty(flat.shape[0], D0 + H, dtype=torch.float32, device=flat.device)
+            # (two `.data` aliases: each has a version counter of its own, so autograd does not take the tower's write
+            # into the right half for an in-place change of the cross result it already handed out, and vice versa)
+            left, right = buf.data[:, :D0], buf.data[:, D0:]
+            cross = self.cross_net(flat, out_into=left)
+            deep = self.dnn(flat, out_into=right)
+            if deep.data_ptr() == right.data_ptr() and deep.stride() == right.stride():
+                both = _SideBySideFn.apply(buf, cross, deep)
+            else:
+                # MLP_Block takes out_into only when the whole tower is its fused Linear / ReLU node: with batch_norm,
+                # net_dropout > 0 or another activation the tower's result is a tensor of its own and is joined here
+                both = torch.cat([cross, deep], dim=1)
+        return {"y_pred": self.output_activation(self.fc(both))}

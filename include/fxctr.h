@@ -812,6 +812,29 @@ int fx_biagg_bwd(const float* g, const float* X, int64_t x_ld, const float* Y, i
                  float* db, float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GDCN / GDCNP (csrc/fx_gatecross.hip): the element-wise half of GateCorssLayer.forward (GDCN.py:197-211)
+ *     x_{i+1} = x_0 * (W_i x_i + b_i) * sigmoid(Wg_i x_i) + x_i
+ * h is the caller's one GEMM of x_i against the layer's packed [2 cols, cols] weight (GDCN.py:183-188: `w`
+ * stacked on `wg`): h[:, :cols] = u0 = W x_i, h[:, cols:] = v = Wg x_i.  b: cols floats (GDCN.py:190-194).
+ * fp32; every matrix has its own row stride in floats (xn may be a column range of a wider buffer, dxn a column
+ * slice of a wider gradient: nothing outside [0, cols) of a row is written); 16-byte accesses when cols is a
+ * multiple of 4 and every base pointer and row stride is 16-byte aligned, scalar otherwise.  No atomics: two runs
+ * give the same bits.  The sigmoid is formed from exp(-|v|): finite and accurate in both saturated tails.
+ *   fx_gate_cross_fwd : xn = x0 * (u0 + b) * sigmoid(v) + xi                                     (GDCN.py:208-210)
+ *   fx_gate_cross_bwd : with u = u0 + b and g = sigmoid(v), both recomputed from h:
+ *                       dh[:, :cols] = dxn * x0 * g,   dh[:, cols:] = dxn * x0 * u * g * (1 - g),
+ *                       dx0 (= when init, += otherwise) dxn * u * g, plus dxn when add_dxn (layer 0, whose x_i is
+ *                       x_0: the residual's gradient joins dx0); the flags of fx_cross_bwd_prep.
+ *   fx_gate_cross_tile_rows : rows of one workgroup's tile (housekeeping, for tests of the tile boundaries).
+ * ------------------------------------------------------------------------------------------ */
+int32_t fx_gate_cross_tile_rows(void);
+int fx_gate_cross_fwd(const float* h, int64_t ldh, const float* x0, int64_t ldx0, const float* xi, int64_t ldxi,
+                      const float* b, float* xn, int64_t ldxn, int64_t rows, int32_t cols, fx_stream_t stream);
+int fx_gate_cross_bwd(const float* dxn, int64_t lddxn, const float* h, int64_t ldh, const float* x0, int64_t ldx0,
+                      const float* b, float* dh, int64_t lddh, float* dx0, int64_t lddx0, int64_t rows, int32_t cols,
+                      int32_t init, int32_t add_dxn, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
