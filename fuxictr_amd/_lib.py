@@ -56,6 +56,13 @@ class GemmProblem(C.Structure):
                 ("epilogue", C.POINTER(GemmEpilogue)), ("split_k", i32), ("workspace", vp)]
 
 
+class GemmStrategyRecord(C.Structure):
+    """struct fx_gemm_strategy_record"""
+    _fields_ = [("strategy", i32), ("n_problems", i32), ("n", i32), ("swapped", i32),
+                ("arm", i32 * 4), ("tile_bm", i32 * 4), ("tile_bn", i32 * 4), ("split_k", i32 * 4),
+                ("tr", i32 * 4), ("plain_vec", i32 * 4)]
+
+
 # name -> (restype, argtypes).  This table is also what tests/test_abi.py checks against the header.
 SIGNATURES = {
     "fx_abi_version": (i32, []),
@@ -110,6 +117,7 @@ SIGNATURES = {
     "fx_gemm_f32_batch": (i32, [C.POINTER(GemmProblem), i32, vp]),
     "fx_gemm_f32": (i32, [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64,
                           C.POINTER(GemmEpilogue), i32, vp, vp]),
+    "fx_gemm_last_strategy": (i32, [C.POINTER(GemmStrategyRecord)]),
     "fx_colsum": (i32, [vp, i64, i64, i64, vp, vp, vp]),
     "fx_mask_mul": (i32, [vp, i64, vp, i64, vp, i64, i64, vp]),
     "fx_cross_bwd_prep": (i32, [vp, i64, vp, vp, vp, vp, i64, i64, i32, i32, vp]),

@@ -8,6 +8,43 @@
 
 #include <mutex>
 
+// The strategy record (fx_gemm_last_strategy): what the last fx_gemm_f32 / fx_gemm_f32_batch call of THIS thread
+// launched.  Host side only, a thread_local struct written on the way to the launch: nothing on the device, no
+// lock (backward batches come from the autograd engine's thread and have their own record).  Diagnostic only.
+static thread_local fx_gemm_strategy_record fx_rec;
+static thread_local bool fx_rec_in_batch = false;     // fx_gemm_f32 called from the single launches of a batch
+
+static void fx_rec_reset(int32_t n_problems) {
+    memset(&fx_rec, 0, sizeof(fx_rec));
+    fx_rec.n_problems = n_problems;
+}
+
+// one problem of the call: the arm that took it, its tile, its K slabs, 16-byte epilogue on / off.  A batch of
+// more than FX_GEMM_RECORD_SLOTS problems (single launches only) keeps the last ones.
+static void fx_rec_put(int slot, int32_t arm, int bm, int bn, int32_t split_k, bool tr) {
+    fx_rec.arm[slot] = arm; fx_rec.tile_bm[slot] = bm; fx_rec.tile_bn[slot] = bn;
+    fx_rec.split_k[slot] = split_k; fx_rec.tr[slot] = tr ? 1 : 0;
+    if (slot >= fx_rec.n) fx_rec.n = slot + 1;
+}
+
+static void fx_rec_push(int32_t arm, int bm, int bn, int32_t split_k, bool tr) {
+    if (fx_rec.n == FX_GEMM_RECORD_SLOTS) {
+        for (int i = 1; i < FX_GEMM_RECORD_SLOTS; ++i) {
+            fx_rec.arm[i - 1] = fx_rec.arm[i]; fx_rec.tile_bm[i - 1] = fx_rec.tile_bm[i];
+            fx_rec.tile_bn[i - 1] = fx_rec.tile_bn[i]; fx_rec.split_k[i - 1] = fx_rec.split_k[i];
+            fx_rec.tr[i - 1] = fx_rec.tr[i];
+        }
+        fx_rec.n = FX_GEMM_RECORD_SLOTS - 1;
+    }
+    fx_rec_put(fx_rec.n, arm, bm, bn, split_k, tr);
+    if (!fx_rec_in_batch) fx_rec.strategy = arm;
+}
+
+extern "C" int fx_gemm_last_strategy(fx_gemm_strategy_record* out) {
+    if (out) *out = fx_rec;
+    return fx_rec.strategy;
+}
+
 static int fx_gemm_pipe_mode() {   // FX_GEMM_PIPE=0 falls back to the unpipelined kernel (A/B runs)
     static const int mode = fx_env_int("FX_GEMM_PIPE", 1);
     return mode;
@@ -55,9 +92,11 @@ static int fx_gemm_prepare(int32_t transa, int32_t transb, int64_t M, int64_t N,
         // workgroup per CU all epilogues run at the same time and nothing covers them; with 64x64
         // tiles three workgroups share a CU and one's epilogue hides under the others' MFMAs.
         // Whole DeepFM step: 1.20 ms (64x64) vs 1.22 (128x64) vs 1.24 (128x128 where it fits).
-        // So: big tiles only when there are >= 4 waves of them (epilogues then overlap anyway).
+        // So: 128x128 only when there are >= 4 waves of them (epilogues then overlap anyway), 64x64 below that;
+        // 128x64 is the tile of N <= 64 alone.  (A rule "128x64 when that gives >= 2048 workgroups" stood between
+        // the two until it was seen that no shape reaches it: ceil(N/64) <= 2 ceil(N/128), so fewer than 1024
+        // workgroups of 128x128 are fewer than 2048 of 128x64.)
         const int64_t t128 = fx_ceil_div(M, 128) * fx_ceil_div(N, 128) * split_k;
-        const int64_t t12864 = fx_ceil_div(M, 128) * fx_ceil_div(N, 64) * split_k;
         if (forced == 2) { bn = 64; }
         else if (forced == 3) { bm = 64; bn = 64; }
         else if (forced == 0 && N <= 64) {
@@ -68,8 +107,7 @@ static int fx_gemm_prepare(int32_t transa, int32_t transb, int64_t M, int64_t N,
         // some boxes — 71.3 vs 71.4 us for 4096x1024x1024 — and loses 4 % on others — 78.2 vs 75.2 us,
         // whole DeepFM step 1.043 vs 1.026 ms, profiles/r03_gemm_lab_h.txt: the single launches keep 64x64)
         } else if (forced == 0 && t128 < 1024) {
-            if (t12864 >= 2048) bn = 64;
-            else { bm = 64; bn = 64; }
+            bm = 64; bn = 64;
         }
     }
     a.tiles_m = (int32_t)fx_ceil_div(M, bm);
@@ -144,27 +182,35 @@ extern "C" int fx_gemm_f32(int32_t transa, int32_t transb, int64_t M, int64_t N,
     int bm = 0, bn = 0;
     int rc = fx_gemm_prepare(transa, transb, M, N, K, A, lda, B, ldb, C, ldc, epi_host, split_k, workspace, a,
                              bm, bn);
+    if (!fx_rec_in_batch) fx_rec_reset(1);
     if (rc != FX_OK) return rc;
     if (M == 0 || N == 0) return FX_OK;
     hipStream_t s = fx_hip_stream(stream);
     FX_CHECK_ARG(!a.epi.rowsum || (K > 8 && !(N <= 4 && !transa)),
                  "fx_gemm_f32: epilogue.rowsum is not available on the K<=8 / N<=4 skinny paths");
-    if (fx_gemm_skinny_launch(transa, transb, a, s, &rc)) return rc;
+    if (fx_gemm_skinny_launch(transa, transb, a, s, &rc)) {
+        if (rc == FX_OK) fx_rec_push(FX_GEMM_SKINNY, 0, 0, a.split_k, false);
+        return rc;
+    }
     const bool a_kc = !transa, b_kc = transb != 0;
     if (fx_gemm_x6_ok(transa, transb, a)) {
         a.tiles_m = (int32_t)fx_ceil_div(M, 128);
         a.tiles_n = (int32_t)fx_ceil_div(N, 128);
         rc = fx_gemm_x6_launch(a_kc, b_kc, a, s);
         if (rc != FX_OK) return rc;
+        fx_rec_push(FX_GEMM_X6, 128, 128, a.split_k, true);
     } else if (fx_gemm_pipe_ok(transa, transb, a)) {
         rc = fx_gemm_tile_launch_pipe(bm, bn, a_kc, b_kc, a, s);
         if (rc != FX_OK) return rc;
         FX_CHECK_LAUNCH();
+        fx_rec_push(FX_GEMM_PIPE, bm, bn, a.split_k, fx_gemm_tr_ok(a));
     } else {
         bool av, bv;
         fx_gemm_operand_vec(transa, transb, a, av, bv);
         fx_gemm_tile_launch_plain(bm, bn, a_kc, b_kc, av, bv, a, s);
         FX_CHECK_LAUNCH();
+        fx_rec_push(FX_GEMM_PLAIN, bm, bn, a.split_k, false);
+        fx_rec.plain_vec[fx_rec.n - 1] = (av ? 1 : 0) | (bv ? 2 : 0);
     }
     if (a.split_k > 1) {
         fx_launch_splitk_reduce(a, s);
@@ -465,6 +511,8 @@ static int fx_batch_try_multi_x6(const fx_gemm_problem* p, int32_t n, fx_stream_
     if (rc != FX_OK) return rc;
     fx_launch_splitk_reduces(ma.p, n, s);
     FX_CHECK_LAUNCH();
+    for (int oi = 0; oi < n; ++oi) fx_rec_put(order[oi], FX_GEMM_MULTI_X6, 128, 128, ma.p[oi].split_k, true);
+    fx_rec.strategy = FX_GEMM_MULTI_X6;
     *launched = true;
     return FX_OK;
 }
@@ -517,6 +565,9 @@ static int fx_batch_try_multi(const fx_gemm_problem* p, int32_t n, fx_stream_t s
     FX_CHECK_LAUNCH();
     fx_launch_splitk_reduces(ma.p, n, s);
     FX_CHECK_LAUNCH();
+    for (int oi = 0; oi < n; ++oi)
+        fx_rec_put(order[oi], FX_GEMM_MULTI_F32, 128, (ma.cfg[oi] & 4) ? 64 : 128, ma.p[oi].split_k, true);
+    fx_rec.strategy = FX_GEMM_MULTI_F32;
     *launched = true;
     return FX_OK;
 }
@@ -544,6 +595,9 @@ static int fx_batch_try_pair_bwd(const fx_gemm_problem* p, int32_t n, fx_stream_
             fx_launch_splitk_reduce(a[i], s);
             FX_CHECK_LAUNCH();
         }
+    for (int i = 0; i < 2; ++i)
+        fx_rec_put(i, FX_GEMM_PAIR_BWD, 64, 64, a[i].split_k, fx_gemm_tr_ok(a[0]) && fx_gemm_tr_ok(a[1]));
+    fx_rec.strategy = FX_GEMM_PAIR_BWD;
     *launched = true;
     return FX_OK;
 }
@@ -573,6 +627,9 @@ static int fx_batch_try_head_bwd(const fx_gemm_problem* p, int32_t n, fx_stream_
     h.use_mask = (e1 && e1->mask) ? 1 : 0;
     rc = fx_head_bwd_launch(h, fx_hip_stream(stream));
     if (rc != FX_OK) return rc;
+    fx_rec_put(0, FX_GEMM_HEAD_BWD, 0, 0, h.dw.split_k, false);
+    fx_rec_put(1, FX_GEMM_HEAD_BWD, 0, 0, 1, false);
+    fx_rec.strategy = FX_GEMM_HEAD_BWD;
     *launched = true;
     return FX_OK;
 }
@@ -602,6 +659,9 @@ static int fx_batch_try_pair_fwd(const fx_gemm_problem* p, int32_t n, fx_stream_
     // launches; the longer problem first it is)
     fx_gemm_tile_launch_pair_fwd(swap ? a[1] : a[0], swap ? a[0] : a[1], fx_hip_stream(stream));
     FX_CHECK_LAUNCH();
+    for (int i = 0; i < 2; ++i) fx_rec_put(i, FX_GEMM_PAIR_FWD, 64, 64, 1, true);
+    fx_rec.strategy = FX_GEMM_PAIR_FWD;
+    fx_rec.swapped = swap ? 1 : 0;
     *launched = true;
     return FX_OK;
 }
@@ -611,20 +671,24 @@ extern "C" int fx_gemm_f32_batch(const fx_gemm_problem* p, int32_t n, fx_stream_
     typedef int (*fx_batch_try_fn)(const fx_gemm_problem*, int32_t, fx_stream_t, bool*);
     static const fx_batch_try_fn tries[] = {fx_batch_try_multi_x6, fx_batch_try_multi, fx_batch_try_pair_bwd,
                                             fx_batch_try_head_bwd, fx_batch_try_pair_fwd};
+    fx_rec_reset(n);
     for (fx_batch_try_fn try_fn : tries) {
         bool launched = false;
         const int rc = try_fn(p, n, stream, &launched);
         if (rc != FX_OK || launched) return rc;
     }
     // problem by problem, each with the slab rule of the kernels that will take it
+    fx_rec.strategy = FX_GEMM_SINGLES;
     for (int i = 0; i < n; ++i) {
         const fx_gemm_problem& q = p[i];
+        fx_rec_in_batch = true;
         const int rc = fx_gemm_f32(q.transa, q.transb, q.M, q.N, q.K, q.A, q.lda, q.B, q.ldb, q.C,
                                    q.ldc, q.epilogue,
                                    fx_gemm_skinny(q) ? q.split_k
                                    : fx_batch_wants_x6(q) ? fx_splitk_rule_x6(q.K, q.workspace ? q.split_k : 1)
                                                           : fx_splitk_rule64(q.M, q.N, q.K, q.split_k),
                                    q.workspace, stream);
+        fx_rec_in_batch = false;
         if (rc != FX_OK) return rc;
     }
     return FX_OK;

@@ -713,6 +713,35 @@ def _gemm(A, B_, C_, transa, transb, bias, act, zout, mul, mask, add, split_k, w
     return C_
 
 
+GEMM_STRATEGIES = ("NONE", "SKINNY", "X6", "PIPE", "PLAIN", "MULTI_X6", "MULTI_F32", "PAIR_BWD", "HEAD_BWD",
+                   "PAIR_FWD", "SINGLES")
+
+
+class GemmStrategy(object):
+    """What fx_gemm_last_strategy reports.  strategy: a name of GEMM_STRATEGIES; launches: one dict per
+    problem in the caller's order (arm, bm, bn, split_k, tr = 16-byte epilogue, av / bv = 16-byte operand
+    loads of the PLAIN arm); swapped: a forward pair ran its second problem first."""
+
+    def __init__(self, rec):
+        self.strategy = GEMM_STRATEGIES[rec.strategy]
+        self.n_problems = rec.n_problems
+        self.swapped = bool(rec.swapped)
+        self.launches = [dict(arm=GEMM_STRATEGIES[rec.arm[i]], bm=rec.tile_bm[i], bn=rec.tile_bn[i],
+                              split_k=rec.split_k[i], tr=bool(rec.tr[i]), av=bool(rec.plain_vec[i] & 1),
+                              bv=bool(rec.plain_vec[i] & 2)) for i in range(rec.n)]
+
+    def __repr__(self):
+        return "GemmStrategy(%s, %r%s)" % (self.strategy, self.launches, ", swapped" if self.swapped else "")
+
+
+def gemm_last_strategy():
+    """Which kernels the last gemm() / gemm_dw_dx() / gemm_batch() call of this thread launched
+    (fx_gemm_last_strategy).  For tests and diagnosis only: nothing may branch on it."""
+    rec = _lib.GemmStrategyRecord()
+    _lib.load().fx_gemm_last_strategy(C.byref(rec))
+    return GemmStrategy(rec)
+
+
 @_timed("colsum", "other")
 def colsum(X, out, workspace):
     M, N = X.shape

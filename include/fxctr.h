@@ -457,6 +457,42 @@ typedef struct fx_gemm_problem {
 } fx_gemm_problem;
 int fx_gemm_f32_batch(const fx_gemm_problem* problems_host, int32_t n, fx_stream_t stream);
 
+/* Which kernels the last fx_gemm_f32 / fx_gemm_f32_batch call of the CALLING THREAD launched (new
+ * functionality, nothing of the reference stands behind it: the tests of the dispatcher assert the arm
+ * they mean to test).  A host-side record, written on the way to the launch: no device work, no lock.
+ * Diagnostic only — no layer may branch on it.
+ *   strategy   what the call did: one of the arms of fx_gemm_f32 (SKINNY: the bandwidth-bound kernels, X6:
+ *              split bf16, PIPE: pipelined fp32 MFMA, PLAIN: the unpipelined fp32-MFMA kernel), one of the
+ *              one-grid strategies of fx_gemm_f32_batch, or SINGLES: the batch fell through to one
+ *              fx_gemm_f32 per problem.  NONE: nothing was launched (M == 0 or N == 0, an error, no call).
+ *   n          entries filled below: one per problem, in the caller's order (a batch of more than
+ *              FX_GEMM_RECORD_SLOTS problems keeps the last ones; a problem without output leaves none)
+ *   arm        per problem: the arm that took it (after SINGLES: the arm of each single launch, so
+ *              arm[n - 1] is the last launch), else the batch strategy
+ *   tile_bm/bn the output tile (0: the kernel has none), split_k: the K slabs actually run,
+ *   tr         1: the 16-byte epilogue, plain_vec (PLAIN only) bit 0 / 1: 16-byte loads of op(A) / op(B),
+ *   swapped    PAIR_FWD: the second problem's workgroups went first.
+ * Returns `strategy`; out may be NULL. */
+enum {
+    FX_GEMM_NONE = 0, FX_GEMM_SKINNY = 1, FX_GEMM_X6 = 2, FX_GEMM_PIPE = 3, FX_GEMM_PLAIN = 4,
+    FX_GEMM_MULTI_X6 = 5, FX_GEMM_MULTI_F32 = 6, FX_GEMM_PAIR_BWD = 7, FX_GEMM_HEAD_BWD = 8,
+    FX_GEMM_PAIR_FWD = 9, FX_GEMM_SINGLES = 10
+};
+#define FX_GEMM_RECORD_SLOTS 4
+typedef struct fx_gemm_strategy_record {
+    int32_t strategy;
+    int32_t n_problems; /* problems of the call (1 for fx_gemm_f32) */
+    int32_t n;
+    int32_t swapped;
+    int32_t arm[FX_GEMM_RECORD_SLOTS];
+    int32_t tile_bm[FX_GEMM_RECORD_SLOTS];
+    int32_t tile_bn[FX_GEMM_RECORD_SLOTS];
+    int32_t split_k[FX_GEMM_RECORD_SLOTS];
+    int32_t tr[FX_GEMM_RECORD_SLOTS];
+    int32_t plain_vec[FX_GEMM_RECORD_SLOTS];
+} fx_gemm_strategy_record;
+int fx_gemm_last_strategy(fx_gemm_strategy_record* out);
+
 /* Column sums (bias gradients): out[n] = sum_m X[m,n].
  * Two-stage deterministic reduction; workspace >= FX_COLSUM_CHUNKS * N floats. */
 #define FX_COLSUM_CHUNKS 64

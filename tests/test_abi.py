@@ -56,6 +56,21 @@ def test_struct_layout_matches_header():
     assert _lib.SC_WORDS * 4 == 64
 
 
+def test_gemm_strategy_record_without_gpu():
+    """fx_gemm_last_strategy: the record's layout, one name per enum value, and NONE after a call that was
+    refused before any launch."""
+    from fuxictr_amd import ops
+    assert ctypes.sizeof(_lib.GemmStrategyRecord) == 4 * (4 + 6 * 4)
+    text = open(os.path.join(ROOT, "include", "fxctr.h")).read()
+    enum = dict((n, int(v)) for n, v in re.findall(r"FX_GEMM_([A-Z0-9_]+) = (\d+)", text))
+    assert [enum[n] for n in ops.GEMM_STRATEGIES] == list(range(len(ops.GEMM_STRATEGIES))) and len(enum) == 11
+    lib = _lib.load()
+    assert lib.fx_gemm_f32(0, 0, 4, 4, 4, None, 4, None, 4, None, 4, None, 1, None, None) == 1
+    rec = ops.gemm_last_strategy()
+    assert rec.strategy == "NONE" and rec.launches == [] and rec.n_problems == 1
+    assert lib.fx_gemm_last_strategy(None) == 0
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

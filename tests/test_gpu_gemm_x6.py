@@ -161,10 +161,12 @@ for tag, (M, N, K) in {"first": (4096, 1024, 624), "cross": (4096, 624, 624), "t
     x, W, b, dz = rnd(M, K), rnd(N, K) * 0.1, rnd(N), rnd(M, N)
     y = torch.empty(M, N, device=dev)
     ops.gemm(x, W, y, transb=True, bias=b, act=1)
+    out[tag + "/strategy_y"] = np.array(ops.gemm_last_strategy().strategy)
     out[tag + "/y"] = y.cpu().numpy()
     dW, dx, rs = torch.empty(N, K, device=dev), torch.empty(M, K, device=dev), torch.empty(N, device=dev)
     ws = torch.empty(ops.gemm_workspace_floats(N, K, 8), device=dev)
     ops.gemm_dw_dx(dz, x, W, dW, dx, split_k=8, workspace=ws, rowsum=rs)
+    out[tag + "/strategy_dW"] = out[tag + "/strategy_dx"] = np.array(ops.gemm_last_strategy().strategy)
     out[tag + "/dW"], out[tag + "/dx"], out[tag + "/db"] = dW.cpu().numpy(), dx.cpu().numpy(), rs.cpu().numpy()
     out[tag + "/ref_y"] = torch.relu(x.double() @ W.double().t() + b.double()).cpu().numpy()
     out[tag + "/ref_dW"] = (dz.double().t() @ x.double()).cpu().numpy()
@@ -183,13 +185,22 @@ def test_x6_switch_selects_other_kernels_with_the_same_results(tmp_path):
                            timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         res[mode] = np.load(out)
+    # what ops.gemm_last_strategy() must say: with the switch off the gradient pairs of the 624-wide layers (320 and
+    # 260 workgroups of 128x128: under the fp32 grid's floor of 512) leave on the 64x64 pair kernel, the tower's
+    # (512) on k_gemm_f32_multi
+    fp32_pair = {"first": "PAIR_BWD", "cross": "PAIR_BWD", "tower": "MULTI_F32"}
     for tag in ("first", "cross", "tower"):
         for k in ("y", "dW", "dx"):
             a, b, ref = res["0"]["%s/%s" % (tag, k)], res["1"]["%s/%s" % (tag, k)], res["1"]["%s/ref_%s" % (tag, k)]
             assert not np.array_equal(a, b), (tag, k, "FX_GEMM_BF16X6 made no difference: which kernel ran?")
+            s0, s1 = (str(res[m]["%s/strategy_%s" % (tag, k)]) for m in ("0", "1"))
+            assert (s0, s1) == (("PIPE", "X6") if k == "y" else (fp32_pair[tag], "MULTI_X6")), (tag, k, s0, s1)
             e0 = np.linalg.norm(a - ref) / np.linalg.norm(ref)
             e1 = np.linalg.norm(b - ref) / np.linalg.norm(ref)
             print("[x6 a/b] %s/%s relative L2 error vs float64: fp32-MFMA %.3e  split-bf16 %.3e" % (tag, k, e0, e1))
+            # (e0 is no mere yardstick: the fp32-MFMA kernels are held to 2e-6 themselves — a broken one must not
+            # make the comparison easier to pass)
+            assert e0 <= 2e-6, (tag, k, e0)
             assert e1 <= 1.2e-6 and e1 <= 1.25 * e0 + 1e-8, (tag, k, e0, e1)
 
 
@@ -208,9 +219,11 @@ def run(tag, x, W, dz):
     # forward x W^T, and the weight-gradient / input-gradient pair of the same layer (K slabs + fused row sums)
     y = torch.empty(M, N, device=dev)
     ops.gemm(x.to(dev), W.to(dev), y, transb=True)
+    sy = ops.gemm_last_strategy().strategy
     dW, dx, rs = torch.empty(N, K, device=dev), torch.empty(M, K, device=dev), torch.empty(N, device=dev)
     ws = torch.empty(ops.gemm_workspace_floats(N, K, 4), device=dev)
     ops.gemm_dw_dx(dz.to(dev), x.to(dev), W.to(dev), dW, dx, split_k=4, workspace=ws, rowsum=rs)
+    out[tag + "/strategy"] = np.array(sy + "+" + ops.gemm_last_strategy().strategy)
     out[tag + "/y"], out[tag + "/dW"], out[tag + "/dx"] = y.cpu().numpy(), dW.cpu().numpy(), dx.cpu().numpy()
 x, W, dz = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05, torch.randn(M, N, generator=g)
 np.savez(sys.argv[1] + ".in", x=x.numpy(), W=W.numpy(), dz=dz.numpy())
@@ -248,6 +261,9 @@ def test_x6_operand_ranges_against_float64_and_the_fp32_kernels(tmp_path):
               "mixed": (1e18, 1e-18, 1e-10)}
     # float32 images of the scaled operands are what both kernels were given
     for tag, (sx, sw, sz) in scales.items():
+        # which kernels ran, said and not inferred: the forward product and the gradient pair (256 + 256 workgroups)
+        assert str(res["0"][tag + "/strategy"]) == "PIPE+MULTI_F32", (tag, res["0"][tag + "/strategy"])
+        assert str(res["1"][tag + "/strategy"]) == "X6+MULTI_X6", (tag, res["1"][tag + "/strategy"])
         xs = (base["x"] * np.float32(sx)).astype(np.float64)
         Ws = (base["W"] * np.float32(sw)).astype(np.float64)
         zs = (base["dz"] * np.float32(sz)).astype(np.float64)
@@ -257,6 +273,7 @@ def test_x6_operand_ranges_against_float64_and_the_fp32_kernels(tmp_path):
             e1 = np.linalg.norm(res["1"]["%s/%s" % (tag, k)] - ref) / np.linalg.norm(ref)
             print("[x6 range] %-11s %-2s relative L2 error vs float64: fp32-MFMA %.3e  split-bf16 %.3e" % (tag, k, e0, e1))
             assert np.isfinite(res["1"]["%s/%s" % (tag, k)]).all(), (tag, k)
+            assert e0 <= 2e-6, (tag, k, e0)        # the fp32-MFMA kernels' own bound, at every finite scale
             if tag == "tiny_1e-35":
                 # the third plane (2^-16 of 1e-35) lies below the smallest normal bf16 (1.2e-38): if the matrix
                 # core flushes it the product keeps 16 significand bits — a documented limit far outside any
