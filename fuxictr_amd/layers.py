@@ -3736,6 +3736,54 @@ class GateCrossLayer(nn.Module):
 GateCorssLayer = GateCrossLayer          # the reference's spelling (GDCN.py:175)
 
 
+class _AFMAttnFn(torch.autograd.Function):
+    """AFM's pairwise attention (AFM.py:84-93) as ONE autograd node over the [B, F, D] record:
+        out = sum_p softmax_p(w2 . relu(W1 e_p + b1)) (wp . e_p) (+ addend),  e_p = x_i * x_j, i < j.
+    Forward one launch (ops.afm_attn_fwd), backward one launch and the fixed-order reduce of the per-workgroup
+    weight gradients (ops.afm_attn_bwd).  Kept for the backward: the record (a view, no copy) and three floats per
+    sample; the pairs are recomputed.  addend: [B, 1] or None; its gradient is dout."""
+
+    @staticmethod
+    def forward(ctx, x, addend, W1, b1, w2, wp):
+        x = _field_view(x)
+        B, F, D = x.shape
+        rows = x.as_strided((B, F * D), (x.stride(0), 1))
+        out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
+        stats = torch.empty(B, 3, dtype=torch.float32, device=x.device)
+        if addend is not None:
+            addend = addend.contiguous()
+        ops.afm_attn_fwd(rows, F, D, W1, b1, w2.reshape(-1), wp.reshape(-1), addend, out, stats)
+        ctx.rows, ctx.stats, ctx.w, ctx.shape = rows, stats, (W1, b1, w2, wp), (B, F, D)
+        ctx.has_add = addend is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, stats, (W1, b1, w2, wp), (B, F, D) = ctx.rows, ctx.stats, ctx.w, ctx.shape
+        A = W1.shape[0]
+        dev = rows.device
+        g = g.contiguous()
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
+        grads = torch.empty(ops.afm_attn_grad_floats(D, A), dtype=torch.float32, device=dev)
+        ws = _Workspace.get(dev, ops.afm_attn_workspace_floats(B, F, D, A), tag="afm")
+        ops.afm_attn_bwd(g, rows, F, D, W1, b1, w2.reshape(-1), wp.reshape(-1), stats, dx.view(B, F * D), grads, ws)
+        AD = A * D
+        return (dx, (g if ctx.has_add else None), grads[:AD].view(A, D), grads[AD:AD + A],
+                grads[AD + A:AD + 2 * A].view_as(w2), grads[AD + 2 * A:].view_as(wp))
+
+
+def afm_attention(feature_emb, attention, weight_p, addend=None):
+    """The fused node behind zoo.AFM: `attention` is AFM's nn.Sequential (Linear(D, A), ReLU, Linear(A, 1, no bias),
+    Softmax(dim=1)), `weight_p` its Linear(D, 1, no bias); -> [B, 1].  afm_attention_native() says whether the shape
+    lies inside the kernel's envelope; outside it the caller composes the modules."""
+    return _AFMAttnFn.apply(feature_emb, addend, attention[0].weight, attention[0].bias, attention[2].weight,
+                            weight_p.weight)
+
+
+def afm_attention_native(num_fields, embedding_dim, attention_dim):
+    return ops.afm_attn_in_envelope(num_fields, embedding_dim, attention_dim)
+
+
 class _SideBySideFn(torch.autograd.Function):
     """`buf` [B, Da + Db] already holds a in its first Da columns and b in the rest (both were written in place):
     hand it on as the concatenation of the two, with the gradient's two column slices (row-strided views, read in

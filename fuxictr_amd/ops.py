@@ -1387,6 +1387,81 @@ def gate_cross_bwd(dxn, h, x0, b, dh, dx0, init, add_dxn):
     return dh, dx0
 
 
+# ---- AFM: pairwise attention over the gather record ---------------------------------------------------
+def afm_attn_limits():
+    """The native envelope of afm_attn_fwd / afm_attn_bwd, stated once: F >= F_min, F * D <= FD_max,
+    F (F - 1) / 2 <= P_max, D <= D_max, A <= A_max."""
+    lim = (C.c_int32 * 5)()
+    _lib.load().fx_afm_attn_limits(lim)
+    return dict(zip(("F_min", "FD_max", "P_max", "D_max", "A_max"), (int(v) for v in lim)))
+
+
+def afm_attn_in_envelope(F, D, A):
+    lim = afm_attn_limits()
+    return (F >= lim["F_min"] and F * D <= lim["FD_max"] and F * (F - 1) // 2 <= lim["P_max"]
+            and 1 <= D <= lim["D_max"] and 1 <= A <= lim["A_max"])
+
+
+def afm_attn_tile_rows(F=2, D=1, A=1):
+    """Samples one workgroup owns at a time (one wave each): 4, fewer for a shape whose backward image would not
+    fit the LDS with 4."""
+    return int(_lib.load().fx_afm_attn_tile_rows(F, D, A))
+
+
+def afm_attn_workspace_floats(B, F, D, A):
+    """Floats of afm_attn_bwd's workspace: the per-workgroup rows of weight gradient + the reduce's own."""
+    return int(_lib.load().fx_afm_attn_workspace_floats(B, F, D, A))
+
+
+def afm_attn_grad_floats(D, A):
+    """grads of afm_attn_bwd: [dW1 (A * D) | db1 (A) | dw2 (A) | dwp (D)]."""
+    return A * D + 2 * A + D
+
+
+def _afm_flops(rec, F, D, W1, *a, **kw):
+    return 2.0 * rec.shape[0] * (F * (F - 1) // 2) * D * W1.shape[0]       # the hidden product E W1^T
+
+
+def _afm_check(rec, F, D, W1, b1, w2, wp):
+    _need_cuda(rec, "rec")
+    A = W1.shape[0]
+    assert rec.dim() == 2 and rec.shape[1] == F * D and rec.stride(1) == 1 and rec.dtype == torch.float32
+    assert afm_attn_in_envelope(F, D, A), "afm_attn: F %d, D %d, A %d outside %s" % (F, D, A, afm_attn_limits())
+    assert tuple(W1.shape) == (A, D) and W1.is_contiguous()
+    assert b1.numel() == A and w2.numel() == A and wp.numel() == D
+    assert b1.is_contiguous() and w2.is_contiguous() and wp.is_contiguous()
+    return rec.shape[0], A
+
+
+@_timed("afm_attn_fwd", "afm", _afm_flops)
+def afm_attn_fwd(rec, F, D, W1, b1, w2, wp, addend, out, stats):
+    """out [B, 1] = sum_p softmax_p(w2 . relu(W1 e_p + b1)) (wp . e_p) (+ addend [B, 1]), e_p = x_i * x_j over the
+    pairs i < j of the sample's F fields; rec: [B, F * D] with unit column stride and any row stride.  stats [B, 3]:
+    the softmax's max and denominator and the result without the addend, for afm_attn_bwd."""
+    B, A = _afm_check(rec, F, D, W1, b1, w2, wp)
+    assert out.numel() == B and out.is_contiguous() and tuple(stats.shape) == (B, 3) and stats.is_contiguous()
+    assert addend is None or (addend.numel() == B and addend.is_contiguous())
+    check(_lib.load().fx_afm_attn_fwd(ptr(rec), _rows(rec), B, F, D, ptr(W1), ptr(b1), ptr(w2), ptr(wp), A,
+                                      ptr(addend), ptr(out), ptr(stats), stream_ptr(rec.device)), "fx_afm_attn_fwd")
+    return out, stats
+
+
+@_timed("afm_attn_bwd", "afm", lambda g, rec, F, D, W1, *a, **kw: 3.0 * _afm_flops(rec, F, D, W1))
+def afm_attn_bwd(g, rec, F, D, W1, b1, w2, wp, stats, drec, grads, workspace):
+    """From g = dout [B, 1] and the forward's stats: drec [B, F * D] (own row stride) and grads
+    [afm_attn_grad_floats(D, A)] = [dW1 | db1 | dw2 | dwp] summed over the batch (per-workgroup partial rows in
+    workspace, then the fixed-order column sums).  workspace: afm_attn_workspace_floats(B, F, D, A) floats."""
+    B, A = _afm_check(rec, F, D, W1, b1, w2, wp)
+    assert g.numel() == B and g.is_contiguous() and tuple(stats.shape) == (B, 3) and stats.is_contiguous()
+    assert tuple(drec.shape) == (B, F * D) and drec.stride(1) == 1
+    assert grads.numel() == afm_attn_grad_floats(D, A) and grads.is_contiguous()
+    assert workspace.numel() >= afm_attn_workspace_floats(B, F, D, A) and workspace.is_contiguous()
+    check(_lib.load().fx_afm_attn_bwd(ptr(g), ptr(rec), _rows(rec), B, F, D, ptr(W1), ptr(b1), ptr(w2), ptr(wp), A,
+                                      ptr(stats), ptr(drec), _rows(drec), ptr(grads), ptr(workspace),
+                                      stream_ptr(rec.device)), "fx_afm_attn_bwd")
+    return drec, grads
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

@@ -1,12 +1,12 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN and GDCNP, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP and AFM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
 model_zoo/FiBiNET/src/FiBiNET.py:45-104,
 model_zoo/MaskNet/src/MaskNet.py:51-123,
 model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101,
-model_zoo/GDCN/src/GDCN.py:24-172), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -19,7 +19,8 @@ from torch import nn
 from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
-                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout)
+                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout,
+                     _FMFn, afm_attention, afm_attention_native)
 from . import ops
 from .rank_model import BaseModel
 
@@ -571,3 +572,48 @@ class GDCNP(_ZooModel):
                 # net_dropout > 0 or another activation the tower's result is a tensor of its own and is joined here
                 both = torch.cat([cross, deep], dim=1)
         return {"y_pred": self.output_activation(self.fc(both))}
+
+
+class AFM(_ZooModel):
+    """Attentional Factorization Machine (AFM.py:24-96): the attention over the pairwise products of the fields."""
+
+    def __init__(self, feature_map, model_id="AFM", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 attention_dropout=[0, 0], attention_dim=10, use_attention=True, embedding_regularizer=None,
+                 net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.use_attention = use_attention
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.product_layer = InnerProductInteraction(feature_map.num_fields, output="elementwise_product")
+        self.lr_layer = LogisticRegression(feature_map, use_bias=True)
+        self.attention = nn.Sequential(nn.Linear(embedding_dim, attention_dim), nn.ReLU(),
+                                       nn.Linear(attention_dim, 1, bias=False), nn.Softmax(dim=1))
+        self.weight_p = nn.Linear(embedding_dim, 1, bias=False)
+        self.dropout1 = nn.Dropout(attention_dropout[0])
+        self.dropout2 = nn.Dropout(attention_dropout[1])
+        for lin in (self.attention[0], self.attention[2], self.weight_p):
+            lin.__dict__["_fx_head_off"] = True             # none of them ends in the model's logit
+        # fused=False: module by module, as the reference's class composes it (the [B, P, D] products, the hidden
+        # tensor, the softmax and the weighted sum as tensors): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_AFM_FUSED", "1") != "0"))
+        self._native = afm_attention_native(feature_map.num_fields, embedding_dim, attention_dim)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # [B, F, D]
+        drops = self.training and (self.dropout1.p > 0 or self.dropout2.p > 0)
+        if self._fused and not self.use_attention and emb.shape[1] > 1:
+            # the plain sum of all pair products is FM's second-order term; the linear part is its addend
+            return {"y_pred": self.output_activation(_FMFn.apply(emb, self.lr_layer(X)))}
+        if self._fused and self.use_attention and self._native and not drops:
+            # ... and the fused node's addend: no separate add launch
+            y_pred = afm_attention(emb, self.attention, self.weight_p, addend=self.lr_layer(X))
+            return {"y_pred": self.output_activation(y_pred)}
+        elementwise_product = self.product_layer(emb)       # [B, F (F - 1) / 2, D]
+        if self.use_attention:
+            attention_weight = self.dropout1(self.attention(elementwise_product))
+            attention_sum = self.dropout2(torch.sum(attention_weight * elementwise_product, dim=1))
+            afm_out = self.weight_p(attention_sum)
+        else:
+            afm_out = torch.flatten(elementwise_product, start_dim=1).sum(dim=-1).unsqueeze(-1)
+        return {"y_pred": self.output_activation(self.lr_layer(X) + afm_out)}

@@ -871,6 +871,34 @@ int fx_gate_cross_bwd(const float* dxn, int64_t lddxn, const float* h, int64_t l
                       int32_t init, int32_t add_dxn, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AFM (csrc/fx_afm.hip): the pairwise attention of AFM.forward (model_zoo/AFM/src/AFM.py:84-93) fused over
+ * the [B, F*D] gather record X (row stride ldx floats).  For the pairs p = (i, j), i < j, in the order of
+ * torch.triu_indices (inner_product.py:37-38, 67-69, "elementwise_product"):
+ *     e_p = x_i * x_j,  z_p = W1 e_p + b1 (AFM.py:62 attention.0),  h_p = relu(z_p) (AFM.py:63),
+ *     s_p = w2 . h_p (AFM.py:64),  a = softmax_p(s) (AFM.py:65),  t_p = wp . e_p (AFM.py:66, 90)
+ *   fx_afm_attn_fwd : out[b] = sum_p a_p t_p (+ addend[b]: lr_layer(X), AFM.py:93); stats[b] = {max_p s_p,
+ *                     sum_p exp(s_p - max), out[b] without the addend}.  The max is subtracted before every exp.
+ *   fx_afm_attn_bwd : with g = dout [B] and the forward's stats, the pairs recomputed from X:
+ *                     dX [B, F*D] (row stride lddx) and grads = [dW1 (A*D) | db1 (A) | dw2 (A) | dwp (D)] summed
+ *                     over the batch: per-workgroup rows in `workspace`, then fx_colsum.  The addend's gradient is g.
+ *   No per-pair value is written to memory.  No atomics: two runs give the same bits.  fp32.  16-byte accesses of
+ *   X and dX when D % 4 == 0 and base pointers and row strides are 16-byte aligned, 4-byte otherwise.
+ *   fx_afm_attn_limits : limits[5] = {least F, most F*D, most pairs, most D, most A}: the native envelope
+ *                     (housekeeping); a shape outside it is refused with FX_ERR_INVALID.
+ *   fx_afm_attn_tile_rows : samples one workgroup owns at a time, for tests of the tile boundaries (housekeeping).
+ *   fx_afm_attn_workspace_floats : floats of fx_afm_attn_bwd's workspace (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+void fx_afm_attn_limits(int32_t* limits);
+int32_t fx_afm_attn_tile_rows(int32_t F, int32_t D, int32_t A);
+int64_t fx_afm_attn_workspace_floats(int64_t B, int32_t F, int32_t D, int32_t A);
+int fx_afm_attn_fwd(const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, const float* W1, const float* b1,
+                    const float* w2, const float* wp, int32_t A, const float* addend, float* out, float* stats,
+                    fx_stream_t stream);
+int fx_afm_attn_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, const float* W1,
+                    const float* b1, const float* w2, const float* wp, int32_t A, const float* stats, float* dX,
+                    int64_t lddx, float* grads, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
