@@ -162,6 +162,10 @@ SIGNATURES = {
     "fx_gate_cross_tile_rows": (i32, []),
     "fx_gate_cross_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, i32, vp]),
     "fx_gate_cross_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i32, i32, i32, vp]),
+    "fx_cross_net_limits": (None, [vp]),
+    "fx_cross_net_workspace_floats": (i64, [i64, i32, i32]),
+    "fx_cross_net_fwd": (i32, [vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, vp]),
+    "fx_cross_net_bwd": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]),
     "fx_afm_attn_limits": (None, [vp]),
     "fx_afm_attn_tile_rows": (i32, [i32, i32, i32]),
     "fx_afm_attn_workspace_floats": (i64, [i64, i32, i32, i32]),

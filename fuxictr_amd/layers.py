@@ -3736,6 +3736,111 @@ class GateCrossLayer(nn.Module):
 GateCorssLayer = GateCrossLayer          # the reference's spelling (GDCN.py:175)
 
 
+class _CrossNetFn(torch.autograd.Function):
+    """DCN's whole rank-1 cross stack (cross_net.py:54, 89-92) as ONE autograd node:
+        x_{l+1} = x_l + ((w_l . x_l) * x_0 + b_l).
+    Forward one launch (ops.cross_net_fwd), backward two (ops.cross_net_bwd: the row pass and the fixed-order sum of
+    its column partials).  Kept for the backward: x_0 (a view) and the [B, L] dots s; no x_l is stored.
+    out_into: an optional [B, D] view (unit column stride) that x_L is written into and that is returned.
+    args = (x0, out_into, stash, w, b, weight_0, bias_0, weight_1, ...): w and b the packed [L, D] storages that the
+    Parameters are views of; stash False: no backward will follow (eval), s is not written."""
+
+    @staticmethod
+    def forward(ctx, x0, out_into, stash, w, b, *params):
+        if x0.stride(-1) != 1:
+            x0 = x0.contiguous()
+        B, D = x0.shape
+        out = out_into if out_into is not None else torch.empty(B, D, dtype=torch.float32, device=x0.device)
+        s = torch.empty(B, w.shape[0], dtype=torch.float32, device=x0.device) if stash else None
+        ops.cross_net_fwd(x0, w, b, out, s)
+        ctx.kept = (x0, w, b, s)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x0, w, b, s = ctx.kept
+        B, D = x0.shape
+        L = w.shape[0]
+        if dout.stride(-1) != 1:
+            dout = dout.contiguous()               # (a row-strided slice of the head's gradient is read in place)
+        dx0 = torch.empty(B, D, dtype=torch.float32, device=x0.device)
+        dw, db = torch.empty_like(w), torch.empty_like(b)
+        ws = _Workspace.get(x0.device, ops.cross_net_workspace_floats(B, D, L), tag="crossnet")
+        ops.cross_net_bwd(dout, x0, w, b, s, dx0, dw, db, True, ws)
+        grads = []
+        for i in range(L):
+            grads += [dw[i:i + 1], db[i]]
+        return (dx0, None, None, None, None) + tuple(grads)
+
+
+class CrossInteraction(nn.Module):
+    """cross_net.py:24-55: `weight` a Linear to one output without a bias, `bias` [input_dim] zeros."""
+
+    def __init__(self, input_dim):
+        super(CrossInteraction, self).__init__()
+        dev = _alloc_device()
+        self.weight = FxLinear(input_dim, 1, bias=False, device=dev)
+        self.weight.__dict__["_fx_head_off"] = True      # a [B, 1] product that is not the model's logit
+        self.bias = nn.Parameter(torch.zeros(input_dim, device=dev))
+
+    def forward(self, X_0, X_i):
+        return self.weight(X_i) * X_0 + self.bias
+
+
+class CrossNet(nn.Module):
+    """cross_net.py:58-92: same constructor, attributes and keys (`cross_net.<i>.weight.weight` [1, D],
+    `cross_net.<i>.bias` [D]).  The L weights and the L biases are views of ONE packed [L, D] storage each, as
+    GateCrossLayer's pairs are of theirs: the kernels read all layers from two pointers, and state_dict /
+    load_state_dict / the dense optimizer see ordinary Parameters.  fused=False, or a shape outside
+    ops.cross_net_limits(): module by module as the reference composes it (a Linear to one output, torch
+    element-wise): the same numbers."""
+
+    def __init__(self, input_dim, num_layers):
+        super(CrossNet, self).__init__()
+        self.num_layers = num_layers
+        self.cross_net = nn.ModuleList(CrossInteraction(input_dim) for _ in range(self.num_layers))
+        self.fused = True
+        dev = _alloc_device()
+        self._w = torch.empty(num_layers, input_dim, device=dev)
+        self._b = torch.empty(num_layers, input_dim, device=dev)
+        for i, layer in enumerate(self.cross_net):
+            self._w[i:i + 1].copy_(layer.weight.weight.data)
+            self._b[i].copy_(layer.bias.data)
+        self._bind_views()
+
+    def _bind_views(self):
+        for i, layer in enumerate(self.cross_net):
+            layer.weight.weight.data = self._w[i:i + 1]
+            layer.bias.data = self._b[i]
+
+    def _apply(self, fn, recurse=True):
+        # nn.Module.to() / cuda(): the packed storages move once and the 2 L Parameters are re-pointed at them
+        super(CrossNet, self)._apply(fn, recurse)
+        self._w, self._b = fn(self._w), fn(self._b)
+        self._bind_views()
+        return self
+
+    def native(self, X_0):
+        """Whether forward(X_0) runs the fused node (and so honours out_into)."""
+        if not self.fused or X_0.dim() != 2 or self.num_layers < 1:
+            return False
+        lim = ops.cross_net_limits()
+        return X_0.shape[1] <= lim["max_cols"] and self.num_layers <= lim["max_layers"]
+
+    def forward(self, X_0, out_into=None):
+        """out_into (native extension): see _CrossNetFn; ignored on the module-by-module route."""
+        if not self.native(X_0):
+            X_i = X_0
+            for i in range(self.num_layers):
+                X_i = X_i + self.cross_net[i](X_0, X_i)
+            return X_i
+        params = []
+        for layer in self.cross_net:
+            params += [layer.weight.weight, layer.bias]
+        stash = torch.is_grad_enabled() and (X_0.requires_grad or any(p.requires_grad for p in params))
+        return _CrossNetFn.apply(X_0, out_into, stash, self._w, self._b, *params)
+
+
 class _AFMAttnFn(torch.autograd.Function):
     """AFM's pairwise attention (AFM.py:84-93) as ONE autograd node over the [B, F, D] record:
         out = sum_p softmax_p(w2 . relu(W1 e_p + b1)) (wp . e_p) (+ addend),  e_p = x_i * x_j, i < j.

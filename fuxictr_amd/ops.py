@@ -1387,6 +1387,63 @@ def gate_cross_bwd(dxn, h, x0, b, dh, dx0, init, add_dxn):
     return dh, dx0
 
 
+# ---- DCN: the rank-1 cross network, the whole stack per call ---------------------------------------------
+def cross_net_limits():
+    """The native envelope of cross_net_fwd / cross_net_bwd and their geometry, stated once: cols <= max_cols,
+    1 <= L <= max_layers; a workgroup owns tile_rows rows at a time and at most max_wg workgroups stride over the
+    row tiles."""
+    lim = (C.c_int32 * 4)()
+    _lib.load().fx_cross_net_limits(lim)
+    return dict(zip(("max_cols", "max_layers", "tile_rows", "max_wg"), (int(v) for v in lim)))
+
+
+def cross_net_workspace_floats(rows, cols, L):
+    return int(_lib.load().fx_cross_net_workspace_floats(rows, cols, L))
+
+
+def _cross_net_wb(w, b, cols):
+    L = w.shape[0]
+    assert w.dim() == 2 and tuple(w.shape) == (L, cols) and tuple(b.shape) == (L, cols), \
+        "w / b must be [L, %d], got %s / %s" % (cols, tuple(w.shape), tuple(b.shape))
+    assert w.is_contiguous() and b.is_contiguous()
+    return L
+
+
+@_timed("cross_net_fwd", "crossnet", lambda x0, *a, **kw: 4.0 * x0.shape[0] * x0.shape[1] * 2.0)     # x0; out
+def cross_net_fwd(x0, w, b, out, s=None):
+    """out = x_L of x_{l+1} = x_l + ((w_l . x_l) * x_0 + b_l), l < L, in one launch.  x0, out: [rows, cols], unit
+    column stride and any row stride each (out may be the left column range of a wider buffer); w, b: [L, cols]
+    contiguous; s: [rows, L] contiguous, receives w_l . x_l for the backward (None: not wanted)."""
+    _need_cuda(x0, "x0")
+    rows, cols = x0.shape
+    L = _cross_net_wb(w, b, cols)
+    assert tuple(out.shape) == (rows, cols)
+    assert s is None or (tuple(s.shape) == (rows, L) and s.is_contiguous())
+    check(_lib.load().fx_cross_net_fwd(ptr(x0), _rows(x0), ptr(w), ptr(b), ptr(out), _rows(out), ptr(s), rows, cols,
+                                       L, stream_ptr(x0.device)), "fx_cross_net_fwd")
+    return out
+
+
+@_timed("cross_net_bwd", "crossnet",
+        lambda dout, x0, w, b, s, dx0, dw, db, init, workspace:                 # dout, x0; dx0 (read when added to)
+        4.0 * x0.shape[0] * x0.shape[1] * (3.0 if init else 4.0))
+def cross_net_bwd(dout, x0, w, b, s, dx0, dw, db, init, workspace):
+    """From dout = dL/dx_L and the forward's s: dx0 (= when init, += otherwise), dw and db [L, cols], in two launches;
+    x_l is recomputed from x0, s and b.  dout is read in place through its row stride (a column slice of a wider
+    gradient).  workspace: cross_net_workspace_floats(rows, cols, L) floats."""
+    _need_cuda(x0, "x0")
+    rows, cols = x0.shape
+    L = _cross_net_wb(w, b, cols)
+    assert tuple(dout.shape) == (rows, cols) and tuple(dx0.shape) == (rows, cols)
+    assert tuple(s.shape) == (rows, L) and s.is_contiguous()
+    assert tuple(dw.shape) == (L, cols) and tuple(db.shape) == (L, cols) and dw.is_contiguous() and db.is_contiguous()
+    assert workspace.is_contiguous() and workspace.numel() >= cross_net_workspace_floats(rows, cols, L)
+    check(_lib.load().fx_cross_net_bwd(ptr(dout), _rows(dout), ptr(x0), _rows(x0), ptr(w), ptr(b), ptr(s), ptr(dx0),
+                                       _rows(dx0), ptr(dw), ptr(db), ptr(workspace), rows, cols, L,
+                                       1 if init else 0, stream_ptr(x0.device)), "fx_cross_net_bwd")
+    return dx0, dw, db
+
+
 # ---- AFM: pairwise attention over the gather record ---------------------------------------------------
 def afm_attn_limits():
     """The native envelope of afm_attn_fwd / afm_attn_bwd, stated once: F >= F_min, F * D <= FD_max,

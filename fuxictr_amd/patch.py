@@ -15,7 +15,7 @@ import importlib
 import sys
 
 LAYER_NAMES = ["FeatureEmbedding", "FeatureEmbeddingDict", "LogisticRegression",
-               "FactorizationMachine", "InnerProductInteraction", "MLP_Block", "CrossNetV2",
+               "FactorizationMachine", "InnerProductInteraction", "MLP_Block", "CrossNet", "CrossNetV2",
                "MaskedAveragePooling", "MaskedSumPooling", "DIN_Attention", "Dice", "CompressedInteractionNet",
                "SqueezeExcitation", "BilinearInteraction", "BilinearInteractionV2"]
 

@@ -1,12 +1,13 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP and AFM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM and DCN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
 model_zoo/FiBiNET/src/FiBiNET.py:45-104,
 model_zoo/MaskNet/src/MaskNet.py:51-123,
 model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101,
-model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96,
+model_zoo/DCN/DCN_torch/src/DCN.py:24-101), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (tests/test_dropin_reference_zoo.py).
@@ -16,7 +17,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout,
@@ -617,3 +618,47 @@ class AFM(_ZooModel):
         else:
             afm_out = torch.flatten(elementwise_product, start_dim=1).sum(dim=-1).unsqueeze(-1)
         return {"y_pred": self.output_activation(self.lr_layer(X) + afm_out)}
+
+
+class DCN(_ZooModel):
+    """Deep & Cross Network (DCN.py:24-101): the rank-1 cross network next to the deep tower, `fc` over both; with
+    `dnn_hidden_units` empty the cross network alone (`dnn` is None, DCN.py:64-76)."""
+
+    def __init__(self, feature_map, model_id="DCN", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[], dnn_activations="ReLU", num_cross_layers=3, net_dropout=0, batch_norm=False,
+                 embedding_regularizer=None, net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        width = feature_map.sum_emb_out_dim()
+        units = list(dnn_hidden_units) if dnn_hidden_units else []
+        self.dnn = self._tower(width, units, dnn_activations, net_dropout, batch_norm, output_dim=None) \
+            if units else None
+        self.crossnet = CrossNet(width, num_cross_layers)
+        self.fc = FxLinear(width + (units[-1] if units else 0), 1, device=self.device)
+        # fused=False: module by module, as the reference's class composes it (per layer a Linear to one output, the
+        # product, the two sums as tensors): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_DCN_FUSED", "1") != "0"))
+        self.crossnet.fused = self._fused
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        flat = self.embedding_layer(X, flatten_emb=True)    # [B, F*D]
+        if self.dnn is None:
+            both = self.crossnet(flat)
+        elif not self.crossnet.native(flat):
+            both = torch.cat([self.crossnet(flat), self.dnn(flat)], dim=-1)
+        else:
+            # the cross stack and the tower's last layer write side by side into one [B, D0 + H] buffer, as in GDCNP
+            D0, H = flat.shape[1], self.fc.in_features - flat.shape[1]
+            buf = torch.empty(flat.shape[0], D0 + H, dtype=torch.float32, device=flat.device)
+            left, right = buf.data[:, :D0], buf.data[:, D0:]
+            cross = self.crossnet(flat, out_into=left)
+            deep = self.dnn(flat, out_into=right)
+            if deep.data_ptr() == right.data_ptr() and deep.stride() == right.stride():
+                both = _SideBySideFn.apply(buf, cross, deep)
+            else:
+                # MLP_Block takes out_into only when the whole tower is its fused Linear / ReLU node (no batch_norm,
+                # no dropout, ReLU): otherwise its result is a tensor of its own and is joined here
+                both = torch.cat([cross, deep], dim=-1)
+        return {"y_pred": self.output_activation(self.fc(both))}

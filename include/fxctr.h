@@ -871,6 +871,36 @@ int fx_gate_cross_bwd(const float* dxn, int64_t lddxn, const float* h, int64_t l
                       int32_t init, int32_t add_dxn, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DCN (csrc/fx_crossnet.hip): the rank-1 cross network, CrossNet.forward over its CrossInteraction layers
+ * (fuxictr/pytorch/layers/interactions/cross_net.py:54, 89-92), all L layers per call:
+ *     x_{l+1} = x_l + ((s_l * x_0) + b_l),   s_l = w_l . x_l
+ * w, b: [L, cols] packed (layer l's `weight.weight` [1, cols] and `bias` [cols]).  fp32; x0, out, dout and dx0 have
+ * their own row stride in floats (out may be the left column range of a wider buffer, dout a column slice of a wider
+ * gradient: nothing outside [0, cols) of a row is written); 16-byte accesses when cols is a multiple of 4 and every
+ * base pointer and row stride is 16-byte aligned, scalar otherwise.  No atomics, fixed-order sums: two runs give the
+ * same bits.
+ *   fx_cross_net_fwd : out = x_L in ONE launch: x_0 and x_l of a row live in registers, no [rows, cols]
+ *                      intermediate is written.  s: [rows, L] packed, receives s_l (null: not wanted).
+ *   fx_cross_net_bwd : from dout = dL/dx_L and the forward's s, with g_L = dout and for l = L-1 .. 0:
+ *                      t_l = g_{l+1} . x_0,  g_l = g_{l+1} + t_l w_l:
+ *                        dx0 (= when init, += otherwise) sum_l s_l g_{l+1} + g_0,
+ *                        dw[l] = sum_rows t_l x_l,   db[l] = sum_rows g_{l+1},
+ *                      x_l recomputed as (1 + sum_{k<l} s_k) x_0 + sum_{k<l} b_k.  TWO launches: the row pass
+ *                      (dx0 and one row of column sums per workgroup in `workspace`) and their fixed-order sum.
+ *   fx_cross_net_limits : limits[4] = {most cols, most L, rows of a workgroup's tile, most workgroups of the row
+ *                      passes}: the native envelope (housekeeping); a shape outside it is refused with
+ *                      FX_ERR_INVALID.
+ *   fx_cross_net_workspace_floats : floats of fx_cross_net_bwd's workspace, 16-byte aligned (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+void fx_cross_net_limits(int32_t* limits);
+int64_t fx_cross_net_workspace_floats(int64_t rows, int32_t cols, int32_t L);
+int fx_cross_net_fwd(const float* x0, int64_t ldx0, const float* w, const float* b, float* out, int64_t ldout,
+                     float* s, int64_t rows, int32_t cols, int32_t L, fx_stream_t stream);
+int fx_cross_net_bwd(const float* dout, int64_t lddout, const float* x0, int64_t ldx0, const float* w, const float* b,
+                     const float* s, float* dx0, int64_t lddx0, float* dw, float* db, float* workspace, int64_t rows,
+                     int32_t cols, int32_t L, int32_t init, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * AFM (csrc/fx_afm.hip): the pairwise attention of AFM.forward (model_zoo/AFM/src/AFM.py:84-93) fused over
  * the [B, F*D] gather record X (row stride ldx floats).  For the pairs p = (i, j), i < j, in the order of
  * torch.triu_indices (inner_product.py:37-38, 67-69, "elementwise_product"):
