@@ -171,6 +171,11 @@ SIGNATURES = {
     "fx_afm_attn_workspace_floats": (i64, [i64, i32, i32, i32]),
     "fx_afm_attn_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "fx_afm_attn_bwd": (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp]),
+    "fx_pairfm_limits": (None, [vp]),
+    "fx_pairfm_tile_rows": (i32, [i32, i32, i32]),
+    "fx_pairfm_workspace_floats": (i64, [i32, i64, i32, i32]),
+    "fx_pairfm_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "fx_pairfm_bwd": (i32, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, vp, i64, vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

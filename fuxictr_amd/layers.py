@@ -3889,6 +3889,61 @@ def afm_attention_native(num_fields, embedding_dim, attention_dim):
     return ops.afm_attn_in_envelope(num_fields, embedding_dim, attention_dim)
 
 
+class _PairFMFn(torch.autograd.Function):
+    """The field-pair interaction of FwFM (FwFM.py:78-88) and FmFM (FmFM.py:84-91) as ONE autograd node over the
+    [B, F, D] record:  out = sum_p u_p(x_i) . x_j (+ wlin . x) (+ bias) (+ addend),  pairs i < j in triu order,
+    u_p = r_p x ("scalar"), w_p * x ("vector") or x^T M_p ("matrix").  Forward one launch (ops.pairfm_fwd), backward
+    one ops.pairfm_bwd (the record's gradient, the weight gradients over slabs of samples, their fixed-order sum).
+    Kept for the backward: the record (a view, no copy) and the parameters; nothing per pair exists.
+    addend: [B, 1] or None; its gradient is dout."""
+
+    @staticmethod
+    def forward(ctx, x, weight, mode, wlin, bias, addend):
+        x = _field_view(x)
+        B, F, D = x.shape
+        rows = x.as_strided((B, F * D), (x.stride(0), 1))
+        out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
+        if addend is not None:
+            addend = addend.contiguous()
+        w = weight.contiguous()
+        wl = wlin.contiguous().view(-1) if wlin is not None else None
+        ops.pairfm_fwd(rows, F, D, mode, w, wl, bias, addend, out)
+        ctx.rows, ctx.w, ctx.wl, ctx.mode, ctx.shape = rows, w, wl, mode, (B, F, D)
+        ctx.wshape = weight.shape
+        ctx.lshape = wlin.shape if wlin is not None else None
+        ctx.has = (bias is not None, addend is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, w, wl, mode, (B, F, D) = ctx.rows, ctx.w, ctx.wl, ctx.mode, ctx.shape
+        has_bias, has_add = ctx.has
+        dev = rows.device
+        g = g.contiguous()
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
+        grads = torch.empty(ops.pairfm_grad_floats(mode, F, D, wl is not None, has_bias), dtype=torch.float32,
+                            device=dev)
+        ws = _Workspace.get(dev, ops.pairfm_workspace_floats(mode, B, F, D), tag="pairfm")
+        ops.pairfm_bwd(g, rows, F, D, mode, w, wl, has_bias, dx.view(B, F * D), grads, ws)
+        nW = w.numel()
+        nL = F * D if wl is not None else 0
+        return (dx, grads[:nW].view(ctx.wshape), None,
+                grads[nW:nW + nL].view(ctx.lshape) if wl is not None else None,
+                grads[nW + nL:nW + nL + 1] if has_bias else None, (g if has_add else None))
+
+
+def pair_interaction(feature_emb, weight, mode, wlin=None, bias=None, addend=None):
+    """The fused node behind zoo.FwFM / zoo.FmFM -> [B, 1].  weight: [P] or [1, P] ("scalar": FwFM's
+    interaction_weight.weight), [P, D] ("vector") or [P, D, D] ("matrix": FmFM's interaction_weight); wlin: FwFM's
+    "FiLV" Linear(F * D, 1).weight; bias: one float; addend: [B, 1].  pair_interaction_native() says whether the shape
+    lies inside the kernel's envelope; outside it the caller composes the modules."""
+    return _PairFMFn.apply(feature_emb, weight, mode, wlin, bias, addend)
+
+
+def pair_interaction_native(F, D, mode):
+    return mode in ops.PAIRFM_MODES and ops.pairfm_in_envelope(F, D)
+
+
 class _SideBySideFn(torch.autograd.Function):
     """`buf` [B, Da + Db] already holds a in its first Da columns and b in the rest (both were written in place):
     hand it on as the concatenation of the two, with the gradient's two column slices (row-strided views, read in

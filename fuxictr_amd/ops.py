@@ -1519,6 +1519,87 @@ def afm_attn_bwd(g, rec, F, D, W1, b1, w2, wp, stats, drec, grads, workspace):
     return drec, grads
 
 
+# ---- FwFM / FmFM: the field-pair interaction with a parameter per pair ---------------------------------
+PAIRFM_MODES = {"scalar": 0, "vector": 1, "matrix": 2}
+
+
+def pairfm_limits():
+    """The native envelope of pairfm_fwd / pairfm_bwd, stated once: F >= F_min, F * D <= FD_max, D <= D_max."""
+    lim = (C.c_int32 * 3)()
+    _lib.load().fx_pairfm_limits(lim)
+    return dict(zip(("F_min", "FD_max", "D_max"), (int(v) for v in lim)))
+
+
+def pairfm_in_envelope(F, D):
+    lim = pairfm_limits()
+    return F >= lim["F_min"] and F * D <= lim["FD_max"] and 1 <= D <= lim["D_max"]
+
+
+def pairfm_tile_rows(mode="matrix", F=2, D=1):
+    """Samples one workgroup owns at a time: 16, 8 for a record too wide for 16 of them in the LDS."""
+    return int(_lib.load().fx_pairfm_tile_rows(PAIRFM_MODES[mode], F, D))
+
+
+def pairfm_workspace_floats(mode, B, F, D):
+    """Floats of pairfm_bwd's workspace: one row of weight gradient per slab of samples + the reduce's own (a
+    single slab writes straight into grads)."""
+    return int(_lib.load().fx_pairfm_workspace_floats(PAIRFM_MODES[mode], B, F, D))
+
+
+def pairfm_weight_floats(mode, F, D):
+    P = F * (F - 1) // 2
+    return P * (D * D if mode == "matrix" else D if mode == "vector" else 1)
+
+
+def pairfm_grad_floats(mode, F, D, wlin=False, bias=False):
+    """grads of pairfm_bwd: [dW | dwlin (F * D, with wlin) | dbias (1, with bias)]."""
+    return pairfm_weight_floats(mode, F, D) + (F * D if wlin else 0) + (1 if bias else 0)
+
+
+def _pairfm_flops(rec, F, D, mode, *a, **kw):
+    return 2.0 * rec.shape[0] * pairfm_weight_floats(mode, F, D) + 2.0 * rec.shape[0] * (F * (F - 1) // 2) * D
+
+
+def _pairfm_check(rec, F, D, mode, W, wlin):
+    _need_cuda(rec, "rec")
+    assert mode in PAIRFM_MODES, mode
+    assert rec.dim() == 2 and rec.shape[1] == F * D and rec.stride(1) == 1 and rec.dtype == torch.float32
+    assert W.numel() == pairfm_weight_floats(mode, F, D) and W.is_contiguous() and W.dtype == torch.float32
+    assert wlin is None or (wlin.numel() == F * D and wlin.is_contiguous())
+    return rec.shape[0]
+
+
+@_timed("pairfm_fwd", "pairfm", _pairfm_flops)
+def pairfm_fwd(rec, F, D, mode, W, wlin, bias, addend, out):
+    """out [B, 1] = sum_p u_p(x_i) . x_j (+ wlin . x) (+ bias) (+ addend [B, 1]) over the pairs i < j of the sample's
+    F fields, u_p(x) = r_p x ("scalar", W [P]), w_p * x ("vector", W [P, D]) or x^T M_p ("matrix", W [P, D, D]);
+    rec: [B, F * D] with unit column stride and any row stride.  A shape outside pairfm_limits() is the library's
+    invalid-argument error."""
+    B = _pairfm_check(rec, F, D, mode, W, wlin)
+    assert out.numel() == B and out.is_contiguous()
+    assert bias is None or bias.numel() == 1
+    assert addend is None or (addend.numel() == B and addend.is_contiguous())
+    check(_lib.load().fx_pairfm_fwd(ptr(rec), _rows(rec), B, F, D, PAIRFM_MODES[mode], ptr(W), ptr(wlin), ptr(bias),
+                                    ptr(addend), ptr(out), stream_ptr(rec.device)), "fx_pairfm_fwd")
+    return out
+
+
+@_timed("pairfm_bwd", "pairfm", lambda g, rec, F, D, mode, *a, **kw: 3.0 * _pairfm_flops(rec, F, D, mode))
+def pairfm_bwd(g, rec, F, D, mode, W, wlin, has_bias, drec, grads, workspace):
+    """From g = dout [B, 1]: drec [B, F * D] (own row stride) and grads [pairfm_grad_floats(..)] = [dW | dwlin |
+    dbias] summed over the batch in a fixed order (per-slab rows in workspace, then the column sums).  workspace:
+    pairfm_workspace_floats(mode, B, F, D) floats."""
+    B = _pairfm_check(rec, F, D, mode, W, wlin)
+    assert g.numel() == B and g.is_contiguous()
+    assert tuple(drec.shape) == (B, F * D) and drec.stride(1) == 1
+    assert grads.numel() == pairfm_grad_floats(mode, F, D, wlin is not None, has_bias) and grads.is_contiguous()
+    assert workspace.numel() >= pairfm_workspace_floats(mode, B, F, D) and workspace.is_contiguous()
+    check(_lib.load().fx_pairfm_bwd(ptr(g), ptr(rec), _rows(rec), B, F, D, PAIRFM_MODES[mode], ptr(W), ptr(wlin),
+                                    1 if has_bias else 0, ptr(drec), _rows(drec), ptr(grads), ptr(workspace),
+                                    stream_ptr(rec.device)), "fx_pairfm_bwd")
+    return drec, grads
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

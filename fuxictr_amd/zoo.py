@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM and DCN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM and FmFM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -7,7 +7,8 @@ model_zoo/FiBiNET/src/FiBiNET.py:45-104,
 model_zoo/MaskNet/src/MaskNet.py:51-123,
 model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101,
 model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96,
-model_zoo/DCN/DCN_torch/src/DCN.py:24-101), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/DCN/DCN_torch/src/DCN.py:24-101, model_zoo/FwFM/src/FwFM.py:24-91,
+model_zoo/FmFM/src/FmFM.py:25-94), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -21,7 +22,7 @@ from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNet, 
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout,
-                     _FMFn, afm_attention, afm_attention_native)
+                     _FMFn, afm_attention, afm_attention_native, pair_interaction, pair_interaction_native)
 from . import ops
 from .rank_model import BaseModel
 
@@ -662,3 +663,102 @@ class DCN(_ZooModel):
                 # no dropout, ReLU): otherwise its result is a tensor of its own and is joined here
                 both = torch.cat([cross, deep], dim=-1)
         return {"y_pred": self.output_activation(self.fc(both))}
+
+
+class FwFM(_ZooModel):
+    """Field-weighted Factorization Machine (FwFM.py:24-91): a trained scalar per field pair over the inner products,
+    plus one of three linear parts."""
+
+    def __init__(self, feature_map, model_id="FwFM", gpu=-1, learning_rate=1e-3, embedding_dim=10, regularizer=None,
+                 linear_type="FiLV", **kwargs):
+        self._base(feature_map, model_id, gpu, regularizer, regularizer, kwargs)      # one keyword feeds both
+        interact_dim = int(feature_map.num_fields * (feature_map.num_fields - 1) / 2)
+        self.interaction_weight = nn.Linear(interact_dim, 1)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.inner_product_layer = InnerProductInteraction(feature_map.num_fields, output="inner_product")
+        self._linear_type = linear_type
+        if linear_type == "LW":
+            self.linear_weight_layer = FeatureEmbedding(feature_map, 1, use_pretrain=False)
+        elif linear_type == "FeLV":
+            self.linear_weight_layer = FeatureEmbedding(feature_map, embedding_dim)
+        elif linear_type == "FiLV":
+            self.linear_weight_layer = nn.Linear(feature_map.num_fields * embedding_dim, 1, bias=False)
+            self.linear_weight_layer.__dict__["_fx_head_off"] = True
+        else:
+            raise NotImplementedError("linear_type={} is not supported.".format(linear_type))
+        self.interaction_weight.__dict__["_fx_head_off"] = True
+        # fused=False: module by module, as the reference's class composes it (the [B, P] inner products, the
+        # Linear over them, the linear part and the sum as tensors): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_PAIRFM_FUSED", "1") != "0"))
+        self._native = pair_interaction_native(feature_map.num_fields, embedding_dim, "scalar")
+        self._ready(kwargs, learning_rate)
+
+    def _linear_part(self, X, feature_emb):
+        if self._linear_type == "LW":
+            return self.linear_weight_layer(X).sum(dim=1)
+        if self._linear_type == "FeLV":
+            return (feature_emb * self.linear_weight_layer(X)).sum((1, 2)).view(-1, 1)
+        return self.linear_weight_layer(feature_emb.flatten(start_dim=1))
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        if self._fused and self._native:
+            lin, bias = self.interaction_weight, self.interaction_weight.bias
+            if self._linear_type == "FiLV":                 # pairs, linear part and bias: one launch
+                y_pred = pair_interaction(feature_emb, lin.weight, "scalar", wlin=self.linear_weight_layer.weight,
+                                          bias=bias)
+            else:                                           # the second table's linear part rides as the addend
+                y_pred = pair_interaction(feature_emb, lin.weight, "scalar", bias=bias,
+                                          addend=self._linear_part(X, feature_emb))
+            return {"y_pred": self.output_activation(y_pred)}
+        poly2_part = self.interaction_weight(self.inner_product_layer(feature_emb))
+        y_pred = poly2_part + self._linear_part(X, feature_emb)     # bias added in poly2_part
+        return {"y_pred": self.output_activation(y_pred)}
+
+
+class FmFM(_ZooModel):
+    """Field-matrixed Factorization Machine (FmFM.py:25-94): a trained vector ("vectorized") or matrix ("matrixed")
+    per field pair between the two embeddings."""
+
+    def __init__(self, feature_map, model_id="FmFM", gpu=-1, learning_rate=1e-3, embedding_dim=10, regularizer=None,
+                 field_interaction_type="matrixed", **kwargs):
+        self._base(feature_map, model_id, gpu, regularizer, regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        num_fields = feature_map.num_fields
+        interact_dim = int(num_fields * (num_fields - 1) / 2)
+        self.field_interaction_type = field_interaction_type
+        # a bare Parameter: reset_parameters() does not touch it, regularization_loss() counts it as a net parameter
+        if field_interaction_type == "vectorized":
+            self.interaction_weight = nn.Parameter(torch.Tensor(interact_dim, embedding_dim))
+        elif field_interaction_type == "matrixed":
+            self.interaction_weight = nn.Parameter(torch.Tensor(interact_dim, embedding_dim, embedding_dim))
+        else:
+            raise ValueError("field_interaction_type={} is not supported.".format(field_interaction_type))
+        nn.init.xavier_normal_(self.interaction_weight)
+        self.lr_layer = LogisticRegression(feature_map)
+        self.triu_index = torch.triu_indices(num_fields, num_fields, offset=1).to(self.device)
+        self._mode = "vector" if field_interaction_type == "vectorized" else "matrix"
+        # fused=False: module by module, as the reference's class composes it (the two [B, P, D] gathers, the batched
+        # product, the two sums as tensors): the same numbers
+        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_PAIRFM_FUSED", "1") != "0"))
+        self._native = pair_interaction_native(num_fields, embedding_dim, self._mode)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        if self._fused and self._native:
+            # ... and lr_layer(X) is the fused node's addend: no separate add launch
+            y_pred = pair_interaction(feature_emb, self.interaction_weight, self._mode, addend=self.lr_layer(X))
+            return {"y_pred": self.output_activation(y_pred)}
+        index = self.triu_index.to(feature_emb.device)
+        left_emb = torch.index_select(feature_emb, 1, index[0])
+        right_emb = torch.index_select(feature_emb, 1, index[1])
+        if self.field_interaction_type == "vectorized":
+            left_emb = left_emb * self.interaction_weight
+        else:
+            left_emb = torch.matmul(left_emb.unsqueeze(2), self.interaction_weight).squeeze(2)
+        y_pred = (left_emb * right_emb).sum(dim=-1).sum(dim=-1, keepdim=True)
+        y_pred = y_pred + self.lr_layer(X)
+        return {"y_pred": self.output_activation(y_pred)}

@@ -929,6 +929,43 @@ int fx_afm_attn_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int3
                     int64_t lddx, float* grads, float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FwFM / FmFM (csrc/fx_pairfm.hip): the field-pair interaction with one trained parameter per pair, fused over
+ * the [B, F*D] gather record X (row stride ldx floats).  For the pairs p = (i, j), i < j, in the order of
+ * torch.triu_indices (model_zoo/FmFM/src/FmFM.py:68; the triu_mask select of inner_product.py:63-66 for FwFM):
+ *     out[b] = sum_p u_p(x_i) . x_j  (+ sum_c wlin[c] x[b, c])  (+ bias[0])  (+ addend[b])
+ *     mode 0 SCALAR: u_p(x) = r_p x      W = r [P]        (model_zoo/FwFM/src/FwFM.py:78-79)
+ *     mode 1 VECTOR: u_p(x) = w_p * x    W = w [P, D]     (FmFM.py:86-87)
+ *     mode 2 MATRIX: u_p(x) = x^T M_p    W = M [P, D, D]  (FmFM.py:88-89: left_emb @ M_p, then . right_emb)
+ *   wlin (nullable, [F*D]) is FwFM's "FiLV" linear part (FwFM.py:65, 87), bias (nullable, one float in device
+ *   memory) interaction_weight.bias (FwFM.py:56), addend (nullable, [B]) lr_layer(X) (FmFM.py:91) or FwFM's "LW" /
+ *   "FeLV" linear part (FwFM.py:80-85).
+ *   fx_pairfm_fwd : out [B], one launch.
+ *   fx_pairfm_bwd : with g = dout [B]:
+ *                     dx_i = g (sum_{j > i} M_ij x_j + sum_{j < i} M_ji^T x_j) + g wlin_i   (MATRIX; w_p * x_j and
+ *                     r_p x_j in the other modes) -> dX [B, F*D] (row stride lddx), one launch;
+ *                     dW_p = sum_b g_b x_i (x) x_j (MATRIX), sum_b g_b (x_i * x_j) (VECTOR), sum_b g_b (x_i . x_j)
+ *                     (SCALAR), dwlin = sum_b g_b x_b, dbias = sum_b g_b -> grads = [dW | dwlin (F*D, when wlin is
+ *                     given) | dbias (1, when has_bias)], one launch over slabs of samples (their partial rows in
+ *                     `workspace`) and fx_colsum over the slabs (one slab: straight into grads).  The addend's
+ *                     gradient is g.
+ *   A workgroup owns a tile of samples (fx_pairfm_tile_rows) and every pair for them: W streams past the tile.
+ *   No per-pair value is written to memory.  No atomics: two runs give the same bits.  fp32.  16-byte accesses of
+ *   X, dX and W when D % 4 == 0 and base pointers and row strides are 16-byte aligned, 4-byte otherwise.
+ *   fx_pairfm_limits : limits[3] = {least F, most F*D, most D}: the native envelope (housekeeping); a shape
+ *                     outside it is refused with FX_ERR_INVALID.
+ *   fx_pairfm_tile_rows : samples one workgroup owns at a time, for tests of the tile boundaries (housekeeping).
+ *   fx_pairfm_workspace_floats : floats of fx_pairfm_bwd's workspace (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+void fx_pairfm_limits(int32_t* limits);
+int32_t fx_pairfm_tile_rows(int32_t mode, int32_t F, int32_t D);
+int64_t fx_pairfm_workspace_floats(int32_t mode, int64_t B, int32_t F, int32_t D);
+int fx_pairfm_fwd(const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t mode, const float* W,
+                  const float* wlin, const float* bias, const float* addend, float* out, fx_stream_t stream);
+int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t mode,
+                  const float* W, const float* wlin, int32_t has_bias, float* dX, int64_t lddx, float* grads,
+                  float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
