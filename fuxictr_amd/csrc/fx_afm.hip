@@ -126,7 +126,7 @@ __device__ __forceinline__ void af_stage_weights(const AfArgs& p, const AfLds& L
     for (int d = t; d < p.D; d += T) smem[L.wp + d] = p.wp[d];
     uint32_t* tab = reinterpret_cast<uint32_t*>(smem + L.tab);
     for (int i = t; i < p.F - 1; i += T) {
-        const int off = i * (2 * p.F - i - 1) / 2;
+        const int off = fx_pair_off(i, p.F);
         for (int j = i + 1; j < p.F; ++j) tab[off + j - i - 1] = ((uint32_t)i << 16) | (uint32_t)j;
     }
 }
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(64 * AF_WAVES) void k_afm_attn_bwd(AfArgs p) {
             for (int j = 0; j < F; ++j) {
                 if (j == i) continue;
                 const int lo = j < i ? j : i, hi = j < i ? i : j;
-                const int q = lo * (2 * F - lo - 1) / 2 + hi - lo - 1;
+                const int q = fx_pair_off(lo, F) + hi - lo - 1;
                 const float ds = dsv[q], dt = dtv[q];
                 const uint32_t mlo = mlov[q], mhi = mhiv[q];
                 float v[VEC];
@@ -399,10 +399,6 @@ __global__ __launch_bounds__(64 * AF_WAVES) void k_afm_attn_bwd(AfArgs p) {
     }
 }
 
-static inline bool af_vec_ok(const void* ptr, int64_t ld) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld % 4 == 0;
-}
-
 static int af_check(const char* who, int64_t B, int32_t F, int32_t D, int32_t A) {
     FX_CHECK_ARG(F >= 2, "%s: F=%d, limit F >= 2", who, F);
     FX_CHECK_ARG(D >= 1 && D <= AF_MAX_D, "%s: D=%d, limit 1 <= D <= %d", who, D, AF_MAX_D);
@@ -417,10 +413,6 @@ static int af_check(const char* who, int64_t B, int32_t F, int32_t D, int32_t A)
 static unsigned af_grid(int64_t B, int nw) {
     const int64_t tiles = fx_ceil_div(B, nw);
     return (unsigned)(tiles < AF_MAX_WG ? tiles : AF_MAX_WG);
-}
-
-static hipError_t af_allow_lds(const void* kernel) {
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AF_LDS_MAX);
 }
 
 extern "C" void fx_afm_attn_limits(int32_t* limits) {
@@ -458,9 +450,9 @@ extern "C" int fx_afm_attn_fwd(const float* X, int64_t ldx, int64_t B, int32_t F
     p.X = X; p.ldx = ldx; p.W1 = W1; p.b1 = b1; p.w2 = w2; p.wp = wp; p.addend = addend; p.out = out;
     p.stats = stats; p.B = B; p.F = F; p.D = D; p.A = A; p.P = F * (F - 1) / 2;
     p.nw = af_waves(F, D, A, p.P);
-    const bool vec4 = D % 4 == 0 && af_vec_ok(X, ldx);
-    static const hipError_t lds_ok[2] = {af_allow_lds(reinterpret_cast<const void*>(k_afm_attn_fwd<1>)),
-                                         af_allow_lds(reinterpret_cast<const void*>(k_afm_attn_fwd<4>))};
+    const bool vec4 = D % 4 == 0 && fx_vec_ok(X, ldx);
+    static const hipError_t lds_ok[2] = {fx_allow_lds(k_afm_attn_fwd<1>, AF_LDS_MAX),
+                                         fx_allow_lds(k_afm_attn_fwd<4>, AF_LDS_MAX)};
     FX_CHECK_HIP(lds_ok[vec4 ? 1 : 0]);
     const size_t lds = af_lds_bytes(F, D, A, p.P, false, p.nw);
     const dim3 grid(af_grid(B, p.nw)), block(64 * p.nw);
@@ -492,9 +484,9 @@ extern "C" int fx_afm_attn_bwd(const float* g, const float* X, int64_t ldx, int6
     p.dX = dX; p.lddx = lddx; p.B = B; p.F = F; p.D = D; p.A = A; p.P = F * (F - 1) / 2;
     p.nw = af_waves(F, D, A, p.P);
     p.partial = workspace;
-    const bool vec4 = D % 4 == 0 && af_vec_ok(X, ldx) && af_vec_ok(dX, lddx);
-    static const hipError_t lds_ok[2] = {af_allow_lds(reinterpret_cast<const void*>(k_afm_attn_bwd<1>)),
-                                         af_allow_lds(reinterpret_cast<const void*>(k_afm_attn_bwd<4>))};
+    const bool vec4 = D % 4 == 0 && fx_vec_ok(X, ldx) && fx_vec_ok(dX, lddx);
+    static const hipError_t lds_ok[2] = {fx_allow_lds(k_afm_attn_bwd<1>, AF_LDS_MAX),
+                                         fx_allow_lds(k_afm_attn_bwd<4>, AF_LDS_MAX)};
     FX_CHECK_HIP(lds_ok[vec4 ? 1 : 0]);
     const size_t lds = af_lds_bytes(F, D, A, p.P, true, p.nw);
     const unsigned G = af_grid(B, p.nw);

@@ -25,10 +25,9 @@
 
 // ---------------------------------------------------------------------------------------------------------
 // pairs
-__host__ __device__ static inline int bl_pstart(int F, int i) { return i * (2 * F - i - 1) / 2; }   // first pair of left field i
 __device__ __forceinline__ int bl_left_of(int F, int p) {
     int i = 0;
-    while (i + 1 < F - 1 && bl_pstart(F, i + 1) <= p) ++i;
+    while (i + 1 < F - 1 && fx_pair_off(i + 1, F) <= p) ++i;
     return i;
 }
 
@@ -149,7 +148,7 @@ __global__ __launch_bounds__(BL_T) void k_bl_fwd(BlArgs p) {
     if ((int)threadIdx.x < npl) {
         const int i = bl_left_of(p.F, p0 + threadIdx.x);
         sI[threadIdx.x] = i;
-        sJ[threadIdx.x] = i + 1 + (p0 + threadIdx.x - bl_pstart(p.F, i));
+        sJ[threadIdx.x] = i + 1 + (p0 + threadIdx.x - fx_pair_off(i, p.F));
     }
     __syncthreads();
     if (p.type == 2) {
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(BL_T) void k_bl_dw(BlArgs p) {
     if ((int)threadIdx.x < npl) {
         const int i = bl_left_of(p.F, p0 + threadIdx.x);
         sI[threadIdx.x] = i;
-        sJ[threadIdx.x] = i + 1 + (p0 + threadIdx.x - bl_pstart(p.F, i));
+        sJ[threadIdx.x] = i + 1 + (p0 + threadIdx.x - fx_pair_off(i, p.F));
     }
     constexpr int NACC = 16;
     float acc[NACC];
@@ -311,8 +310,8 @@ __global__ __launch_bounds__(BL_T) void k_bl_reduce_pairs(const float* perpair, 
     __shared__ double red[16][16];
     const int lane = threadIdx.x & 15, slice = threadIdx.x >> 4;
     const int w = blockIdx.y;
-    const int pa = type == 0 ? 0 : (w < F - 1 ? bl_pstart(F, w) : P);
-    const int pb = type == 0 ? P : (w < F - 1 ? bl_pstart(F, w + 1) : P);
+    const int pa = type == 0 ? 0 : (w < F - 1 ? fx_pair_off(w, F) : P);
+    const int pb = type == 0 ? P : (w < F - 1 ? fx_pair_off(w + 1, F) : P);
     const int o = blockIdx.x * 16 + lane;
     double s = 0.0;
     if (o < DD)
@@ -355,7 +354,7 @@ __global__ __launch_bounds__(BL_T) void k_bl_dx(BlArgs p) {
         for (int i = 0; i < F - 1; ++i) {
             for (int j0 = i + 1; j0 < F; j0 += PG) {
                 const int npl = F - j0 < PG ? F - j0 : PG;
-                const int pbase = bl_pstart(F, i) + (j0 - i - 1);
+                const int pbase = fx_pair_off(i, F) + (j0 - i - 1);
                 const bool one = p.type != 2;
                 __syncthreads();             // the last chunk's readers of sW / sPT are done; sV / sdV are written
                 const bool stage = p.type == 2 || (p.type == 1 ? j0 == i + 1 : (i == 0 && j0 == 1));
@@ -457,8 +456,6 @@ static int bl_check(const char* who, const float* X, int64_t x_ld, int64_t B, in
     return FX_OK;
 }
 
-static inline bool bl_al16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 extern "C" int64_t fx_bilinear_workspace_floats(int64_t B, int32_t F, int32_t D) {
     if (F < 2 || F > BL_MAX || D < 1 || D > BL_MAX) return 0;
     const BlPlan q = bl_plan(B, F, D, D % 4 == 0);
@@ -474,8 +471,7 @@ extern "C" int fx_bilinear_fwd(const float* X, int64_t x_ld, int64_t B, int32_t 
     FX_CHECK_ARG(out_col >= 0 && out_ld >= out_col + (int64_t)P * D,
                  "fx_bilinear_fwd: row stride %lld < column offset %lld + P*D", (long long)out_ld, (long long)out_col);
     if (B == 0) return FX_OK;
-    const bool vec4 = D % 4 == 0 && x_ld % 4 == 0 && out_ld % 4 == 0 && out_col % 4 == 0 && bl_al16(X) &&
-                      bl_al16(W) && bl_al16(out);
+    const bool vec4 = D % 4 == 0 && out_col % 4 == 0 && fx_vec_ok(X, x_ld) && fx_al16(W) && fx_vec_ok(out, out_ld);
     const BlPlan q = bl_plan(B, F, D, vec4);
     FX_CHECK_ARG(q.lds_pg <= BL_LDS_STATIC, "fx_bilinear_fwd: %zu bytes of LDS", q.lds_pg);
     BlArgs p;
@@ -503,8 +499,8 @@ extern "C" int fx_bilinear_bwd(const float* X, int64_t x_ld, int64_t B, int32_t 
                  "fx_bilinear_bwd: row stride %lld < column offset %lld + P*D", (long long)dout_ld,
                  (long long)dout_col);
     FX_CHECK_ARG(dx_ld >= (int64_t)F * D, "fx_bilinear_bwd: dX sample stride %lld < F*D", (long long)dx_ld);
-    const bool vec4 = D % 4 == 0 && x_ld % 4 == 0 && dout_ld % 4 == 0 && dout_col % 4 == 0 && dx_ld % 4 == 0 &&
-                      bl_al16(X) && bl_al16(W) && bl_al16(dOut) && bl_al16(dX) && bl_al16(workspace);
+    const bool vec4 = D % 4 == 0 && dout_col % 4 == 0 && fx_vec_ok(X, x_ld) && fx_al16(W) &&
+                      fx_vec_ok(dOut, dout_ld) && fx_vec_ok(dX, dx_ld) && fx_al16(workspace);
     const BlPlan q = bl_plan(B, F, D, vec4);
     FX_CHECK_ARG(q.lds_pg <= BL_LDS_STATIC && q.lds_dx <= BL_LDS_STATIC, "fx_bilinear_bwd: %zu / %zu bytes of LDS",
                  q.lds_pg, q.lds_dx);
@@ -764,8 +760,7 @@ extern "C" int fx_senet_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, 
     const size_t lds = se_lds_bytes(F, R, true);
     FX_CHECK_ARG(lds <= SE_LDS_MAX, "fx_senet_bwd: %zu bytes of LDS", lds);
     // (dynamic LDS above 64 KiB has to be allowed per kernel: asked for once)
-    static const hipError_t lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_senet_bwd),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, SE_LDS_MAX);
+    static const hipError_t lds_ok = fx_allow_lds(k_senet_bwd, SE_LDS_MAX);
     FX_CHECK_HIP(lds_ok);
     const unsigned grid = se_bwd_grid(B);
     hipStream_t s = fx_hip_stream(stream);

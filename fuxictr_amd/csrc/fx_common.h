@@ -45,6 +45,22 @@ static inline int fx_env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// ---- what the hosts of the fused layers ask before a launch ----------------------------------------------
+// A 16-byte aligned pointer: the float4 accesses at multiples of 4 floats behind it are legal ...
+static inline bool fx_al16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
+// ... and stay so in every row when the rows lie `ld` floats apart (ld = 0: one row).
+static inline bool fx_vec_ok(const void* ptr, int64_t ld) { return fx_al16(ptr) && ld % 4 == 0; }
+// Lets `kernel` take up to `bytes` of dynamic LDS (beyond the 64 KiB a launch gets unasked).  Callers keep the
+// result in a function-local `static const`: one call per kernel and process.
+template <typename Kernel>
+static inline hipError_t fx_allow_lds(Kernel kernel, int bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               bytes);
+}
+// The F (F - 1) / 2 field pairs i < j in triu order: the index of (i, i + 1), the first pair of left field i.
+// Pair (i, j) is fx_pair_off(i, F) + j - i - 1.
+__host__ __device__ static inline int fx_pair_off(int i, int F) { return i * (2 * F - i - 1) / 2; }
+
 // ---- fx_sort.hip: device-wide stable LSD radix sort of (uint32 key, uint32 value) pairs --------
 size_t fx_sort_temp_bytes(int64_t n);
 size_t fx_sort_zero_words(int64_t n);   // leading words of `temp` that must be 0 before the sort

@@ -347,10 +347,6 @@ __global__ __launch_bounds__(CN_RED_COLS * CN_RED_PARTS) void k_cross_net_reduce
 static_assert(CN_RED_COLS == 64 && CN_RED_PARTS == 4, "k_cross_net_reduce: a group is a wave, four groups");
 static_assert(CN_MAX_L <= CN_THREADS && CN_MAX_L <= 64, "one thread per layer sums t_l");
 
-static inline bool cn_vec_ok(const void* ptr, int64_t ld) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld % 4 == 0;
-}
-
 // a [rows, cols] matrix with row stride ld
 static int cn_check_mat(const char* who, const char* name, const void* ptr, int64_t ld, int64_t cols) {
     FX_CHECK_ARG(ptr, "%s: null %s", who, name);
@@ -399,8 +395,8 @@ extern "C" int fx_cross_net_fwd(const float* x0, int64_t ldx0, const float* w, c
     memset(&p, 0, sizeof(p));
     p.x0 = x0; p.ldx0 = ldx0; p.w = w; p.b = b; p.out = out; p.ldout = ldout; p.s = s;
     p.rows = rows; p.cols = cols; p.L = L;
-    const bool vec4 = cols % 4 == 0 && cn_vec_ok(x0, ldx0) && cn_vec_ok(out, ldout) && cn_vec_ok(w, 0) &&
-                      cn_vec_ok(b, 0);
+    const bool vec4 = cols % 4 == 0 && fx_vec_ok(x0, ldx0) && fx_vec_ok(out, ldout) && fx_vec_ok(w, 0) &&
+                      fx_vec_ok(b, 0);
     const dim3 grid(cn_grid(rows)), block(64, CN_ROWS);
     hipStream_t st = fx_hip_stream(stream);
     if (vec4) hipLaunchKernelGGL((k_cross_net_fwd<4, CN_NREG / 4>), grid, block, 0, st, p);
@@ -432,8 +428,8 @@ extern "C" int fx_cross_net_bwd(const float* dout, int64_t lddout, const float* 
     p.dx0 = dx0; p.lddx0 = lddx0; p.dw = dw; p.db = db; p.partial = workspace; p.pstride = cn_pstride(cols, L);
     p.rows = rows; p.cols = cols; p.L = L; p.init = init ? 1 : 0;
     p.G = (int)cn_grid(rows);
-    const bool vec4 = cols % 4 == 0 && cn_vec_ok(dout, lddout) && cn_vec_ok(x0, ldx0) && cn_vec_ok(dx0, lddx0) &&
-                      cn_vec_ok(w, 0) && cn_vec_ok(workspace, 0);
+    const bool vec4 = cols % 4 == 0 && fx_vec_ok(dout, lddout) && fx_vec_ok(x0, ldx0) && fx_vec_ok(dx0, lddx0) &&
+                      fx_vec_ok(w, 0) && fx_vec_ok(workspace, 0);
     const dim3 grid(p.G), block(64, CN_ROWS);
     if (vec4) hipLaunchKernelGGL((k_cross_net_bwd<2, 2, 1>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((k_cross_net_bwd<1, 1, 2>), grid, block, 0, st, p);

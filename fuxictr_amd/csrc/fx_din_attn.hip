@@ -1361,10 +1361,6 @@ extern "C" int64_t fx_din_attn_workspace_floats(int64_t B, int32_t L, int32_t E,
     return need;
 }
 
-static bool da_al16(const void* p, int64_t ld0, int64_t ld1 = 0) {
-    return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld0 % 4 == 0 && ld1 % 4 == 0;
-}
-
 enum DaPass { DA_STATS, DA_FWD, DA_BWD_SUMS, DA_BWD };
 
 struct DaGradRows {          // the row operands only the backward passes have (null: the pass has none)
@@ -1395,8 +1391,9 @@ static int da_prepare(DaPass pass, const char* who, const float* q, int64_t q_ld
     a.q = q; a.q_ld = q_ld; a.K = K; a.k_ldb = k_ldb; a.k_ldl = k_ldl;
     a.n_rows = B * L; a.nb = (int32_t)B; a.L = L; a.E = E; a.H = H; a.W1 = W1; a.b1 = b1;
     a.dout = g_.dout; a.dout_ld = g_.dout_ld; a.dK = g_.dK; a.dk_ldb = g_.dk_ldb; a.dk_ldl = g_.dk_ldl;
-    a.vec = (E % 8 == 0) && da_al16(q, q_ld) && da_al16(K, k_ldb, k_ldl) &&
-            (!g_.dout || da_al16(g_.dout, g_.dout_ld)) && (!g_.dK || da_al16(g_.dK, g_.dk_ldb, g_.dk_ldl));
+    a.vec = (E % 8 == 0) && fx_vec_ok(q, q_ld) && fx_vec_ok(K, k_ldb) && k_ldl % 4 == 0 &&
+            (!g_.dout || fx_vec_ok(g_.dout, g_.dout_ld)) &&
+            (!g_.dK || (fx_vec_ok(g_.dK, g_.dk_ldb) && g_.dk_ldl % 4 == 0));
     // the q-split formulation: E = 8 / 16 with 16-byte rows, L >= 32 (FX_DIN_ATTN_QSPLIT=0: never)
     static const bool on = fx_env_int("FX_DIN_ATTN_QSPLIT", 1) != 0;
     p.qsplit = on && a.vec && (E == 16 || E == 8) && L >= 32;

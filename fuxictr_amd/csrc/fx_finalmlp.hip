@@ -335,10 +335,6 @@ __global__ __launch_bounds__(FM_T) void k_biagg_bwd(AggArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static inline bool fm_al16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-// a matrix that 16-byte accesses may touch: base and row stride (0: a broadcast row) multiples of 16 bytes
-static inline bool fm_vec_ok(const void* ptr, int64_t ld) { return fm_al16(ptr) && ld % 4 == 0; }
-
 static int fm_reduce(hipStream_t s, const float* partial, int nslab, int64_t C, const FmOut& o) {
     hipLaunchKernelGGL(k_fm_reduce, dim3((unsigned)fx_ceil_div(C, 64)), dim3(FM_T), 0, s, partial, nslab, C, o);
     FX_CHECK_LAUNCH();
@@ -384,8 +380,8 @@ extern "C" int fx_gate2_fwd(const float* E, int64_t e_ld, int64_t B, int32_t W, 
     p.E = E; p.e_ld = e_ld; p.B = B; p.W = W;
     p.Z1 = Z1; p.z1_ld = z1_ld; p.Z2 = Z2; p.z2_ld = z2_ld;
     p.F1 = F1; p.f1_ld = f1_ld; p.F2 = F2; p.f2_ld = f2_ld;
-    const bool vec4 = W % 4 == 0 && fm_vec_ok(E, e_ld) && fm_vec_ok(Z1, z1_ld) && fm_vec_ok(F1, f1_ld) &&
-                      (!Z2 || (fm_vec_ok(Z2, z2_ld) && fm_vec_ok(F2, f2_ld)));
+    const bool vec4 = W % 4 == 0 && fx_vec_ok(E, e_ld) && fx_vec_ok(Z1, z1_ld) && fx_vec_ok(F1, f1_ld) &&
+                      (!Z2 || (fx_vec_ok(Z2, z2_ld) && fx_vec_ok(F2, f2_ld)));
     const int64_t total = B * (vec4 ? W / 4 : W);
     int64_t grid = fx_ceil_div(total, FM_T);
     if (grid > FM_MAX_WG) grid = FM_MAX_WG;
@@ -425,9 +421,9 @@ extern "C" int fx_gate2_bwd(const float* dF1, int64_t df1_ld, const float* dF2, 
     p.dZ1 = dZ1; p.dz1_ld = dz1_ld; p.dZ2 = dZ2; p.dz2_ld = dz2_ld;
     const FmSlabs sl = fm_slabs(B);
     p.partial = workspace; p.rows_per_slab = sl.rows_per_slab;
-    const bool vec4 = W % 4 == 0 && fm_vec_ok(E, e_ld) && fm_vec_ok(dE, de_ld) && fm_vec_ok(Z1, z1_ld) &&
-                      fm_vec_ok(dF1, df1_ld) && (bc1 || fm_vec_ok(dZ1, dz1_ld)) &&
-                      (!Z2 || (fm_vec_ok(Z2, z2_ld) && fm_vec_ok(dF2, df2_ld) && (bc2 || fm_vec_ok(dZ2, dz2_ld))));
+    const bool vec4 = W % 4 == 0 && fx_vec_ok(E, e_ld) && fx_vec_ok(dE, de_ld) && fx_vec_ok(Z1, z1_ld) &&
+                      fx_vec_ok(dF1, df1_ld) && (bc1 || fx_vec_ok(dZ1, dz1_ld)) &&
+                      (!Z2 || (fx_vec_ok(Z2, z2_ld) && fx_vec_ok(dF2, df2_ld) && (bc2 || fx_vec_ok(dZ2, dz2_ld))));
     const dim3 grid((unsigned)fx_ceil_div(vec4 ? W / 4 : W, FM_T), (unsigned)sl.nslab);
     hipStream_t s = fx_hip_stream(stream);
     if (vec4) hipLaunchKernelGGL(k_gate2_bwd<4>, grid, dim3(FM_T), 0, s, p);
@@ -466,8 +462,8 @@ extern "C" int fx_biagg_fwd(const float* X, int64_t x_ld, const float* Y, int64_
     p.X = X; p.x_ld = x_ld; p.Y = Y; p.y_ld = y_ld; p.T = T; p.t_ld = t_ld;
     p.B = B; p.dx = dx; p.dy = dy;
     p.wx = w_x; p.wy = w_y; p.bx = b_x; p.by = b_y; p.out_add = out_add; p.out = out;
-    const bool vec4 = dx % 4 == 0 && dy % 4 == 0 && fm_vec_ok(X, x_ld) && fm_vec_ok(Y, y_ld) && fm_vec_ok(T, t_ld) &&
-                      fm_al16(w_x) && fm_al16(w_y);
+    const bool vec4 = dx % 4 == 0 && dy % 4 == 0 && fx_vec_ok(X, x_ld) && fx_vec_ok(Y, y_ld) && fx_vec_ok(T, t_ld) &&
+                      fx_al16(w_x) && fx_al16(w_y);
     p.L = ag_lanes(dx, dy, vec4 ? 4 : 1);
     const int64_t per_wg = (FM_T / 64) * (64 / p.L);
     int64_t grid = fx_ceil_div(B, per_wg);
@@ -500,9 +496,9 @@ extern "C" int fx_biagg_bwd(const float* g, const float* X, int64_t x_ld, const 
     p.dT = dT; p.dt_ld = dt_ld; p.dY = dY; p.dy_ld = dy_ld; p.dXr = dXr; p.dxr_ld = dxr_ld;
     const FmSlabs sl = fm_slabs(B);
     p.partial = workspace; p.rows_per_slab = sl.rows_per_slab;
-    const bool vec4 = dx % 4 == 0 && dy % 4 == 0 && fm_vec_ok(X, x_ld) && fm_vec_ok(Y, y_ld) && fm_vec_ok(T, t_ld) &&
-                      fm_al16(w_x) && fm_al16(w_y) && fm_vec_ok(dT, dt_ld) && fm_vec_ok(dY, dy_ld) &&
-                      (!dXr || fm_vec_ok(dXr, dxr_ld));
+    const bool vec4 = dx % 4 == 0 && dy % 4 == 0 && fx_vec_ok(X, x_ld) && fx_vec_ok(Y, y_ld) && fx_vec_ok(T, t_ld) &&
+                      fx_al16(w_x) && fx_al16(w_y) && fx_vec_ok(dT, dt_ld) && fx_vec_ok(dY, dy_ld) &&
+                      (!dXr || fx_vec_ok(dXr, dxr_ld));
     const int64_t chunks = vec4 ? (int64_t)dx / 4 + dy / 4 : (int64_t)dx + dy;
     const dim3 grid((unsigned)fx_ceil_div(chunks, FM_T), (unsigned)sl.nslab);
     hipStream_t s = fx_hip_stream(stream);

@@ -112,10 +112,6 @@ __global__ __launch_bounds__(GX_LANES * GX_ROWS) void k_gate_cross_bwd(GxArgs p)
     }
 }
 
-static inline bool gx_vec_ok(const void* ptr, int64_t ld) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld % 4 == 0;
-}
-
 // a [rows, width] matrix with row stride ld
 static int gx_check_mat(const char* who, const char* name, const void* ptr, int64_t ld, int64_t width) {
     FX_CHECK_ARG(ptr, "%s: null %s", who, name);
@@ -149,8 +145,8 @@ extern "C" int fx_gate_cross_fwd(const float* h, int64_t ldh, const float* x0, i
     memset(&p, 0, sizeof(p));
     p.h = h; p.ldh = ldh; p.x0 = x0; p.ldx0 = ldx0; p.xi = xi; p.ldxi = ldxi; p.b = b;
     p.xn = xn; p.ldxn = ldxn; p.rows = rows; p.cols = cols;
-    const bool vec4 = cols % 4 == 0 && gx_vec_ok(h, ldh) && gx_vec_ok(x0, ldx0) && gx_vec_ok(xi, ldxi) &&
-                      gx_vec_ok(xn, ldxn) && gx_vec_ok(b, 0);
+    const bool vec4 = cols % 4 == 0 && fx_vec_ok(h, ldh) && fx_vec_ok(x0, ldx0) && fx_vec_ok(xi, ldxi) &&
+                      fx_vec_ok(xn, ldxn) && fx_vec_ok(b, 0);
     const dim3 grid = gx_grid(rows, vec4 ? cols / 4 : cols), block(GX_LANES, GX_ROWS);
     hipStream_t s = fx_hip_stream(stream);
     if (vec4) hipLaunchKernelGGL(k_gate_cross_fwd<4>, grid, block, 0, s, p);
@@ -177,8 +173,8 @@ extern "C" int fx_gate_cross_bwd(const float* dxn, int64_t lddxn, const float* h
     p.dxn = dxn; p.lddxn = lddxn; p.h = h; p.ldh = ldh; p.x0 = x0; p.ldx0 = ldx0; p.b = b;
     p.dh = dh; p.lddh = lddh; p.dx0 = dx0; p.lddx0 = lddx0; p.rows = rows; p.cols = cols;
     p.init = init ? 1 : 0; p.add_dxn = add_dxn ? 1 : 0;
-    const bool vec4 = cols % 4 == 0 && gx_vec_ok(dxn, lddxn) && gx_vec_ok(h, ldh) && gx_vec_ok(x0, ldx0) &&
-                      gx_vec_ok(dh, lddh) && gx_vec_ok(dx0, lddx0) && gx_vec_ok(b, 0);
+    const bool vec4 = cols % 4 == 0 && fx_vec_ok(dxn, lddxn) && fx_vec_ok(h, ldh) && fx_vec_ok(x0, ldx0) &&
+                      fx_vec_ok(dh, lddh) && fx_vec_ok(dx0, lddx0) && fx_vec_ok(b, 0);
     const dim3 grid = gx_grid(rows, vec4 ? cols / 4 : cols), block(GX_LANES, GX_ROWS);
     hipStream_t s = fx_hip_stream(stream);
     if (vec4) hipLaunchKernelGGL(k_gate_cross_bwd<4>, grid, block, 0, s, p);

@@ -335,8 +335,6 @@ __global__ __launch_bounds__(LN_T) void k_mask_grad(const float* dM, int64_t dm_
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static inline bool ln_al16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 template <bool BWD, int VEC, int CH, bool BLOCK>
 static void ln_launch_one(unsigned grid, hipStream_t s, const LnArgs& p) {
     if constexpr (BWD) hipLaunchKernelGGL((k_ln_bwd<VEC, CH, BLOCK>), dim3(grid), dim3(LN_T), 0, s, p);
@@ -402,8 +400,7 @@ extern "C" int fx_layernorm_fwd(const float* X, int64_t x_ld, int64_t rows, int3
     p.X = X; p.x_ld = x_ld; p.rows = rows; p.G = G; p.N = N; p.relu = relu ? 1 : 0;
     p.gamma = gamma; p.beta = beta; p.eps = eps;
     p.Y = Y + y_col; p.y_ld = y_ld; p.stats = stats;
-    const bool vec4 = N % 4 == 0 && x_ld % 4 == 0 && y_ld % 4 == 0 && ln_al16(X) && ln_al16(p.Y) &&
-                      ln_al16(gamma) && ln_al16(beta);
+    const bool vec4 = N % 4 == 0 && fx_vec_ok(X, x_ld) && fx_vec_ok(p.Y, y_ld) && fx_al16(gamma) && fx_al16(beta);
     return ln_launch<false>(ln_plan(N, vec4), fx_hip_stream(stream), p);
 }
 
@@ -433,9 +430,8 @@ extern "C" int fx_layernorm_bwd(const float* X, int64_t x_ld, int64_t rows, int3
     p.dX = dX; p.dx_ld = dx_ld; p.dx_acc = dx_accumulate ? 1 : 0;
     const LnSlabs sl = ln_slabs(rows, C);
     p.partial = workspace; p.rows_per_slab = sl.rows_per_slab;
-    const bool vec4 = N % 4 == 0 && x_ld % 4 == 0 && dy_ld % 4 == 0 && dx_ld % 4 == 0 && ln_al16(X) &&
-                      ln_al16(p.dY) && ln_al16(dX) && ln_al16(gamma) &&
-                      (!relu || (y_ld % 4 == 0 && ln_al16(p.Y)));
+    const bool vec4 = N % 4 == 0 && fx_vec_ok(X, x_ld) && fx_vec_ok(p.dY, dy_ld) && fx_vec_ok(dX, dx_ld) &&
+                      fx_al16(gamma) && (!relu || fx_vec_ok(p.Y, y_ld));
     hipStream_t s = fx_hip_stream(stream);
     if (int st = ln_launch<true>(ln_plan(N, vec4), s, p)) return st;
     hipLaunchKernelGGL(k_ln_dparam, dim3((unsigned)fx_ceil_div(C, LN_T), (unsigned)sl.nslab), dim3(LN_T), 0, s, p);
@@ -456,8 +452,7 @@ extern "C" int fx_mask_grad(const float* dM, int64_t dm_ld, const float* Vmask, 
                  "fx_mask_grad: a row stride is smaller than its row (%lld, %lld, %lld)", (long long)dm_ld,
                  (long long)vm_ld, (long long)out_ld);
     if (rows == 0) return FX_OK;
-    const bool vec4 = H % 4 == 0 && dm_ld % 4 == 0 && vm_ld % 4 == 0 && out_ld % 4 == 0 && ln_al16(dM) &&
-                      ln_al16(Vmask) && ln_al16(out);
+    const bool vec4 = H % 4 == 0 && fx_vec_ok(dM, dm_ld) && fx_vec_ok(Vmask, vm_ld) && fx_vec_ok(out, out_ld);
     const int64_t total = rows * (vec4 ? H / 4 : H);
     int64_t grid = fx_ceil_div(total, LN_T);
     if (grid > LN_MAX_WG) grid = LN_MAX_WG;

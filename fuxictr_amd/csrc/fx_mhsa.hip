@@ -315,11 +315,6 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_reduce(const float* partial, int 
     if (slice == 0 && e < n) out[e] = (float)((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
 }
 
-// dynamic LDS above 64 KiB has to be allowed per kernel: asked for once, for the largest image any shape needs
-static hipError_t mh_allow_lds(const void* kernel) {
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MH_LDS_MAX);
-}
-
 static int mh_check(const char* who, const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* Wq,
                     const float* Wk, const float* Wv, int32_t A, int32_t H) {
     FX_CHECK_ARG(F >= 1 && F <= MH_MAX, "%s: F=%d, limit 1 <= F <= 64", who, F);
@@ -366,9 +361,9 @@ extern "C" int fx_mhsa_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, i
     const bool wlds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 3, 1, true) <= MH_LDS_MAX;
     const size_t lds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 3, 1, wlds);
     const unsigned grid = (unsigned)(B < MH_FWD_GRID ? B : MH_FWD_GRID);
-    // (once per process: both instantiations may use the whole 160 KiB)
-    static const hipError_t lds_ok[2] = {mh_allow_lds(reinterpret_cast<const void*>(k_mhsa_fwd<false>)),
-                                         mh_allow_lds(reinterpret_cast<const void*>(k_mhsa_fwd<true>))};
+    // (once per process: both instantiations may use the whole 160 KiB, the largest image any shape needs)
+    static const hipError_t lds_ok[2] = {fx_allow_lds(k_mhsa_fwd<false>, MH_LDS_MAX),
+                                         fx_allow_lds(k_mhsa_fwd<true>, MH_LDS_MAX)};
     FX_CHECK_HIP(lds_ok[wlds ? 1 : 0]);
     if (wlds) hipLaunchKernelGGL(k_mhsa_fwd<true>, dim3(grid), dim3(MH_T), lds, fx_hip_stream(stream), p);
     else hipLaunchKernelGGL(k_mhsa_fwd<false>, dim3(grid), dim3(MH_T), lds, fx_hip_stream(stream), p);
@@ -381,7 +376,7 @@ static int mh_launch_bwd(const MhsaArgs& p, unsigned grid, size_t lds, hipStream
     const int AD = p.A * p.D;
 #define FX_MHSA_BWD(RR)                                                                                  \
     do {                                                                                                 \
-        static const hipError_t lds_ok = mh_allow_lds(reinterpret_cast<const void*>(k_mhsa_bwd<WLDS, RR>)); \
+        static const hipError_t lds_ok = fx_allow_lds(k_mhsa_bwd<WLDS, RR>, MH_LDS_MAX);                 \
         FX_CHECK_HIP(lds_ok);                                                                            \
         hipLaunchKernelGGL((k_mhsa_bwd<WLDS, RR>), dim3(grid), dim3(MH_T), lds, s, p);                   \
     } while (0)

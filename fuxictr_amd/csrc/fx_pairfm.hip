@@ -61,17 +61,15 @@ struct PfArgs {
     int slab_rows, has_bias;
 };
 
-__host__ __device__ inline int pf_off(int i, int F) { return i * (2 * F - i - 1) / 2; }
-
 // pair p -> (i, j)
 __device__ __forceinline__ void pf_pair(int p, int F, int& i, int& j) {
     const float b = 2.f * (float)F - 1.f;
     int ii = (int)((b - sqrtf(fmaxf(b * b - 8.f * (float)p, 0.f))) * 0.5f);
     ii = ii < 0 ? 0 : (ii > F - 2 ? F - 2 : ii);
-    while (ii > 0 && pf_off(ii, F) > p) --ii;
-    while (ii < F - 2 && pf_off(ii + 1, F) <= p) ++ii;
+    while (ii > 0 && fx_pair_off(ii, F) > p) --ii;
+    while (ii < F - 2 && fx_pair_off(ii + 1, F) <= p) ++ii;
     i = ii;
-    j = p - pf_off(ii, F) + ii + 1;
+    j = p - fx_pair_off(ii, F) + ii + 1;
 }
 
 static inline int pf_tile(int F, int D) { return F * D <= PF_TILE16_FD ? 16 : 8; }
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(PF_NT) void k_pairfm_tile(PfArgs a) {
                     for (int j = js; j < F; j += NS) {
                         if (j == i) continue;
                         const int lo = j < i ? j : i, hi = j < i ? i : j;
-                        const int p = pf_off(lo, F) + hi - lo - 1;
+                        const int p = fx_pair_off(lo, F) + hi - lo - 1;
                         const float* xj = xsT + j * D * T;
                         if (mode == PF_MATRIX) {
                             const float* Mp = a.W + (int64_t)p * D * D;
@@ -437,8 +435,6 @@ __global__ __launch_bounds__(PF_DW_NT) void k_pairfm_dw(PfArgs a, int ts) {
     }
 }
 
-static inline bool pf_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 static int pf_check(const char* who, int32_t mode, int64_t B, int32_t F, int32_t D) {
     FX_CHECK_ARG(mode >= PF_SCALAR && mode <= PF_MATRIX, "%s: mode=%d, not 0 (scalar), 1 (vector) or 2 (matrix)", who,
                  mode);
@@ -460,17 +456,11 @@ static inline int pf_dw_rows(int F, int D) {
     return fit < PF_DW_ROWS ? fit : PF_DW_ROWS;
 }
 
-static hipError_t pf_allow_lds(const void* kernel) {
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS_MAX);
-}
-
 template <bool BWD>
 static int pf_launch_tile(const PfArgs& p, int T, bool vec4, hipStream_t s) {
     static const hipError_t lds_ok[4] = {
-        pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_tile<16, 4, BWD>)),
-        pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_tile<16, 1, BWD>)),
-        pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_tile<8, 4, BWD>)),
-        pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_tile<8, 1, BWD>))};
+        fx_allow_lds(k_pairfm_tile<16, 4, BWD>, PF_LDS_MAX), fx_allow_lds(k_pairfm_tile<16, 1, BWD>, PF_LDS_MAX),
+        fx_allow_lds(k_pairfm_tile<8, 4, BWD>, PF_LDS_MAX), fx_allow_lds(k_pairfm_tile<8, 1, BWD>, PF_LDS_MAX)};
     FX_CHECK_HIP(lds_ok[(T == 16 ? 0 : 2) + (vec4 ? 0 : 1)]);
     const size_t lds = 4 * (size_t)(pf_tile_fixed(p.F, p.D, T) + (p.wlds + 3) / 4 * 4);
     const int64_t tiles = fx_ceil_div(p.B, T);
@@ -520,7 +510,7 @@ extern "C" int fx_pairfm_fwd(const float* X, int64_t ldx, int64_t B, int32_t F, 
     p.B = B; p.F = F; p.D = D; p.P = F * (F - 1) / 2; p.mode = mode; p.nW = pf_w_floats(mode, F, D);
     const int T = pf_tile(F, D);
     p.wlds = pf_wlds(mode, F, D, T);
-    const bool vec4 = D % 4 == 0 && pf_aligned(X) && ldx % 4 == 0 && pf_aligned(W);
+    const bool vec4 = D % 4 == 0 && fx_vec_ok(X, ldx) && fx_al16(W);
     return pf_launch_tile<false>(p, T, vec4, fx_hip_stream(stream));
 }
 
@@ -547,8 +537,8 @@ extern "C" int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_
     p.B = B; p.F = F; p.D = D; p.P = F * (F - 1) / 2; p.mode = mode; p.nW = nW; p.n = n;
     const int T = pf_tile(F, D);
     p.wlds = pf_wlds(mode, F, D, T);
-    const bool vecx = D % 4 == 0 && pf_aligned(X) && ldx % 4 == 0 && pf_aligned(W);
-    const bool vec4 = vecx && pf_aligned(dX) && lddx % 4 == 0;
+    const bool vecx = D % 4 == 0 && fx_vec_ok(X, ldx) && fx_al16(W);
+    const bool vec4 = vecx && fx_vec_ok(dX, lddx);
     const int NCF = F * (D / (vec4 ? 4 : 1));
     int ns = PF_NT / NCF;
     ns = ns > F - 1 ? F - 1 : ns;
@@ -566,8 +556,8 @@ extern "C" int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_
                           (wlin ? F * NC : 0) + (has_bias ? 1 : 0);
     const int ts = pf_dw_rows(F, D);
     const size_t lds = 4 * ((size_t)ts * ((F * D + 3) / 4 * 4) + ts);
-    static const hipError_t lds_ok[2] = {pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_dw<4>)),
-                                         pf_allow_lds(reinterpret_cast<const void*>(k_pairfm_dw<1>))};
+    static const hipError_t lds_ok[2] = {fx_allow_lds(k_pairfm_dw<4>, PF_LDS_MAX),
+                                         fx_allow_lds(k_pairfm_dw<1>, PF_LDS_MAX)};
     FX_CHECK_HIP(lds_ok[vecx ? 0 : 1]);
     const dim3 grid((unsigned)fx_ceil_div(items, PF_DW_NT), (unsigned)slabs), block(PF_DW_NT);
     if (vecx) hipLaunchKernelGGL(k_pairfm_dw<4>, grid, block, lds, s, p, ts);

@@ -86,6 +86,42 @@ def get_initializer(initializer):
     return initializer
 
 
+# ------------------------------------------------------------------------------------------------
+# what the kernels read in place, one helper per meaning: a tensor that fits is handed on as it is (a slice of
+# the gather record, a column slice of a cat's gradient), anything else is copied
+# ------------------------------------------------------------------------------------------------
+def _unit_cols(x):
+    """Unit stride over the last axis; any row stride, any alignment."""
+    return x if x.stride(-1) == 1 else x.contiguous()
+
+
+def _rows_view(x):
+    """[rows, n] as the GEMMs and fx_layernorm_* read it: unit column stride and 16-byte aligned rows (a prefix
+    of the gather record)."""
+    if x.stride(-1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+def _field_view(x):
+    """[B, F, D] with dense fields: unit stride over d, D over the fields, any sample stride (a prefix of the
+    gather record)."""
+    if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
+        x = x.contiguous()
+    return x
+
+
+def _field_rows(x):
+    """_field_view(x) as its [B, F * D] rows (a view of it, the sample stride kept)."""
+    x = _field_view(x)
+    B, F, D = x.shape
+    return x.as_strided((B, F * D), (x.stride(0), 1))
+
+
+def _empty(*shape, device):
+    return torch.empty(*shape, dtype=torch.float32, device=device)
+
+
 class _BatchState(object):
     """What the embedding path has already done for ONE batch: its packed input matrices (a captured
     step keeps them as its static buffers) and the results of the current step's launches."""
@@ -1599,8 +1635,7 @@ class _DlrmMixFn(torch.autograd.Function):
     def backward(ctx, g):
         (rec,) = ctx.saved_tensors
         B, F, D = rec.shape
-        if g.stride(-1) != 1:
-            g = g.contiguous()
+        g = _unit_cols(g)
         demb = torch.empty(B, F, D, dtype=torch.float32, device=rec.device)
         ops.dot_interact_bwd(rec.view(B, F * D), g, F, D, demb.view(B, F * D), tail=D + ctx.pad)
         # (the dense vector's gradient is a COPY of its slot, B x D floats: handing out a view of demb
@@ -1674,6 +1709,17 @@ _FORCE_SPLITK = int(_os.environ.get("FX_DW_SPLITK", "0"))
 _MLP_PAD = _os.environ.get("FX_MLP_PAD", "1") != "0"      # A/B switch of the 4-float input padding
 
 
+def _pad_cols(width):
+    """Zero columns behind a tower input of `width` floats that bring its rows to 16 bytes (_MLPFn.forward)."""
+    return (-width) % 4 if (width >= 64 and _MLP_PAD) else 0
+
+
+def tower_pad(tower, width):
+    """The columns the producer of `tower`'s [B, width] input appends itself: the fused node then takes the padded
+    rows as they are instead of padding them with a cat.  0 for a tower that runs module by module."""
+    return _pad_cols(width) if getattr(tower, "_fused", None) is not None else 0
+
+
 def _split_k_for(M, N, K):
     """Split the contraction when the output grid alone cannot fill 256 CUs (weight gradients): aim
     for ~1024 workgroups of 64x64 — the 4 per CU the 64x64 kernel keeps resident (measured,
@@ -1711,6 +1757,18 @@ class _Workspace(object):
         return buf
 
 
+def _bias_grad(dz, need_bias):
+    """-> (db or None, whether the dW GEMM sums it in its epilogue).  The GEMM does so only when it contracts over
+    more than 8 rows (fx_gemm_f32: "rowsum is not available on the K<=8 / N<=4 skinny paths"); a smaller batch
+    takes the column sums of dz in a launch of their own (_bias_grad_alone), after the GEMM."""
+    db = torch.empty(dz.shape[1], dtype=torch.float32, device=dz.device) if need_bias else None
+    return db, need_bias and dz.shape[0] > 8
+
+
+def _bias_grad_alone(dz, db):
+    ops.colsum(dz, db, _Workspace.get(dz.device, _lib.FX_COLSUM_CHUNKS * dz.shape[1]))
+
+
 def linear_grads(dz, x, W, need_bias, mask=None, add=None, dx_out=None):
     """dW, db (as linear_weight_grads) and dx = dz W (+ the ReLU `mask` of the layer below / the
     residual `add` in the epilogue), the two products in one launch.  dx_out: where dx goes (a
@@ -1728,8 +1786,10 @@ def linear_grads(dz, x, W, need_bias, mask=None, add=None, dx_out=None):
         sk = max(sk, min(8, Bsz // 256))
     sk = max(sk, 1)
     ws = _Workspace.get(dz.device, ops.gemm_workspace_floats(N_out, K_in, sk))
-    db = torch.empty(N_out, dtype=torch.float32, device=dz.device) if need_bias else None
-    ops.gemm_dw_dx(dz, x, W, dW, dx, split_k=sk, workspace=ws, rowsum=db, mask=mask, add=add)
+    db, in_gemm = _bias_grad(dz, need_bias)
+    ops.gemm_dw_dx(dz, x, W, dW, dx, split_k=sk, workspace=ws, rowsum=db if in_gemm else None, mask=mask, add=add)
+    if need_bias and not in_gemm:
+        _bias_grad_alone(dz, db)
     return dW, db, dx
 
 
@@ -1740,9 +1800,11 @@ def linear_weight_grads(dz, x, W_shape, need_bias):
     dW = torch.empty(N_out, K_in, dtype=torch.float32, device=dz.device)
     sk = _split_k_for(N_out, K_in, Bsz)
     ws = _Workspace.get(dz.device, ops.gemm_workspace_floats(N_out, K_in, sk))
-    db = torch.empty(N_out, dtype=torch.float32, device=dz.device) if need_bias else None
+    db, in_gemm = _bias_grad(dz, need_bias)
     # the bias gradient (column sums of dz) rides along in the dW GEMM: its A tiles ARE dz
-    ops.gemm(dz, x, dW, transa=True, transb=False, split_k=sk, workspace=ws, rowsum=db)
+    ops.gemm(dz, x, dW, transa=True, transb=False, split_k=sk, workspace=ws, rowsum=db if in_gemm else None)
+    if need_bias and not in_gemm:
+        _bias_grad_alone(dz, db)
     return dW, db
 
 
@@ -1833,15 +1895,14 @@ class _MLPFn(torch.autograd.Function):
         that is returned (DLRM: a slot of the gather record).
         An input that is already zero-padded to the aligned width (K0 + pad columns) is taken as it is."""
         need_dx = x.requires_grad
-        if x.stride(-1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-            x = x.contiguous()       # a 16-byte aligned row-strided view (record prefix) is read in place
+        x = _rows_view(x)
         n = len(acts)
         # An input width that is not a multiple of 4 floats (DLRM's top MLP reads 27*26/2 + 16 = 367
         # columns) leaves the rows of x and W0 4-byte aligned: the GEMMs would take the unpipelined
         # kernel (55 us instead of 28 for 4096 x 1024 x 367, and no dW + dX pair).  One zero column
         # more on both operands changes no sum and keeps every row 16-byte aligned.
         K0 = wb[0].shape[1]
-        pad = (-K0) % 4 if (K0 >= 64 and _MLP_PAD) else 0
+        pad = _pad_cols(K0)
         W0p = None
         pre_padded = pad > 0 and x.shape[1] == K0 + pad
         if pad:
@@ -1933,8 +1994,7 @@ class _MLPFn(torch.autograd.Function):
         if not head_used:
             if acts[n - 1]:
                 # (a column slice of the gradient of the torch.cat that joins the towers is read in place)
-                dz = ops.mask_mul(dy if dy.stride(-1) == 1 else dy.contiguous(), hs[n],
-                                  torch.empty_like(hs[n]))
+                dz = ops.mask_mul(_unit_cols(dy), hs[n], torch.empty_like(hs[n]))
             else:
                 dz = dy.contiguous()
         for i in range(top, -1, -1):
@@ -2288,8 +2348,7 @@ class _DinAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, K, mask_i32, W1, b1, alpha, W2, b2, mod):
-        if q.stride(-1) != 1:
-            q = q.contiguous()       # a row-strided view (a slot of the gather record) is read in place
+        q = _unit_cols(q)            # (a slot of the gather record)
         B, L, E = K.shape
         out = torch.empty(B, E, dtype=torch.float32, device=q.device)
         stats, a, training, dist, n_total = _din_attn_forward(q, K, mask_i32, W1, b1, alpha, W2, b2,
@@ -2302,8 +2361,7 @@ class _DinAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         q, K, mask_i32, W1, b1, alpha, W2, stats, a = ctx.saved_tensors
         B, L, E = K.shape
-        if dout.stride(-1) != 1:
-            dout = dout.contiguous()     # (a column slice of the tower's input gradient is read in place)
+        dout = _unit_cols(dout)      # (a column slice of the tower's input gradient)
         dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
         dK = torch.empty(B, L, E, dtype=torch.float32, device=q.device)
         dW1, db1, dalpha, dW2, db2 = _din_attn_backward(
@@ -2652,8 +2710,7 @@ class _CrossNetV2Fn(torch.autograd.Function):
         wb, xs, zs = ctx.wb, ctx.xs, ctx.zs
         n = len(wb) // 2
         x0 = xs[0]
-        if dxn.stride(-1) != 1:
-            dxn = dxn.contiguous()         # (a row-strided slice of a cat's gradient is read in place)
+        dxn = _unit_cols(dxn)              # (a row-strided slice of a cat's gradient)
         dx0 = torch.empty_like(x0)
         t = torch.empty_like(x0)
         grads = [None] * (2 * n)
@@ -2752,14 +2809,9 @@ class _CrossDeepFn(torch.autograd.Function):
                 dxn = torch.zeros_like(x0)
             if ddeep is None:
                 ddeep = torch.zeros_like(hs[n_deep])
-            if dxn.stride(-1) != 1:
-                dxn = dxn.contiguous()
-            if ddeep.stride(-1) != 1:
-                ddeep = ddeep.contiguous()
+            dxn, ddeep = _unit_cols(dxn), _unit_cols(ddeep)
         else:
-            dout = douts[0]
-            if dout.stride(-1) != 1:
-                dout = dout.contiguous()
+            dout = _unit_cols(douts[0])
             dxn = dout[:, :D0]                              # row-strided views, read in place
             ddeep = dout[:, D0:]
         note = ctx.relu_note
@@ -2933,14 +2985,6 @@ class MultiHeadSelfAttention(nn.Module):
         return out
 
 
-def _field_view(x):
-    """[B, F, D] as fx_senet_* / fx_bilinear_* read it: unit stride over d, D over the fields, any sample
-    stride (a prefix of the gather record is read in place); anything else is copied."""
-    if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
-        x = x.contiguous()
-    return x
-
-
 class _SENetFn(torch.autograd.Function):
     """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
     three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are
@@ -3053,8 +3097,7 @@ class _FiBiNETMixFn(torch.autograd.Function):
         x, A, (W1, W2, Wp, Wq), (act, kind) = ctx.x, ctx.A, ctx.w, ctx.cfg
         B, F, D = x.shape
         PD = (F * (F - 1) // 2) * D
-        if g.stride(1) != 1:
-            g = g.contiguous()
+        g = _unit_cols(g)
         dev = x.device
         dx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
         dA = torch.empty(B, F, dtype=torch.float32, device=dev)
@@ -3115,14 +3158,6 @@ class BilinearInteractionV2(_BilinearBase):
         self.init_weights()
 
 
-def _rows_view(x):
-    """[rows, n] as the GEMMs and fx_layernorm_* read it in place: unit column stride, 16-byte aligned rows
-    (a prefix of the gather record); anything else is copied."""
-    if x.stride(-1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
-    return x
-
-
 class _LayerNormFn(torch.autograd.Function):
     """torch.nn.LayerNorm over G groups of N columns (+ the ReLU behind it) as ONE autograd node: forward one
     launch, backward three.  `packed` is the [2, G, N] storage that the G per-group weight / bias Parameters in
@@ -3131,8 +3166,7 @@ class _LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, G, N, eps, relu, packed, *params):
-        if x.stride(-1) != 1:
-            x = x.contiguous()
+        x = _unit_cols(x)
         rows = x.shape[0]
         gamma, beta = (packed[0], packed[1]) if packed is not None else (params[0], params[1])
         y = torch.empty(rows, G * N, dtype=torch.float32, device=x.device)
@@ -3147,8 +3181,7 @@ class _LayerNormFn(torch.autograd.Function):
         x, gamma, stats, y = ctx.x, ctx.gamma, ctx.stats, ctx.y
         G, N, relu, is_packed = ctx.cfg
         rows = x.shape[0]
-        if dy.stride(-1) != 1:
-            dy = dy.contiguous()
+        dy = _unit_cols(dy)
         dx = torch.empty(rows, G * N, dtype=torch.float32, device=x.device)
         dgb = torch.empty(2, G, N, dtype=torch.float32, device=x.device)
         ws = _Workspace.get(x.device, ops.layernorm_workspace_floats(rows, G, N), tag="layernorm")
@@ -3187,12 +3220,43 @@ class LayerNorm(nn.Module):
         return y.reshape(*lead, n)
 
 
-class FieldLayerNorm(nn.ModuleList):
+class _PackedViews(object):
+    """Mixin (ahead of nn.Module in the bases) of a layer whose Parameters are views of packed storages: the fused
+    node reads the storages, state_dict / load_state_dict / the dense optimizer see ordinary Parameters.  The class
+    names its storages in `_PACKED` (attributes holding a tensor or a list of tensors) and fills in _bind_views():
+    "Parameter i is this slice of storage k".  Whatever gives the module new tensors ends in _bind_views():
+    .to() / .cuda() / .double() move each storage once, copy.deepcopy and unpickling hand __setstate__ Parameters
+    that are clones (Parameter.__deepcopy__, the pickle of a view) holding the same numbers as the storages' copies.
+    _apply runs nn.Module._apply first, so everything else the module holds (GateCrossLayer's `b`, buffers, any
+    `.grad`) moves as usual; the viewing Parameters are converted there once and then re-pointed (FieldLayerNorm
+    used to skip that step and left their `.grad` behind).
+    Not for the embedding tables' row record (_TableGroup, FeatureEmbeddingDict._bind_views / _apply): a stride-W
+    layout with a weakref owner and optimizer state behind it, which keeps its own code."""
+    _PACKED = ()
+
+    def _bind_views(self):
+        raise NotImplementedError
+
+    def _apply(self, fn, recurse=True):
+        super(_PackedViews, self)._apply(fn, recurse)
+        for name in self._PACKED:
+            held = getattr(self, name)
+            setattr(self, name, [fn(t) for t in held] if isinstance(held, list) else fn(held))
+        self._bind_views()
+        return self
+
+    def __setstate__(self, state):
+        super(_PackedViews, self).__setstate__(state)
+        self._bind_views()
+
+
+class FieldLayerNorm(_PackedViews, nn.ModuleList):
     """MaskNet's `emb_norm` (MaskNet.py:97-99, 116-118): a ModuleList of one LayerNorm(embedding_dim) per field,
     the reference's keys `<i>.weight` / `<i>.bias` of shape [D].  The 2 F Parameters are views of ONE packed
     [2, F, D] storage, as the embedding tables are views of their row record: the kernel reads all fields' affine
     pairs in one grouped launch over the gather record, and state_dict / load_state_dict / the dense optimizer see
     2 F ordinary Parameters."""
+    _PACKED = ("_packed",)
 
     def __init__(self, num_fields, embedding_dim, eps=1e-5):
         ops.layernorm_check(num_fields, embedding_dim, "FieldLayerNorm")
@@ -3208,12 +3272,6 @@ class FieldLayerNorm(nn.ModuleList):
         for i, mod in enumerate(self):
             mod.weight.data = self._packed[0, i]
             mod.bias.data = self._packed[1, i]
-
-    def _apply(self, fn, recurse=True):
-        # nn.Module.to() / cuda(): move the packed storage, then re-point the per-field Parameters at it
-        self._packed = fn(self._packed)
-        self._bind_views()
-        return self
 
     def forward(self, feature_emb):
         """[batch, F, D] (the gather record, read in place) -> [batch, F * D]"""
@@ -3247,12 +3305,9 @@ class _MaskStageFn(torch.autograd.Function):
         B, dev = v_emb.shape[0], v_emb.device
         R, H, O = blocks[0][0].shape[0], blocks[0][2].shape[0], blocks[0][4].shape[0]
 
-        def buf(width):
-            return torch.empty(B, nb * width, dtype=torch.float32, device=dev)
-
         def cols(t, k, width):
             return t[:, k * width:(k + 1) * width] if nb > 1 else t
-        h1, vmask, m, z = buf(R), buf(H), buf(H), buf(O)
+        h1, vmask, m, z = (_empty(B, nb * width, device=dev) for width in (R, H, H, O))
         ops.gemm_batch([ops.gemm_problem(v_emb, blk[0], cols(h1, k, R), transb=True, bias=blk[1], act=1)
                         for k, blk in enumerate(blocks)])
         ops.gemm_batch([ops.gemm_problem(cols(h1, k, R), blk[2], cols(m, k, H), transb=True, bias=blk[3],
@@ -3261,7 +3316,7 @@ class _MaskStageFn(torch.autograd.Function):
                         for k, blk in enumerate(blocks)])
         out, stats = z, None
         if ln:
-            out = buf(O)
+            out = _empty(B, nb * O, device=dev)
             stats = torch.empty(nb, B * 2, dtype=torch.float32, device=dev)
             for k, blk in enumerate(blocks):
                 ops.layernorm_fwd(cols(z, k, O), 1, O, blk[5], blk[6], eps, True, out, stats[k], y_col=k * O)
@@ -3274,8 +3329,7 @@ class _MaskStageFn(torch.autograd.Function):
         v_emb, v_hid, h1, vmask, m, z, out, stats = ctx.kept
         (ln, nb, R, H, O), blocks = ctx.cfg, ctx.blocks
         B, dev = v_emb.shape[0], v_emb.device
-        if dy.stride(-1) != 1:
-            dy = dy.contiguous()
+        dy = _unit_cols(dy)
 
         def cols(t, k, width):
             return t[:, k * width:(k + 1) * width] if nb > 1 else t
@@ -3426,15 +3480,10 @@ class ParallelMaskNet(nn.Module):
 # FinalMLP: feature selection gates and the two-stream aggregation head
 # ------------------------------------------------------------------------------------------------
 # Rows that the gate tower of a FeatureSelection without context features runs on: row 0 is the `ctx_bias`, the rest
-# are zeros.  One row would do; the weight-gradient GEMM sums its bias gradient in the epilogue only when it
-# contracts over more than 8 rows (fx_gemm_f32: "rowsum is not available on the K<=8 / N<=4 skinny paths"), and 9 is
-# the smallest count that does.
+# are zeros.  One row would do, but the weight-gradient GEMM sums its bias gradient in the epilogue only when it
+# contracts over more than 8 rows (_bias_grad); with fewer the bias gradient costs a column-sum launch of its own,
+# and 9 is the smallest count that keeps it in the GEMM.
 _GATE_ROWS = 9
-
-
-def _unit_cols(x):
-    """[rows, n] with unit column stride as fx_gate2_* / fx_biagg_* read it (any row stride, any alignment)."""
-    return x if x.stride(-1) == 1 else x.contiguous()
 
 
 class _FeatureGateFn(torch.autograd.Function):
@@ -3568,11 +3617,8 @@ class _AggregationFn(torch.autograd.Function):
         dy = y.shape[1]
         dev = x.device
         g = dout.contiguous()
-
-        def buf(*shape):
-            return torch.empty(*shape, dtype=torch.float32, device=dev)
-        dT, dY, dXr, dX = buf(B, dy), buf(B, dy), buf(B, dx), buf(B, dx)
-        dwx, dwy, db, dW = buf(1, dx), buf(1, dy), buf(2), buf(H, dxh, dyh)
+        dT, dY, dXr, dX, dwx, dwy, db, dW = (_empty(*shape, device=dev) for shape in (
+            (B, dy), (B, dy), (B, dx), (B, dx), (1, dx), (1, dy), (2,), (H, dxh, dyh)))
         ws = _Workspace.get(dev, ops.biagg_workspace_floats(B, dx, dy), tag="biagg")
         ops.biagg_bwd(g, x, y, T, w_x, w_y, dT, dY, dXr, dwx, dwy, db, ws)
         sk = max(_split_k_for(dxh, dyh, B), 1)
@@ -3663,8 +3709,7 @@ class _GateCrossFn(torch.autograd.Function):
         n = len(packed)
         x0 = xs[0]
         D = x0.shape[1]
-        if dxn.stride(-1) != 1:
-            dxn = dxn.contiguous()         # (a row-strided slice of the head's gradient is read in place)
+        dxn = _unit_cols(dxn)              # (a row-strided slice of the head's gradient)
         dx0 = torch.empty_like(x0)
         dh = torch.empty_like(hs[0])       # one buffer: layer i's GEMMs have read it before layer i - 1 writes it
         grads = [None] * (3 * n)
@@ -3676,13 +3721,14 @@ class _GateCrossFn(torch.autograd.Function):
         return (dxn, None, None) + tuple(grads)
 
 
-class GateCrossLayer(nn.Module):
+class GateCrossLayer(_PackedViews, nn.Module):
     """GDCN.py:175-211 (`GateCorssLayer` there; the alias below keeps that spelling): the reference's keys
     `w.<i>.weight` [D, D], `wg.<i>.weight` [D, D] (neither Linear has a bias) and `b.<i>` [D], b uniform(0, 1).
     w_i and wg_i are views of ONE packed [2D, D] storage per layer (w on top of wg), as FieldLayerNorm's pairs
     are of theirs: one GEMM gives both products, and state_dict / load_state_dict / the dense optimizer see
     ordinary Parameters.  fused=False: module by module as the reference composes it (two FxLinear, torch
     element-wise): the same numbers."""
+    _PACKED = ("_packed",)
 
     def __init__(self, input_dim, cn_layers=3):
         super(GateCrossLayer, self).__init__()
@@ -3709,14 +3755,6 @@ class GateCrossLayer(nn.Module):
             D = p.shape[1]
             self.w[i].weight.data = p[:D]
             self.wg[i].weight.data = p[D:]
-
-    def _apply(self, fn, recurse=True):
-        # nn.Module.to() / cuda(): b and the buffers as always; the packed storages move once and the 2 n weight
-        # Parameters are re-pointed at them
-        super(GateCrossLayer, self)._apply(fn, recurse)
-        self._packed = [fn(p) for p in self._packed]
-        self._bind_views()
-        return self
 
     def forward(self, x, out_into=None):
         """out_into (native extension): see _GateCrossFn; ignored on the module-by-module route."""
@@ -3747,8 +3785,7 @@ class _CrossNetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, out_into, stash, w, b, *params):
-        if x0.stride(-1) != 1:
-            x0 = x0.contiguous()
+        x0 = _unit_cols(x0)
         B, D = x0.shape
         out = out_into if out_into is not None else torch.empty(B, D, dtype=torch.float32, device=x0.device)
         s = torch.empty(B, w.shape[0], dtype=torch.float32, device=x0.device) if stash else None
@@ -3761,8 +3798,7 @@ class _CrossNetFn(torch.autograd.Function):
         x0, w, b, s = ctx.kept
         B, D = x0.shape
         L = w.shape[0]
-        if dout.stride(-1) != 1:
-            dout = dout.contiguous()               # (a row-strided slice of the head's gradient is read in place)
+        dout = _unit_cols(dout)                    # (a row-strided slice of the head's gradient)
         dx0 = torch.empty(B, D, dtype=torch.float32, device=x0.device)
         dw, db = torch.empty_like(w), torch.empty_like(b)
         ws = _Workspace.get(x0.device, ops.cross_net_workspace_floats(B, D, L), tag="crossnet")
@@ -3787,13 +3823,14 @@ class CrossInteraction(nn.Module):
         return self.weight(X_i) * X_0 + self.bias
 
 
-class CrossNet(nn.Module):
+class CrossNet(_PackedViews, nn.Module):
     """cross_net.py:58-92: same constructor, attributes and keys (`cross_net.<i>.weight.weight` [1, D],
     `cross_net.<i>.bias` [D]).  The L weights and the L biases are views of ONE packed [L, D] storage each, as
     GateCrossLayer's pairs are of theirs: the kernels read all layers from two pointers, and state_dict /
     load_state_dict / the dense optimizer see ordinary Parameters.  fused=False, or a shape outside
     ops.cross_net_limits(): module by module as the reference composes it (a Linear to one output, torch
     element-wise): the same numbers."""
+    _PACKED = ("_w", "_b")
 
     def __init__(self, input_dim, num_layers):
         super(CrossNet, self).__init__()
@@ -3812,13 +3849,6 @@ class CrossNet(nn.Module):
         for i, layer in enumerate(self.cross_net):
             layer.weight.weight.data = self._w[i:i + 1]
             layer.bias.data = self._b[i]
-
-    def _apply(self, fn, recurse=True):
-        # nn.Module.to() / cuda(): the packed storages move once and the 2 L Parameters are re-pointed at them
-        super(CrossNet, self)._apply(fn, recurse)
-        self._w, self._b = fn(self._w), fn(self._b)
-        self._bind_views()
-        return self
 
     def native(self, X_0):
         """Whether forward(X_0) runs the fused node (and so honours out_into)."""
@@ -3850,9 +3880,8 @@ class _AFMAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, addend, W1, b1, w2, wp):
-        x = _field_view(x)
         B, F, D = x.shape
-        rows = x.as_strided((B, F * D), (x.stride(0), 1))
+        rows = _field_rows(x)
         out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
         stats = torch.empty(B, 3, dtype=torch.float32, device=x.device)
         if addend is not None:
@@ -3899,9 +3928,8 @@ class _PairFMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, mode, wlin, bias, addend):
-        x = _field_view(x)
         B, F, D = x.shape
-        rows = x.as_strided((B, F * D), (x.stride(0), 1))
+        rows = _field_rows(x)
         out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
         if addend is not None:
             addend = addend.contiguous()
@@ -3957,6 +3985,23 @@ class _SideBySideFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         return None, dout[:, :ctx.Da], dout[:, ctx.Da:]
+
+
+def side_by_side(cross, deep, x, width):
+    """[cross(x) | deep(x)], `width` columns (the `in_features` of the `fc` over both): the cross branch's last
+    launch and the tower's last layer write side by side into one buffer, through their `out_into`.  Joined by
+    torch.cat instead when the tower hands back a tensor of its own: MLP_Block takes out_into only when the whole
+    tower is its fused Linear / ReLU node (no batch_norm, no dropout, ReLU)."""
+    D0 = x.shape[1]
+    buf = torch.empty(x.shape[0], width, dtype=torch.float32, device=x.device)
+    # (two `.data` aliases: each has a version counter of its own, so autograd does not take the tower's write
+    # into the right half for an in-place change of the cross result it already handed out, and vice versa)
+    left, right = buf.data[:, :D0], buf.data[:, D0:]
+    a = cross(x, out_into=left)
+    b = deep(x, out_into=right)
+    if b.data_ptr() == right.data_ptr() and b.stride() == right.stride():
+        return _SideBySideFn.apply(buf, a, b)
+    return torch.cat([a, b], dim=1)
 
 
 def link_fusion(model):

@@ -21,8 +21,9 @@ from torch import nn
 from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
-                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _MLP_PAD, _RecordGradSlot, _SideBySideFn, din_record_layout,
-                     _FMFn, afm_attention, afm_attention_native, pair_interaction, pair_interaction_native)
+                     ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
+                     _FMFn, afm_attention, afm_attention_native, pair_interaction, pair_interaction_native, side_by_side,
+                     tower_pad)
 from . import ops
 from .rank_model import BaseModel
 
@@ -40,6 +41,11 @@ class _ZooModel(BaseModel):
         self.compile(kwargs["optimizer"], kwargs["loss"], learning_rate)
         self.reset_parameters()
         self.model_to_device()
+
+    @staticmethod
+    def _fused_flag(kwargs, env_name):
+        """The model's `fused` keyword; without it the environment switch `env_name` (on unless "0")."""
+        return bool(kwargs.get("fused", _os.environ.get(env_name, "1") != "0"))
 
     def _tower(self, input_dim, units, activations, dropout, batch_norm, output_dim=1,
                output_activation=None):
@@ -277,9 +283,7 @@ class DLRM(_ZooModel):
         assert dense_vec.data_ptr() == dest.data_ptr()
         P = n_slots * (n_slots - 1) // 2
         # the top tower pads an unaligned input width itself (one cat): hand it the padded row instead
-        fused_top = getattr(self.top_mlp, "_fused", None) is not None
-        pad = (-(P + D)) % 4 if (fused_top and P + D >= 64 and _MLP_PAD) else 0
-        return _DlrmMixFn.apply(rec, dense_vec, pad)
+        return _DlrmMixFn.apply(rec, dense_vec, tower_pad(self.top_mlp, P + D))
 
     def forward(self, inputs):
         X = self.get_inputs(inputs)
@@ -375,7 +379,7 @@ class FiBiNET(_ZooModel):
                                hidden_activations, net_dropout, batch_norm)
         # fused=False: the layers one after another, as the reference's class composes them behind
         # patch.install() (V = A * X, the two branch tensors and their cat in memory): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_FIBINET_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_FIBINET_FUSED")
         self._ready(kwargs, learning_rate)
 
     def forward(self, inputs):
@@ -384,8 +388,7 @@ class FiBiNET(_ZooModel):
         if self._fused:
             width = 2 * self.bilinear_interaction1.interact_dim * emb.shape[2]
             # (the tower pads an unaligned input width itself, one cat: hand it the padded rows instead)
-            fused_dnn = getattr(self.dnn, "_fused", None) is not None
-            pad = (-width) % 4 if (fused_dnn and width >= 64 and _MLP_PAD) else 0
+            pad = tower_pad(self.dnn, width)
             excite = self.senet_layer.excitation
             comb = _FiBiNETMixFn.apply(emb, excite[0].weight, excite[2].weight, self.senet_layer._act,
                                        self.bilinear_interaction1.bilinear_W,
@@ -426,7 +429,7 @@ class MaskNet(_ZooModel):
         self.emb_norm = FieldLayerNorm(self.num_fields, embedding_dim) if emb_layernorm else None
         # fused=False: module by module, as the reference's class composes them (one LayerNorm launch per field and
         # their cat, V_mask * V_hidden as a tensor, LayerNorm and ReLU apart): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_MASKNET_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_MASKNET_FUSED")
         self.mask_net.fused = self._fused
         self._ready(kwargs, learning_rate)
 
@@ -465,7 +468,7 @@ class FinalMLP(_ZooModel):
         # fused=False: module by module, as the reference's class composes them (the gate towers on B rows with their
         # Sigmoid, the gates and the gated records as tensors, the head from two Linears and broadcast matmuls): the
         # same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_FINALMLP_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_FINALMLP_FUSED")
         self.fusion_module.fused = self._fused
         if self.use_fs:
             self.fs_module.fused = self._fused
@@ -526,7 +529,7 @@ class GDCN(_ZooModel):
         self.cross_net = GateCrossLayer(width, num_cross_layers)
         # fused=False: module by module, as the reference's class composes it (two Linears per layer, the sigmoid, the
         # products and the sums as tensors): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_GDCN_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_GDCN_FUSED")
         self.cross_net.fused = self._fused
         self._ready(kwargs, learning_rate)
 
@@ -549,7 +552,7 @@ class GDCNP(_ZooModel):
         self.dnn = self._tower(width, units, dnn_activations, net_dropout, batch_norm, output_dim=None)
         self.cross_net = GateCrossLayer(width, num_cross_layers)
         self.fc = FxLinear(units[-1] + width, 1, device=self.device)
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_GDCN_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_GDCN_FUSED")
         self.cross_net.fused = self._fused
         self._ready(kwargs, learning_rate)
 
@@ -559,20 +562,7 @@ class GDCNP(_ZooModel):
         if not self._fused or self.cross_net.cn_layers < 1:
             both = torch.cat([self.cross_net(flat), self.dnn(flat)], dim=1)
         else:
-            # the last cross layer and the tower's last layer write side by side into one [B, D0 + H] buffer
-            D0, H = flat.shape[1], self.fc.in_features - flat.shape[1]
-            buf = torch.empty(flat.shape[0], D0 + H, dtype=torch.float32, device=flat.device)
-            # (two `.data` aliases: each has a version counter of its own, so autograd does not take the tower's write
-            # into the right half for an in-place change of the cross result it already handed out, and vice versa)
-            left, right = buf.data[:, :D0], buf.data[:, D0:]
-            cross = self.cross_net(flat, out_into=left)
-            deep = self.dnn(flat, out_into=right)
-            if deep.data_ptr() == right.data_ptr() and deep.stride() == right.stride():
-                both = _SideBySideFn.apply(buf, cross, deep)
-            else:
-                # MLP_Block takes out_into only when the whole tower is its fused Linear / ReLU node: with batch_norm,
-                # net_dropout > 0 or another activation the tower's result is a tensor of its own and is joined here
-                both = torch.cat([cross, deep], dim=1)
+            both = side_by_side(self.cross_net, self.dnn, flat, self.fc.in_features)
         return {"y_pred": self.output_activation(self.fc(both))}
 
 
@@ -596,7 +586,7 @@ class AFM(_ZooModel):
             lin.__dict__["_fx_head_off"] = True             # none of them ends in the model's logit
         # fused=False: module by module, as the reference's class composes it (the [B, P, D] products, the hidden
         # tensor, the softmax and the weighted sum as tensors): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_AFM_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_AFM_FUSED")
         self._native = afm_attention_native(feature_map.num_fields, embedding_dim, attention_dim)
         self._ready(kwargs, learning_rate)
 
@@ -638,7 +628,7 @@ class DCN(_ZooModel):
         self.fc = FxLinear(width + (units[-1] if units else 0), 1, device=self.device)
         # fused=False: module by module, as the reference's class composes it (per layer a Linear to one output, the
         # product, the two sums as tensors): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_DCN_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_DCN_FUSED")
         self.crossnet.fused = self._fused
         self._ready(kwargs, learning_rate)
 
@@ -650,18 +640,7 @@ class DCN(_ZooModel):
         elif not self.crossnet.native(flat):
             both = torch.cat([self.crossnet(flat), self.dnn(flat)], dim=-1)
         else:
-            # the cross stack and the tower's last layer write side by side into one [B, D0 + H] buffer, as in GDCNP
-            D0, H = flat.shape[1], self.fc.in_features - flat.shape[1]
-            buf = torch.empty(flat.shape[0], D0 + H, dtype=torch.float32, device=flat.device)
-            left, right = buf.data[:, :D0], buf.data[:, D0:]
-            cross = self.crossnet(flat, out_into=left)
-            deep = self.dnn(flat, out_into=right)
-            if deep.data_ptr() == right.data_ptr() and deep.stride() == right.stride():
-                both = _SideBySideFn.apply(buf, cross, deep)
-            else:
-                # MLP_Block takes out_into only when the whole tower is its fused Linear / ReLU node (no batch_norm,
-                # no dropout, ReLU): otherwise its result is a tensor of its own and is joined here
-                both = torch.cat([cross, deep], dim=-1)
+            both = side_by_side(self.crossnet, self.dnn, flat, self.fc.in_features)
         return {"y_pred": self.output_activation(self.fc(both))}
 
 
@@ -689,7 +668,7 @@ class FwFM(_ZooModel):
         self.interaction_weight.__dict__["_fx_head_off"] = True
         # fused=False: module by module, as the reference's class composes it (the [B, P] inner products, the
         # Linear over them, the linear part and the sum as tensors): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_PAIRFM_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_PAIRFM_FUSED")
         self._native = pair_interaction_native(feature_map.num_fields, embedding_dim, "scalar")
         self._ready(kwargs, learning_rate)
 
@@ -741,7 +720,7 @@ class FmFM(_ZooModel):
         self._mode = "vector" if field_interaction_type == "vectorized" else "matrix"
         # fused=False: module by module, as the reference's class composes it (the two [B, P, D] gathers, the batched
         # product, the two sums as tensors): the same numbers
-        self._fused = bool(kwargs.get("fused", _os.environ.get("FX_PAIRFM_FUSED", "1") != "0"))
+        self._fused = self._fused_flag(kwargs, "FX_PAIRFM_FUSED")
         self._native = pair_interaction_native(num_fields, embedding_dim, self._mode)
         self._ready(kwargs, learning_rate)
 
