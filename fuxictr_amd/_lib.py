@@ -64,6 +64,18 @@ class GemmStrategyRecord(C.Structure):
 
 
 # name -> (restype, argtypes).  This table is also what tests/test_abi.py checks against the header.
+class BstInput(C.Structure):
+    """struct fx_bst_input"""
+    _fields_ = [("seq", vp * 3), ("tgt", vp * 3), ("seq_ld", i64 * 3), ("seq_row_ld", i64 * 3), ("tgt_ld", i64 * 3),
+                ("pos", vp), ("n_parts", i32), ("D", i32)]
+
+
+class BstWeights(C.Structure):
+    """struct fx_bst_weights"""
+    _fields_ = [(n, vp) for n in ("in_w", "in_b", "out_w", "out_b", "w1", "b1", "w2", "b2", "ln1_w", "ln1_b",
+                                  "ln2_w", "ln2_b")]
+
+
 SIGNATURES = {
     "fx_abi_version": (i32, []),
     "fx_last_error": (C.c_char_p, []),
@@ -176,6 +188,13 @@ SIGNATURES = {
     "fx_pairfm_workspace_floats": (i64, [i32, i64, i32, i32]),
     "fx_pairfm_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "fx_pairfm_bwd": (i32, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, vp, i64, vp, vp, vp]),
+    "fx_bst_limits": (None, [vp]),
+    "fx_bst_grad_floats": (i64, [i32, i32, i32]),
+    "fx_bst_workspace_floats": (i64, [i64, i32, i32, i32]),
+    "fx_bst_block_fwd": (i32, [C.POINTER(BstInput), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
+                               i32, i32, vp, vp]),
+    "fx_bst_block_bwd": (i32, [C.POINTER(BstInput), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
+                               i32, i32, vp, C.POINTER(BstInput), i32, vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

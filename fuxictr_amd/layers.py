@@ -16,6 +16,7 @@ into libfxctr.so (include/fxctr.h):
 
 torch is used for device memory, streams, nn.Module bookkeeping and the autograd tape only.
 """
+import math
 import os
 from collections import OrderedDict
 from functools import partial  # noqa: F401  (used by eval'ed initializer strings)
@@ -3970,6 +3971,223 @@ def pair_interaction(feature_emb, weight, mode, wlin=None, bias=None, addend=Non
 
 def pair_interaction_native(F, D, mode):
     return mode in ops.PAIRFM_MODES and ops.pairfm_in_envelope(F, D)
+
+
+class _BSTBlockFn(torch.autograd.Function):
+    """One transformer block of BST (BST.py:345-366, with the pooling of BST.py:209-229 behind the last one) as ONE
+    autograd node: forward one launch (ops.bst_block_fwd), backward one launch and the fixed-order reduce of the
+    per-workgroup parameter gradients (ops.bst_block_bwd).  Kept for the backward: the block's inputs (views, no
+    copy) and the ids; Q, K, V, the attention weights and every intermediate are recomputed.
+    Either `x` [B, L1, n * D] (a later block, or a caller that holds the concatenation: its parts are column slices)
+    or n sequence parts [B, L, D] and n target parts [B, D] in `tensors`, read in place; then the 12 parameters
+    in the order of ops.BST_WEIGHTS (None for the LayerNorm ones without layer_norm)."""
+
+    @staticmethod
+    def _parts(x, D, seqs, tgts):
+        if x is None:
+            return list(seqs), list(tgts)
+        L = x.shape[1] - 1
+        n = x.shape[2] // D
+        return ([x[:, :L, i * D:(i + 1) * D] for i in range(n)], [x[:, L, i * D:(i + 1) * D] for i in range(n)])
+
+    @staticmethod
+    def forward(ctx, cfg, ids, pos, x, n_parts, *tensors):
+        H, layer_norm, residual, causal, pool = cfg
+        seqs = [t if t.stride(2) == 1 else t.contiguous() for t in tensors[:n_parts]]
+        tgts = [t if t.stride(1) == 1 else t.contiguous() for t in tensors[n_parts:2 * n_parts]]
+        w = tuple(None if t is None else t.contiguous() for t in tensors[2 * n_parts:])
+        if x is not None:
+            x = x.contiguous()
+            D = pos.shape[1] if pos is not None else x.shape[2]
+        else:
+            D = tgts[0].shape[1]
+        if pos is not None:
+            pos = pos.contiguous()
+        ps, pt = _BSTBlockFn._parts(x, D, seqs, tgts)
+        B, L1 = pt[0].shape[0], ps[0].shape[1] + 1
+        dm = D * (len(pt) + (1 if pos is not None else 0))
+        y = _empty(B, L1, dm, device=pt[0].device) if ops.BST_POOLS[pool] == 0 else _empty(B, dm, device=pt[0].device)
+        ops.bst_block_fwd(ps, pt, pos, ids, w, H, layer_norm, residual, causal, pool, y)
+        # (through save_for_backward: autograd then notices a parameter or input changed in place before the backward)
+        ctx.save_for_backward(x, pos, ids, *(tuple(seqs) + tuple(tgts) + w))
+        ctx.cfg, ctx.shape = cfg, (B, L1, dm, D, n_parts)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, L1, dm, D, n_parts = ctx.shape
+        saved = ctx.saved_tensors
+        x, pos, ids = saved[:3]
+        seqs, tgts, w = list(saved[3:3 + n_parts]), list(saved[3 + n_parts:3 + 2 * n_parts]), saved[3 + 2 * n_parts:]
+        H, layer_norm, residual, causal, pool = ctx.cfg
+        dev = dy.device
+        need = ctx.needs_input_grad          # (cfg, ids, pos, x, n_parts, parts.., parameters..)
+        ps, pt = _BSTBlockFn._parts(x, D, seqs, tgts)
+        if x is not None:
+            dx = torch.empty_like(x) if need[3] else None
+            dseqs, dtgts = _BSTBlockFn._parts(dx, D, (), ()) if need[3] else ([None] * len(pt), [None] * len(pt))
+            dparts = ()
+        else:                                # a part nobody differentiates is not written (a null destination)
+            dx = None
+            dseqs = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + i] else None
+                     for i, t in enumerate(seqs)]
+            dtgts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + n_parts + i] else None
+                     for i, t in enumerate(tgts)]
+            dparts = tuple(dseqs) + tuple(dtgts)
+        pos_D = D if pos is not None else 0
+        grads = torch.empty(ops.bst_grad_floats(L1, dm, pos_D), dtype=torch.float32, device=dev)
+        ws = _Workspace.get(dev, ops.bst_workspace_floats(B, L1, dm, pos_D), tag="bst")
+        ops.bst_block_bwd(ps, pt, pos, ids, w, H, layer_norm, residual, causal, pool, dy.contiguous(), dseqs, dtgts,
+                          grads, ws)
+        DD = dm * dm
+        sizes = (3 * DD, DD, DD, DD, 3 * dm, dm, dm, dm, dm, dm, dm, dm)
+        order = ("in_w", "out_w", "w1", "w2", "in_b", "out_b", "b1", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
+        got, off = {}, 0
+        for name, n in zip(order, sizes):
+            got[name] = grads[off:off + n]
+            off += n
+        # (the kernel forms every parameter gradient in its one launch; a frozen parameter just gets none back)
+        dw = tuple(got[name].view(t.shape) if t is not None and need[5 + 2 * n_parts + k] else None
+                   for k, (name, t) in enumerate(zip(ops.BST_WEIGHTS, w)))
+        dpos = grads[off:].view(L1, D) if pos is not None and need[2] else None
+        return (None, None, dpos, dx, None) + dparts + dw
+
+
+class _Params(nn.Module):
+    """A container of Parameters under the reference's names; nothing to call (nn.Module.forward raises)."""
+
+
+class TransformerBlock(nn.Module):
+    """BST's transformer block (model_zoo/BST/src/BST.py:317-366): same constructor, same state_dict keys
+    (`attention.in_proj_weight`, `attention.in_proj_bias`, `attention.out_proj.weight|bias`, `ffn.0|2.weight|bias`,
+    `layer_norm1|2.weight|bias`); the arithmetic is fx_bst_block_*.  `attention` holds torch.nn.MultiheadAttention's
+    parameters with its default initialisation and has no forward of its own."""
+
+    def __init__(self, model_dim=64, ffn_dim=64, num_heads=8, attn_dropout=0.0, net_dropout=0.0,
+                 layer_norm=True, use_residual=True):
+        super(TransformerBlock, self).__init__()
+        if attn_dropout > 0 or net_dropout > 0:
+            raise NotImplementedError("TransformerBlock(attn_dropout > 0 or net_dropout > 0): dropout inside the "
+                                      "transformer is outside the fused kernel's scope")
+        if ffn_dim != model_dim:
+            raise NotImplementedError("TransformerBlock: ffn_dim={} != model_dim={}, the fused kernel keeps one "
+                                      "width".format(ffn_dim, model_dim))
+        ops.bst_check(1, model_dim, num_heads, who="TransformerBlock")
+        dev = _alloc_device()
+        self.model_dim, self.num_heads = model_dim, num_heads
+        self.use_residual = bool(use_residual)
+        att = _Params()
+        att.in_proj_weight = nn.Parameter(torch.empty(3 * model_dim, model_dim, device=dev))
+        att.in_proj_bias = nn.Parameter(torch.zeros(3 * model_dim, device=dev))
+        att.out_proj = _Params()
+        att.out_proj.weight = nn.Parameter(torch.empty(model_dim, model_dim, device=dev))
+        att.out_proj.bias = nn.Parameter(torch.zeros(model_dim, device=dev))
+        nn.init.xavier_uniform_(att.in_proj_weight)
+        nn.init.kaiming_uniform_(att.out_proj.weight, a=5 ** 0.5)
+        self.attention = att
+        self.ffn = nn.Sequential(nn.Linear(model_dim, ffn_dim, device=dev), nn.LeakyReLU(),
+                                 nn.Linear(ffn_dim, model_dim, device=dev))
+        self.layer_norm1 = nn.LayerNorm(model_dim, device=dev) if layer_norm else None
+        self.layer_norm2 = nn.LayerNorm(model_dim, device=dev) if layer_norm else None
+
+    def _weights(self):
+        ln1, ln2 = self.layer_norm1, self.layer_norm2
+        return (self.attention.in_proj_weight, self.attention.in_proj_bias, self.attention.out_proj.weight,
+                self.attention.out_proj.bias, self.ffn[0].weight, self.ffn[0].bias, self.ffn[2].weight,
+                self.ffn[2].bias, ln1.weight if ln1 is not None else None, ln1.bias if ln1 is not None else None,
+                ln2.weight if ln2 is not None else None, ln2.bias if ln2 is not None else None)
+
+    def _cfg(self, causal, pool):
+        if pool not in ops.BST_POOLS:
+            raise ValueError("seq_pooling_type={} not supported.".format(pool))
+        return (self.num_heads, self.layer_norm1 is not None, self.use_residual, bool(causal), pool)
+
+    def forward(self, x, attn_mask=None, ids=None, causal=False, pool="none"):
+        """x [B, L1, model_dim]; ids: int32 [B, L1 - 1] of the history (0 = padding) or None.  The masks are built
+        in the kernel from `ids` and `causal` (BST.py:183-207), so a materialised attn_mask is not taken."""
+        if attn_mask is not None:
+            raise NotImplementedError("TransformerBlock: a materialised attn_mask is not taken; pass ids= and causal=")
+        if x.dim() != 3 or x.shape[2] != self.model_dim:
+            raise NotImplementedError("TransformerBlock: input {}, built for [batch, positions, {}]".format(
+                tuple(x.shape), self.model_dim))
+        ops.bst_check(x.shape[1], self.model_dim, self.num_heads, who="TransformerBlock")
+        return _BSTBlockFn.apply(self._cfg(causal, pool), ids, None, x, 0, *self._weights())
+
+
+class BehaviorTransformer(nn.Module):
+    """BST's stack of transformer blocks over [history | target] with the trained position embedding concatenated
+    per position (BST.py:248-314): same constructor, keys `transformer_blocks.N.*` and `position_emb`, the same
+    sinusoid from reset_parameters.  The first block assembles its input in LDS from the parts (no torch.cat of
+    [B, L1, dm]); the pooling over positions (BST.py:209-229) rides in the last block's launches."""
+
+    def __init__(self, seq_len=1, model_dim=64, num_heads=8, stacked_transformer_layers=1, attn_dropout=0.0,
+                 net_dropout=0.0, use_position_emb=True, position_dim=4, layer_norm=True, use_residual=True):
+        super(BehaviorTransformer, self).__init__()
+        ops.bst_check(seq_len, model_dim, num_heads, position_dim if use_position_emb else None,
+                      who="BehaviorTransformer")
+        if stacked_transformer_layers < 1:
+            raise ValueError("BehaviorTransformer: stacked_transformer_layers={}".format(stacked_transformer_layers))
+        self.seq_len, self.model_dim = seq_len, model_dim
+        self.position_dim = position_dim
+        self.use_position_emb = use_position_emb
+        self.transformer_blocks = nn.ModuleList(
+            TransformerBlock(model_dim=model_dim, ffn_dim=model_dim, num_heads=num_heads, attn_dropout=attn_dropout,
+                             net_dropout=net_dropout, layer_norm=layer_norm, use_residual=use_residual)
+            for _ in range(stacked_transformer_layers))
+        if self.use_position_emb:
+            self.position_emb = nn.Parameter(torch.empty(seq_len, position_dim, device=_alloc_device()))
+            self.reset_parameters()
+
+    def reset_parameters(self):
+        seq_len = self.position_emb.size(0)
+        pe = torch.zeros(seq_len, self.position_dim)
+        position = torch.arange(0, seq_len).float().unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, self.position_dim, 2).float()
+                             * (-math.log(10000.0) / self.position_dim))
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term)
+        self.position_emb.data = pe.to(self.position_emb.device)
+
+    def _run(self, x, seqs, tgts, ids, causal, pool):
+        blocks = self.transformer_blocks
+        pos = self.position_emb if self.use_position_emb else None
+        for i, blk in enumerate(blocks):
+            cfg = blk._cfg(causal, pool if i == len(blocks) - 1 else "none")
+            if i == 0:
+                x = _BSTBlockFn.apply(cfg, ids, pos, x, len(tgts), *(tuple(seqs) + tuple(tgts) + blk._weights()))
+            else:
+                x = _BSTBlockFn.apply(cfg, ids, None, x, 0, *blk._weights())
+        return x.flatten(start_dim=1) if pool == "concat" else x
+
+    def forward_parts(self, seqs, tgts, ids=None, causal=False, pool="none"):
+        """seqs[i] [B, L, D], tgts[i] [B, D]: the embedded history and target of each field (views of the gather
+        record are read in place), D = position_dim; ids: int32 [B, L] of the first history field (0 = padding)."""
+        n, D = len(tgts), tgts[0].shape[-1]
+        if n != len(seqs) or not 1 <= n <= ops.BST_MAX_PARTS or any(t.shape[-1] != D for t in list(seqs) + list(tgts)):
+            raise NotImplementedError("BehaviorTransformer: {} sequence / {} target parts, the fused kernel takes 1 "
+                                      "to {} pairs of one width".format(len(seqs), n, ops.BST_MAX_PARTS))
+        if D * (n + int(self.use_position_emb)) != self.model_dim or seqs[0].shape[1] + 1 != self.seq_len \
+                or (self.use_position_emb and D != self.position_dim):
+            raise NotImplementedError("BehaviorTransformer: parts {} x [{} + 1, {}], built for seq_len {} and "
+                                      "model_dim {}".format(n, seqs[0].shape[1], D, self.seq_len, self.model_dim))
+        return self._run(None, seqs, tgts, ids, causal, pool)
+
+    def forward(self, x, attn_mask=None, ids=None, causal=False, pool="none"):
+        """x [B, seq_len, model_dim - position_dim]: the concatenated [history | target] embeddings (BST.py:170)."""
+        if attn_mask is not None:
+            raise NotImplementedError("BehaviorTransformer: a materialised attn_mask is not taken; pass ids= and "
+                                      "causal=")
+        width = self.model_dim - (self.position_dim if self.use_position_emb else 0)
+        if x.dim() != 3 or x.shape[1] != self.seq_len or x.shape[2] != width:
+            raise NotImplementedError("BehaviorTransformer: input {}, built for [batch, {}, {}]".format(
+                tuple(x.shape), self.seq_len, width))
+        if self.use_position_emb:
+            ops.bst_check(self.seq_len, self.model_dim, self.transformer_blocks[0].num_heads, self.position_dim,
+                          who="BehaviorTransformer")
+            if width % self.position_dim or not 1 <= width // self.position_dim <= ops.BST_MAX_PARTS:
+                raise NotImplementedError("BehaviorTransformer: input width {} is not 1 to {} parts of position_dim "
+                                          "{}".format(width, ops.BST_MAX_PARTS, self.position_dim))
+        return self._run(x, (), (), ids, causal, pool)
 
 
 class _SideBySideFn(torch.autograd.Function):

@@ -1600,6 +1600,152 @@ def pairfm_bwd(g, rec, F, D, mode, W, wlin, has_bias, drec, grads, workspace):
     return drec, grads
 
 
+# ---- BST: one fused transformer block over the positions of a sample --------------------------------
+BST_MAX = 64         # L1 = history + target positions, and dm of fx_bst_block_*
+BST_MAX_PARTS = 3
+BST_POOLS = {"none": 0, "concat": 0, "mean": 1, "sum": 2, "target": 3}
+# the order of fx_bst_weights and of the parameter gradients' matrices / vectors
+BST_WEIGHTS = ("in_w", "in_b", "out_w", "out_b", "w1", "b1", "w2", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
+
+
+def bst_check(L1, dm, H, D=None, who="bst"):
+    """The limits of fx_bst_block_*, raised here before anything is launched."""
+    if not 1 <= L1 <= BST_MAX:
+        raise NotImplementedError("{}: L1={} (history + target), the kernel's limit is 1 <= L1 <= {}"
+                                  .format(who, L1, BST_MAX))
+    if not 1 <= dm <= BST_MAX:
+        raise NotImplementedError("{}: dm={}, the kernel's limit is 1 <= dm <= {}".format(who, dm, BST_MAX))
+    if H < 1 or dm % H:
+        raise NotImplementedError("{}: H={} does not divide dm={}".format(who, H, dm))
+    if D is not None and (D < 1 or dm % D or dm // D > BST_MAX_PARTS + 1):
+        raise NotImplementedError("{}: D={} must divide dm={} at most {} times".format(who, D, dm,
+                                                                                       BST_MAX_PARTS + 1))
+
+
+def bst_limits():
+    """(most L1, most dm, forward grid, backward grid) of fx_bst_block_*."""
+    lim = (C.c_int32 * 4)()
+    _lib.load().fx_bst_limits(lim)
+    return tuple(int(v) for v in lim)
+
+
+def bst_grad_floats(L1, dm, pos_D):
+    """grads of bst_block_bwd: [d in_w (3 dm dm) | d out_w | d w1 | d w2 (dm dm each) | d in_b (3 dm) | d out_b |
+    d b1 | d b2 | d ln1_w | d ln1_b | d ln2_w | d ln2_b (dm each) | d position_emb (L1 * pos_D)]."""
+    return 6 * dm * dm + 10 * dm + L1 * pos_D
+
+
+def bst_workspace_floats(B, L1, dm, pos_D):
+    return int(_lib.load().fx_bst_workspace_floats(B, L1, dm, pos_D))
+
+
+def bst_flops(B, L1, dm, backward=False):
+    """fp32 flops of one block: forward 2 L1 dm (6 dm + 2 L1) per sample (three projections, scores, P V, the output
+    projection, two FFN layers); the backward runs that again and adds 2 L1 dm (15 dm + 5 L1): Q, K, V and the
+    scores a second time, dP, dV, dQ, dK, four dX products over the weights and six weight gradients."""
+    fwd = 2.0 * L1 * dm * (6 * dm + 2 * L1)
+    return B * (fwd + 2.0 * L1 * dm * (15 * dm + 5 * L1) if backward else fwd)
+
+
+def _bst_input(seqs, tgts, pos, who):
+    n = len(tgts)
+    assert 1 <= n <= BST_MAX_PARTS and len(seqs) == n, who
+    d = _lib.BstInput()
+    D = next((t.shape[-1] for t in list(tgts) + list(seqs) if t is not None), 1)
+    for i, (s, t) in enumerate(zip(seqs, tgts)):
+        if t is not None:
+            assert t.dim() == 2 and t.shape[1] == D and t.stride(1) == 1 and t.dtype == torch.float32, who
+            d.tgt[i], d.tgt_ld[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else D)
+        if s is not None and s.shape[1] > 0:
+            assert s.dim() == 3 and s.shape[2] == D and s.stride(2) == 1 and s.dtype == torch.float32, who
+            d.seq[i] = s.data_ptr()
+            d.seq_row_ld[i] = s.stride(1) if s.shape[1] > 1 else D
+            d.seq_ld[i] = s.stride(0) if s.shape[0] > 1 else s.shape[1] * d.seq_row_ld[i]
+    if pos is not None:
+        assert pos.is_contiguous() and pos.shape[1] == D and pos.dtype == torch.float32, who
+        d.pos = pos.data_ptr()
+    d.n_parts, d.D = n, D
+    return d
+
+
+def _bst_weights(w):
+    s = _lib.BstWeights()
+    for name, t in zip(BST_WEIGHTS, w):
+        if t is not None:
+            assert t.is_contiguous() and t.dtype == torch.float32, name
+            setattr(s, name, t.data_ptr())
+    return s
+
+
+def _bst_shape(seqs, tgts, pos):
+    B, D = tgts[0].shape
+    L1 = (seqs[0].shape[1] if seqs[0] is not None else 0) + 1
+    return B, L1, D * (len(tgts) + (1 if pos is not None else 0)), D
+
+
+def _bst_ids(ids, B, L1):
+    if ids is None:
+        return vp(0), 0
+    assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L1 - 1) and (L1 == 1 or ids.stride(1) == 1)
+    return ptr(ids), (ids.stride(0) if B > 1 else L1 - 1)
+
+
+def _bst_bytes_fwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool, Y):
+    B, L1, dm, D = _bst_shape(seqs, tgts, pos)
+    return 4.0 * (B * L1 * len(tgts) * D + (B * (L1 - 1) if ids is not None else 0) + Y.numel()
+                  + 6 * dm * dm + 10 * dm)
+
+
+def _bst_bytes_bwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool, dY, *a, **kw):
+    B, L1, dm, D = _bst_shape(seqs, tgts, pos)
+    G = min(B, bst_limits()[3])
+    n = bst_grad_floats(L1, dm, D if pos is not None else 0)
+    return 4.0 * (2 * B * L1 * len(tgts) * D + (B * (L1 - 1) if ids is not None else 0) + dY.numel()
+                  + 6 * dm * dm + 10 * dm + 2 * G * n)
+
+
+@_timed("bst_block_fwd", "bst", _bst_bytes_fwd)
+def bst_block_fwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool, Y):
+    """One transformer block.  seqs[i] [B, L, D] / tgts[i] [B, D]: part i of the history positions and of the target
+    (views with unit stride over D are read in place; a later block passes x[:, :L] and x[:, L] of its [B, L1, dm]
+    input), pos: position_emb [L1, D] or None, ids: int32 [B, L] of the first sequence field (0 = padding) or None,
+    w: the 12 tensors of BST_WEIGHTS (the LayerNorm ones None without layer_norm), pool: a key of BST_POOLS.
+    Y: [B, L1, dm] ("none" / "concat") or [B, dm], contiguous."""
+    _need_cuda(Y, "Y")
+    B, L1, dm, D = _bst_shape(seqs, tgts, pos)
+    bst_check(L1, dm, H, D)
+    assert Y.is_contiguous() and Y.numel() == (B * L1 * dm if BST_POOLS[pool] == 0 else B * dm)
+    ip, iw = _bst_ids(ids, B, L1)
+    check(_lib.load().fx_bst_block_fwd(C.byref(_bst_input(seqs, tgts, pos, "bst_block_fwd")), ip, iw, B, L1, dm, H,
+                                       C.byref(_bst_weights(w)), 1 if layer_norm else 0, 1 if residual else 0,
+                                       1 if causal else 0, BST_POOLS[pool], ptr(Y), stream_ptr(Y.device)),
+          "fx_bst_block_fwd")
+    return Y
+
+
+@_timed("bst_block_bwd", "bst", _bst_bytes_bwd)
+def bst_block_bwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool, dY, dseqs, dtgts, grads, workspace,
+                  dx_accumulate=False):
+    """From dY (the shape of Y): the parts' gradients into dseqs[i] / dtgts[i] (the shapes of seqs / tgts, own
+    strides; None: not wanted; added to when dx_accumulate) and grads [bst_grad_floats(..)].  workspace:
+    bst_workspace_floats(B, L1, dm, pos_D) floats."""
+    _need_cuda(dY, "dY")
+    B, L1, dm, D = _bst_shape(seqs, tgts, pos)
+    bst_check(L1, dm, H, D)
+    pos_D = D if pos is not None else 0
+    assert dY.is_contiguous() and dY.numel() == (B * L1 * dm if BST_POOLS[pool] == 0 else B * dm)
+    assert grads.is_contiguous() and grads.numel() == bst_grad_floats(L1, dm, pos_D)
+    assert workspace.is_contiguous() and workspace.numel() >= bst_workspace_floats(B, L1, dm, pos_D)
+    ip, iw = _bst_ids(ids, B, L1)
+    din = _bst_input(dseqs, dtgts, None, "bst_block_bwd")
+    check(_lib.load().fx_bst_block_bwd(C.byref(_bst_input(seqs, tgts, pos, "bst_block_bwd")), ip, iw, B, L1, dm, H,
+                                       C.byref(_bst_weights(w)), 1 if layer_norm else 0, 1 if residual else 0,
+                                       1 if causal else 0, BST_POOLS[pool], ptr(dY), C.byref(din),
+                                       1 if dx_accumulate else 0, ptr(grads), ptr(workspace),
+                                       stream_ptr(dY.device)), "fx_bst_block_bwd")
+    return grads
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM and FmFM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM and BST, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -8,7 +8,8 @@ model_zoo/MaskNet/src/MaskNet.py:51-123,
 model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-101,
 model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96,
 model_zoo/DCN/DCN_torch/src/DCN.py:24-101, model_zoo/FwFM/src/FwFM.py:24-91,
-model_zoo/FmFM/src/FmFM.py:25-94), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/FmFM/src/FmFM.py:25-94,
+model_zoo/BST/src/BST.py:33-366), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -18,7 +19,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (BehaviorTransformer, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -741,3 +742,73 @@ class FmFM(_ZooModel):
         y_pred = (left_emb * right_emb).sum(dim=-1).sum(dim=-1, keepdim=True)
         y_pred = y_pred + self.lr_layer(X)
         return {"y_pred": self.output_activation(y_pred)}
+
+
+class BST(_ZooModel):
+    """Behavior Sequence Transformer (BST.py:33-245): per (target, sequence) pair a stack of transformer blocks over
+    [history | target] with a trained position embedding, pooled over the positions, next to the other fields'
+    embeddings in front of the DNN.  Each block is one fused launch per direction (layers.BehaviorTransformer)."""
+
+    def __init__(self, feature_map, model_id="BST", gpu=-1, dnn_hidden_units=[256, 128, 64], dnn_activations="ReLU",
+                 num_heads=2, stacked_transformer_layers=1, attention_dropout=0, learning_rate=1e-3, embedding_dim=10,
+                 net_dropout=0, batch_norm=False, layer_norm=True, use_residual=True,
+                 bst_target_field=[("item_id", "cate_id")], bst_sequence_field=[("click_history", "cate_history")],
+                 seq_pooling_type="mean", use_position_emb=True, use_causal_mask=False, embedding_regularizer=None,
+                 net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        targets = bst_target_field if isinstance(bst_target_field, list) else [bst_target_field]
+        sequences = bst_sequence_field if isinstance(bst_sequence_field, list) else [bst_sequence_field]
+        assert len(targets) == len(sequences), "len(self.bst_target_field) != len(self.bst_sequence_field)"
+        self.bst_target_field = [tuple(f) if isinstance(f, list) else f for f in targets]
+        self.bst_sequence_field = [tuple(f) if isinstance(f, list) else f for f in sequences]
+        if seq_pooling_type not in ("mean", "sum", "target", "concat"):
+            raise ValueError("seq_pooling_type={} not supported.".format(seq_pooling_type))
+        self.use_causal_mask = use_causal_mask
+        self.seq_pooling_type = seq_pooling_type
+        self.feature_map = feature_map
+        self.embedding_dim = embedding_dim
+        self.num_heads = num_heads
+        self.embedding_layer = FeatureEmbeddingDict(feature_map, embedding_dim)
+        self.transformer_encoders = nn.ModuleList()
+        seq_out_dim = 0
+        for sequence_field in self.bst_sequence_field:
+            names = _fields(sequence_field)
+            model_dim = embedding_dim * (int(use_position_emb) + len(names))      # the position emb is concatenated
+            seq_len = feature_map.features[names[0]]["max_len"] + 1                # + the target item
+            seq_out_dim += self.get_seq_out_dim(model_dim, seq_len, sequence_field, embedding_dim)
+            self.transformer_encoders.append(
+                BehaviorTransformer(seq_len=seq_len, model_dim=model_dim, num_heads=num_heads,
+                                    stacked_transformer_layers=stacked_transformer_layers,
+                                    attn_dropout=attention_dropout, net_dropout=net_dropout,
+                                    position_dim=embedding_dim, use_position_emb=use_position_emb,
+                                    layer_norm=layer_norm, use_residual=use_residual))
+        self.dnn = self._tower(feature_map.sum_emb_out_dim() + seq_out_dim, dnn_hidden_units, dnn_activations,
+                               net_dropout, batch_norm, output_activation=self.output_activation)
+        self._ready(kwargs, learning_rate)
+
+    def get_seq_out_dim(self, model_dim, seq_len, sequence_field, embedding_dim):
+        num_seq_field = len(sequence_field) if type(sequence_field) == tuple else 1
+        if self.seq_pooling_type == "concat":
+            return seq_len * model_dim - num_seq_field * embedding_dim
+        return model_dim - num_seq_field * embedding_dim
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # name -> [B, D] | [B, L, D]
+        pooled, dropped = [], set()
+        for encoder, target, sequence in zip(self.transformer_encoders, self.bst_target_field,
+                                             self.bst_sequence_field):
+            seq_names = _fields(sequence)
+            # padding_idx 0 marks the empty positions (BST.py:193 on the FIRST sequence field); the packed int32 id
+            # columns themselves are the mask: no cast / compare / [B * H, L1, L1] tensor
+            ids = self.embedding_layer.packed_ids(X, seq_names[0])
+            if ids is None:
+                ids = (X[seq_names[0]].long() != 0).to(torch.int32).contiguous()
+            pooled.append(encoder.forward_parts([emb[f] for f in seq_names], [emb[f] for f in _fields(target)],
+                                                ids=ids, causal=self.use_causal_mask, pool=self.seq_pooling_type))
+            dropped.update(seq_names)
+        # the other fields in the feature map's order, which is the order the reference's loaders hand the batch in
+        # (BST.py:178 follows the batch dict's own order; a captured step's static batch is ordered by packed matrix,
+        # so the dict's order is nothing to build the DNN's input on)
+        rest = [emb[f] for f in self.feature_map.features if f in emb and f not in dropped]
+        return {"y_pred": self.dnn(torch.cat(rest + pooled, dim=-1))}

@@ -966,6 +966,58 @@ int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_
                   float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * BST (csrc/fx_bst.hip): one transformer block of the Behavior Sequence Transformer over the L1 = L + 1 positions
+ * of a sample (the history's L positions, then the target), fused (model_zoo/BST/src/BST.py:317-366; the masks of
+ * BST.py:183-207, the pooling of BST.py:209-229; torch.nn.MultiheadAttention's packed in_proj):
+ *     X    = [part 0 | .. | part n_parts-1 | pos]   per position, dm = (n_parts + (pos != NULL)) * D columns
+ *     QKV  = X in_w^T + in_b                         in_w [3 dm, dm], in_b [3 dm]
+ *     P_h  = softmax_rows(Q_h K_h^T / sqrt(dm / H)), score(i, j) = -inf where masked(i, j)
+ *     s    = concat_h(P_h V_h) out_w^T + out_b (+ X when residual);   s = LN1(s) when layer_norm (eps 1e-5)
+ *     out  = w2 LeakyReLU_0.01(w1 s + b1) + b2 (+ s when residual);   out = LN2(out) when layer_norm
+ *     masked(i, j) = (pad[j] and i != j) or (causal and j > i);  pad[j] = (ids[b, j] == 0) for j < L, pad[L] = 0
+ *   The diagonal is always open: an all-padding history is legal and gives finite numbers.
+ *   fx_bst_input: part i of position f < L is seq[i] + b * seq_ld[i] + f * seq_row_ld[i], of the target
+ *   tgt[i] + b * tgt_ld[i], D floats each (views into the gather record are read in place); pos (nullable) is
+ *   position_emb [L1, D].  A later block takes its [B, L1, dm] input as one part of D = dm.
+ *   pool: 0 none: Y [B, L1, dm] (also BST's "concat");  1 mean over the unpadded positions (sum / (count + 1e-12));
+ *   2 sum over them;  3 target (row L): Y [B, dm] (BST.py:219-227).
+ *   fx_bst_block_fwd : one launch.  Neither Q / K / V nor scores nor any intermediate reaches memory.
+ *   fx_bst_block_bwd : from dY (the shape of Y) one launch that recomputes the forward and writes the parts'
+ *                     gradients through `din` (the same description; a NULL pointer: not wanted; added to when
+ *                     dx_accumulate), the per-workgroup rows of the parameter gradients into `workspace`, then
+ *                     fx_colsum over the rows: grads = [d in_w | d out_w | d w1 | d w2 | d in_b | d out_b | d b1 |
+ *                     d b2 | d ln1_w | d ln1_b | d ln2_w | d ln2_b | d pos (L1 * D, when pos)]
+ *                     (fx_bst_grad_floats; the LayerNorm entries are 0 without layer_norm).
+ *   No atomics: two runs give the same bits.  fp32.
+ *   Limits: 1 <= L1 <= 64, 1 <= dm <= 64, H divides dm, D divides dm at most 4 times, ffn width = dm.
+ *   fx_bst_limits : limits[4] = {most L1, most dm, forward grid, backward grid} (housekeeping).
+ *   fx_bst_workspace_floats : floats of fx_bst_block_bwd's workspace, pos_D = D with pos, else 0 (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fx_bst_input {
+    const float* seq[3];
+    const float* tgt[3];
+    int64_t seq_ld[3];
+    int64_t seq_row_ld[3];
+    int64_t tgt_ld[3];
+    const float* pos;
+    int32_t n_parts;
+    int32_t D;
+} fx_bst_input;
+typedef struct fx_bst_weights {
+    const float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+} fx_bst_weights;
+void fx_bst_limits(int32_t* limits);
+int64_t fx_bst_grad_floats(int32_t L1, int32_t dm, int32_t pos_D);
+int64_t fx_bst_workspace_floats(int64_t B, int32_t L1, int32_t dm, int32_t pos_D);
+int fx_bst_block_fwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
+                     int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual, int32_t causal,
+                     int32_t pool, float* Y, fx_stream_t stream);
+int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
+                     int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual, int32_t causal,
+                     int32_t pool, const float* dY, const fx_bst_input* din, int32_t dx_accumulate, float* grads,
+                     float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with

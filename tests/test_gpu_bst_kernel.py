@@ -1,0 +1,309 @@
+"""fx_bst_block_fwd / fx_bst_block_bwd alone, through ops, on a real MI355X against an fp64 torch-autograd restatement
+of the block's formulas (test_bst_host.bst_block; no nn.MultiheadAttention anywhere).
+
+Yardstick (that of tests/test_gpu_mhsa.py): per compared tensor e32 = max |the same block in fp32 torch on the CPU -
+fp64|; the HIP result must lie within 4 * e32 + 1e-6 * max|ref|.  The observed ratio err / bound is printed per tensor.
+
+The LeakyReLU's kink: a sample whose fp64 FFN pre-activation has an element within 1e-5 of zero gets an all-zero
+upstream gradient (samples are independent, so it drops out of every gradient); at most 10 % of a case's samples may
+go that way, which is asserted.  Measured on the CPU (fp64 reference alone) when this file was written, default-like
+initialisation and inputs of std 0.5: 0 to 3 of 33 samples at L1 = 51, dm = 48 (4 % on average over the five flag
+sets), 0 to 2 of 1027 at L1 = 3, dm = 8, and 0 or 1 of 7 at L1 = dm = 64, where one sample is already over the cap.
+After LayerNorm the pre-activation's scale does not follow the input's, so the inputs are fixed by SEEDS instead: one
+seed per shape, picked once on the CPU as the first of 100 + shape, + 10, .. whose fp64 reference is under the cap for
+all five flag sets (only L1 = dm = 64 needed a second and third try)."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from fuxictr_amd import _lib, ops  # noqa: E402
+from test_bst_host import bst_block  # noqa: E402
+
+NAMES = ops.BST_WEIGHTS
+FLAGS = [  # (layer_norm, residual, causal, pool): LN x residual all four ways, causal on and off, every pooling
+    (True, True, False, "mean"), (True, False, True, "sum"), (False, True, True, "target"),
+    (False, False, False, "concat"), (True, True, True, "none")]
+
+
+def make_ids(B, L, rng):
+    """Per sample, in turn: all padded, none padded, padding at the front, at the back, interleaved."""
+    ids = rng.integers(1, 50, size=(B, L)).astype(np.int32)
+    for b in range(B):
+        kind = b % 5
+        if kind == 0:
+            ids[b, :] = 0
+        elif kind == 2:
+            ids[b, :max(1, L // 3)] = 0
+        elif kind == 3:
+            ids[b, L - max(1, L // 3):] = 0
+        elif kind == 4:
+            ids[b, ::2] = 0
+    return torch.from_numpy(ids)
+
+
+def make_case(B, L, n_parts, D, H, pos, layer_norm, seed, x_scale=0.5, w_scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    dm = D * (n_parts + int(pos))
+    L1 = L + 1
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(*shape, generator=g, dtype=torch.float64) * s)
+    seqs = [rnd(B, L, D, s=x_scale) for _ in range(n_parts)]
+    tgts = [rnd(B, D, s=x_scale) for _ in range(n_parts)]
+    P = rnd(L1, D, s=0.7) if pos else None
+    u = 1.0 / dm ** 0.5
+    w = [rnd(3 * dm, dm, s=w_scale * (2.0 / (4 * dm)) ** 0.5), rnd(3 * dm, s=0.1), rnd(dm, dm, s=w_scale * u),
+         rnd(dm, s=0.1), rnd(dm, dm, s=u), rnd(dm, s=0.1), rnd(dm, dm, s=u), rnd(dm, s=0.1)]
+    w += [1.0 + rnd(dm, s=0.1), rnd(dm, s=0.1), 1.0 + rnd(dm, s=0.1), rnd(dm, s=0.1)] if layer_norm else [None] * 4
+    ids = make_ids(B, L, np.random.default_rng(seed))
+    return seqs, tgts, P, ids, w, (B, L1, dm, D)
+
+
+def reference(case, H, flags, dtype, gy=None):
+    """-> (Y, grads dict, upstream gradient, dropped samples) of the block in `dtype` torch on the CPU."""
+    seqs, tgts, P, ids, w, (B, L1, dm, D) = case
+    ln, res, causal, pool = flags
+
+    def leaf(t):
+        return None if t is None else t.to(dtype).clone().requires_grad_(True)
+    ls, lt, lw, lp = [leaf(t) for t in seqs], [leaf(t) for t in tgts], [leaf(t) for t in w], leaf(P)
+    pre = []
+    y = bst_block(ls, lt, lp, ids, lw, H, ln, res, causal, pool, ffn_pre=pre)
+    dropped = 0
+    if gy is None:
+        gen = torch.Generator().manual_seed(99)
+        gy = torch.randn(y.shape, generator=gen, dtype=torch.float64)
+        near = (pre[0].abs() < 1e-5).reshape(B, -1).any(dim=1)
+        gy[near] = 0.0
+        dropped = int(near.sum())
+    wanted = {"seq%d" % i: t for i, t in enumerate(ls) if t.numel()}
+    wanted.update({"tgt%d" % i: t for i, t in enumerate(lt)})
+    wanted.update({n: t for n, t in zip(NAMES, lw) if t is not None})
+    if lp is not None:
+        wanted["pos"] = lp
+    got = torch.autograd.grad(y, list(wanted.values()), gy.to(dtype))
+    return y.detach(), dict(zip(wanted.keys(), [t.detach() for t in got])), gy, dropped
+
+
+def run_hip(case, H, flags, gy, dev):
+    seqs, tgts, P, ids, w, (B, L1, dm, D) = case
+    ln, res, causal, pool = flags
+
+    def d(t):
+        return None if t is None else t.to(torch.float32).to(dev).contiguous()
+    hs, ht, hw, hp = [d(t) for t in seqs], [d(t) for t in tgts], tuple(d(t) for t in w), d(P)
+    hid = ids.to(dev)
+    y = torch.empty((B, L1, dm) if ops.BST_POOLS[pool] == 0 else (B, dm), dtype=torch.float32, device=dev)
+    ops.bst_block_fwd(hs, ht, hp, hid, hw, H, ln, res, causal, pool, y)
+    pos_D = D if P is not None else 0
+    dseqs, dtgts = [torch.empty_like(t) for t in hs], [torch.empty_like(t) for t in ht]
+    grads = torch.empty(ops.bst_grad_floats(L1, dm, pos_D), dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.bst_workspace_floats(B, L1, dm, pos_D), dtype=torch.float32, device=dev)
+    ops.bst_block_bwd(hs, ht, hp, hid, hw, H, ln, res, causal, pool, d(gy), dseqs, dtgts, grads, ws)
+    torch.cuda.synchronize()
+    return y, dseqs, dtgts, grads
+
+
+def split_grads(grads, L1, dm, D, layer_norm, has_pos):
+    DD = dm * dm
+    out, off = {}, 0
+    for name, n, shape in (("in_w", 3 * DD, (3 * dm, dm)), ("out_w", DD, (dm, dm)), ("w1", DD, (dm, dm)),
+                           ("w2", DD, (dm, dm)), ("in_b", 3 * dm, (3 * dm,)), ("out_b", dm, (dm,)),
+                           ("b1", dm, (dm,)), ("b2", dm, (dm,)), ("ln1_w", dm, (dm,)), ("ln1_b", dm, (dm,)),
+                           ("ln2_w", dm, (dm,)), ("ln2_b", dm, (dm,))):
+        if layer_norm or not name.startswith("ln"):
+            out[name] = grads[off:off + n].view(shape)
+        off += n
+    if has_pos:
+        out["pos"] = grads[off:].view(L1, D)
+    return out
+
+
+def check(tag, case, H, flags, dev):
+    seqs, tgts, P, ids, w, (B, L1, dm, D) = case
+    y64, g64, gy, dropped = reference(case, H, flags, torch.float64)
+    assert dropped <= 0.1 * B, (tag, dropped, B)
+    y32, g32, _, _ = reference(case, H, flags, torch.float32, gy=gy)
+    y, dseqs, dtgts, grads = run_hip(case, H, flags, gy, dev)
+    got = split_grads(grads.cpu(), L1, dm, D, flags[0], P is not None)
+    got.update({"seq%d" % i: t.cpu() for i, t in enumerate(dseqs) if t.numel()})
+    got.update({"tgt%d" % i: t.cpu() for i, t in enumerate(dtgts)})
+    pairs = [("Y", y.cpu().reshape(y64.shape), y64, y32)] + [(k, got[k], g64[k], g32[k]) for k in g64]
+    worst = 0.0
+    for name, hip, r64, r32 in pairs:
+        assert torch.isfinite(hip).all(), (tag, name)
+        e32 = float((r32.double() - r64).abs().max())
+        bound = 4.0 * e32 + 1e-6 * float(r64.abs().max())
+        err = float((hip.double() - r64).abs().max())
+        ratio = err / bound if bound > 0 else (0.0 if err == 0 else float("inf"))
+        worst = max(worst, ratio)
+        print("%s %-6s err %.3e bound %.3e ratio %.3f" % (tag, name, err, bound, ratio))
+        assert err <= bound, (tag, name, err, bound)
+    return worst
+
+
+SEEDS = (100, 101, 122, 103, 104)      # per shape; see the module docstring
+
+
+def shapes():
+    grid = ops.bst_limits()[2]
+    return [(33, 50, 2, 16, 2, True), (5, 1, 1, 4, 1, False), (7, 63, 1, 32, 64, True), (9, 6, 3, 5, 4, True),
+            (grid + 3, 2, 1, 4, 2, True)]
+
+
+@pytest.mark.parametrize("flags", FLAGS, ids=lambda f: "ln%d_res%d_causal%d_%s" % (f[0], f[1], f[2], f[3]))
+@pytest.mark.parametrize("shape", range(5))
+def test_block_against_fp64(shape, flags):
+    B, L, n_parts, D, H, pos = shapes()[shape]
+    case = make_case(B, L, n_parts, D, H, pos, flags[0], seed=SEEDS[shape])
+    check("B%d L%d p%d D%d H%d pos%d %s" % (B, L, n_parts, D, H, pos, flags[3]), case, H, flags,
+          torch.device("cuda", 0))
+
+
+def test_scores_of_plus_minus_80_stay_finite_and_in_bound():
+    B, L, n_parts, D, H = 9, 12, 2, 8, 2
+    case = make_case(B, L, n_parts, D, H, True, True, seed=7, x_scale=6.0, w_scale=4.0)
+    seqs, tgts, P, ids, w, (B, L1, dm, D) = case
+    X = torch.cat([torch.cat([s, t.unsqueeze(1)], 1) for s, t in zip(seqs, tgts)] + [P.expand(B, L1, D)], dim=-1)
+    QKV = X @ w[0].t() + w[1]
+    hd = dm // H
+    Q, K = (QKV[..., i * dm:(i + 1) * dm].reshape(B, L1, H, hd).permute(0, 2, 1, 3) for i in (0, 1))
+    S = Q @ K.transpose(-1, -2) / hd ** 0.5
+    assert float(S.max()) >= 80 and float(S.min()) <= -80, (float(S.min()), float(S.max()))
+    check("scores+-80", case, H, (True, True, False, "mean"), torch.device("cuda", 0))
+
+
+def test_parts_in_a_wider_record_and_the_accumulate_flag():
+    """The parts are views into a wider record (own batch and position strides), read in place; the gradients are
+    written through strides of their own, the bytes between them stay untouched; dx_accumulate adds."""
+    dev = torch.device("cuda", 0)
+    B, L, D, H = 6, 7, 8, 2
+    flags = (True, True, False, "mean")
+    case = make_case(B, L, 2, D, H, True, True, seed=11)
+    seqs, tgts, P, ids, w, (B, L1, dm, D) = case
+    y64, g64, gy, _ = reference(case, H, flags, torch.float64)
+    y32, g32, _, _ = reference(case, H, flags, torch.float32, gy=gy)
+    rec = torch.full((B, 3 + 2 * L + 4, D + 3), float("nan"), dtype=torch.float32, device=dev)
+    # part 0: target in slot 1, history in slots 3 .. 3+L; part 1: target in slot 2, history in the last L slots
+    t0, t1 = rec[:, 1, :D], rec[:, 2, 1:D + 1]
+    s0, s1 = rec[:, 3:3 + L, :D], rec[:, 3 + L:3 + 2 * L, 2:D + 2]
+    for view, src in ((t0, tgts[0]), (t1, tgts[1]), (s0, seqs[0]), (s1, seqs[1])):
+        view.copy_(src.float())
+    hw = tuple(None if t is None else t.float().to(dev) for t in w)
+    y = torch.empty(B, dm, dtype=torch.float32, device=dev)
+    ops.bst_block_fwd([s0, s1], [t0, t1], P.float().to(dev), ids.to(dev), hw, H, *flags, y)
+    drec = torch.full_like(rec, 3.0)
+    dviews = ([drec[:, 3:3 + L, :D], drec[:, 3 + L:3 + 2 * L, 2:D + 2]], [drec[:, 1, :D], drec[:, 2, 1:D + 1]])
+    grads = torch.empty(ops.bst_grad_floats(L1, dm, D), dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.bst_workspace_floats(B, L1, dm, D), dtype=torch.float32, device=dev)
+    names = (("seq0", dviews[0][0]), ("seq1", dviews[0][1]), ("tgt0", dviews[1][0]), ("tgt1", dviews[1][1]))
+    touched = torch.zeros_like(drec, dtype=torch.bool)
+    touched[:, 3:3 + L, :D] = True
+    touched[:, 3 + L:3 + 2 * L, 2:D + 2] = True
+    touched[:, 1, :D] = True
+    touched[:, 2, 1:D + 1] = True
+
+    def backward(accumulate):
+        ops.bst_block_bwd([s0, s1], [t0, t1], P.float().to(dev), ids.to(dev), hw, H, *flags, gy.float().to(dev),
+                          dviews[0], dviews[1], grads, ws, dx_accumulate=accumulate)
+        torch.cuda.synchronize()
+        assert bool((drec[~touched] == 3.0).all())
+    backward(False)                         # overwrites the 3.0 in its own places only
+    first = {}
+    for name, view in names:
+        e32 = float((g32[name].double() - g64[name]).abs().max())
+        bound = 4.0 * e32 + 1e-6 * float(g64[name].abs().max())
+        err = float((view.cpu().double() - g64[name]).abs().max())
+        assert err <= bound, (name, err, bound)
+        first[name] = view.clone()
+    # onto its own first result.  The kernel adds the residual's share and then the rest: two fp32 additions onto
+    # the old value, each off by at most half an ulp of its result, so |acc - 2 first| <= 2 * 2^-24 * 2 max|acc|
+    # per element (from the number format alone; the yardstick above is untouched).  An overwrite would miss by
+    # |first|.
+    backward(True)
+    for name, view in names:
+        err = float((view.double() - 2.0 * first[name].double()).abs().max())
+        bound = 2.0 ** -22 * float(view.abs().max())
+        assert 0 < float(first[name].abs().max()) and err <= bound, (name, err, bound)
+    assert float((y.cpu().double() - y64).abs().max()) <= 4.0 * float((y32.double() - y64).abs().max()) + \
+        1e-6 * float(y64.abs().max())
+
+
+def test_two_launches_give_the_same_bits():
+    dev = torch.device("cuda", 0)
+    case = make_case(33, 50, 2, 16, 2, True, True, seed=5)
+    flags = (True, True, False, "mean")
+    gy = torch.randn(33, 48, dtype=torch.float64, generator=torch.Generator().manual_seed(1))
+    a = run_hip(case, 2, flags, gy, dev)
+    b = run_hip(case, 2, flags, gy, dev)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[3], b[3])
+    for x, y in zip(a[1] + a[2], b[1] + b[2]):
+        assert torch.equal(x, y)
+
+
+def test_limits_are_rejected_before_any_launch():
+    import ctypes
+    with pytest.raises(NotImplementedError, match="L1 <= 64"):
+        ops.bst_check(65, 48, 2, 16)
+    with pytest.raises(NotImplementedError, match="dm <= 64"):
+        ops.bst_check(51, 96, 2, 32)
+    dev = torch.device("cuda", 0)
+    case = make_case(3, 64, 1, 8, 2, True, True, seed=3)              # L1 = 65
+    seqs, tgts, P, ids, w, _ = case
+    with pytest.raises(NotImplementedError, match="L1 <= 64"):
+        run_hip(case, 2, (True, True, False, "mean"), torch.zeros(3, 16, dtype=torch.float64), dev)
+    lib = _lib.load()
+    inp, wt = _lib.BstInput(), _lib.BstWeights()
+    inp.n_parts, inp.D = 1, 8
+    st = lib.fx_bst_block_fwd(ctypes.byref(inp), None, 0, 3, 65, 8, 2, ctypes.byref(wt), 1, 1, 0, 1, None, None)
+    assert st == 1 and b"L1 <= 64" in lib.fx_last_error()
+
+
+def test_a_chain_of_two_blocks_agrees_with_the_fp64_chain():
+    dev = torch.device("cuda", 0)
+    B, L, D, H = 12, 9, 8, 2
+    c1 = make_case(B, L, 1, D, H, True, True, seed=21)
+    c2 = make_case(B, L, 1, 2 * D, H, False, True, seed=22)           # (only its weights are used)
+    seqs, tgts, P, ids, w1, (B, L1, dm, D) = c1
+    w2 = c2[4]
+    f1, f2 = (True, True, False, "none"), (True, True, False, "mean")
+    outs = {}
+    for dtype in (torch.float64, torch.float32):
+        def leaf(t):
+            return t.to(dtype).clone().requires_grad_(True)
+        ls, lt, lp = leaf(seqs[0]), leaf(tgts[0]), leaf(P)
+        lw1, lw2 = [leaf(t) for t in w1], [leaf(t) for t in w2]
+        x = bst_block([ls], [lt], lp, ids, lw1, H, *f1)
+        y = bst_block([x[:, :L]], [x[:, L]], None, ids, lw2, H, *f2)
+        gy = torch.randn(y.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(4))
+        got = torch.autograd.grad(y, [ls, lt, lp, lw1[0], lw2[0]], gy.to(dtype))
+        outs[dtype] = [y.detach()] + [t.detach() for t in got]
+
+    def d(t):
+        return None if t is None else t.float().to(dev).contiguous()
+    hs, ht, hp, hid = d(seqs[0]), d(tgts[0]), d(P), ids.to(dev)
+    hw1, hw2 = tuple(d(t) for t in w1), tuple(d(t) for t in w2)
+    x = torch.empty(B, L1, dm, dtype=torch.float32, device=dev)
+    y = torch.empty(B, dm, dtype=torch.float32, device=dev)
+    ops.bst_block_fwd([hs], [ht], hp, hid, hw1, H, *f1, x)
+    ops.bst_block_fwd([x[:, :L]], [x[:, L]], None, hid, hw2, H, *f2, y)
+    dx = torch.empty_like(x)
+    ga = torch.empty(ops.bst_grad_floats(L1, dm, D), dtype=torch.float32, device=dev)
+    gb = torch.empty(ops.bst_grad_floats(L1, dm, 0), dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.bst_workspace_floats(B, L1, dm, D), dtype=torch.float32, device=dev)
+    ops.bst_block_bwd([x[:, :L]], [x[:, L]], None, hid, hw2, H, *f2, d(gy), [dx[:, :L]], [dx[:, L]], gb, ws)
+    ds, dt = torch.empty_like(hs), torch.empty_like(ht)
+    ops.bst_block_bwd([hs], [ht], hp, hid, hw1, H, *f1, dx, [ds], [dt], ga, ws)
+    torch.cuda.synchronize()
+    DD = dm * dm
+    hip = [y.cpu(), ds.cpu(), dt.cpu(), ga[6 * DD + 10 * dm:].view(L1, D).cpu(), ga[:3 * DD].view(3 * dm, dm).cpu(),
+           gb[:3 * DD].view(3 * dm, dm).cpu()]
+    for name, h, r64, r32 in zip(("Y", "dseq", "dtgt", "dpos", "d in_w 0", "d in_w 1"), hip, outs[torch.float64],
+                                 outs[torch.float32]):
+        e32 = float((r32.double() - r64).abs().max())
+        bound = 4.0 * e32 + 1e-6 * float(r64.abs().max())
+        err = float((h.double() - r64).abs().max())
+        print("chain %-9s err %.3e bound %.3e ratio %.3f" % (name, err, bound, err / bound))
+        assert err <= bound, (name, err, bound)
