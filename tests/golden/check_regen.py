@@ -32,9 +32,10 @@ def main(other):
                 ma.pop("torch", None), mb.pop("torch", None)
                 if ma != mb:
                     diffs.append("meta")
-            elif a[k].shape != b[k].shape or not np.array_equal(a[k], b[k], equal_nan=True):
-                d = np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max() \
-                    if a[k].shape == b[k].shape else "shape"
+            elif a[k].shape != b[k].shape or not np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"):
+                # (group_metrics.npz holds the metrics' names: arrays of strings)
+                d = "shape" if a[k].shape != b[k].shape else "values" if a[k].dtype.kind not in "biuf" else \
+                    np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max()
                 diffs.append("%s (max |d| %s)" % (k, d))
         print("%-32s %s" % (fn, "identical" if not diffs else "DIFFERS: " + "; ".join(diffs[:6])))
         bad += bool(diffs)

@@ -8,6 +8,7 @@ own DeepFM / DCNv2 on CPU, runs forward + `train_step` (rank_model.py:307-323) o
 synthetic batches and stores inputs, initial weights and the reference's outputs in
 tests/golden/<case>.npz.  Nothing is written inside /root/reference.
 """
+import contextlib
 import json
 import os
 import sys
@@ -113,6 +114,131 @@ def make_batches(rng, spec, B, n, pad_frac=0.02):
         b["label"] = (rng.random(B) < 0.3).astype(np.float32)
         batches.append(b)
     return batches
+
+
+def _rounded(v):
+    if isinstance(v, (list, tuple)):
+        return [_rounded(x) for x in v]
+    return round(v, 3) if isinstance(v, float) else v
+
+
+def record_case(case, build_reference, probe, accept, finish=None, is_table=lambda k: "embedding_layers" in k,
+                make_spec=None, edit_batches=None):
+    """One fixture of a make_golden_<family>.py: everything its cases share.
+      build_reference(case, fmap) -> the reference's model, with whatever the family does to a fresh one besides
+          rescaling the tables;
+      probe(model, batch, case) -> (logit0, pred0, shares) of one eval forward of the last batch, `shares` a dict of
+          the figures that show the fixture is not vacuous (kept in `meta`, floats rounded to 3 places).  The probe
+          removes the hooks it registers and puts back what it changes;
+      accept(shares, case) -> bool: the tables are scaled by `emb_scale`, then doubled until this holds, at most up
+          to `emb_scale_max`; a case that names `emb_scale_max` gets the scale that was reached as
+          `meta["emb_scale_used"]`.  A family that asserts in its probe and never rescales passes
+          `lambda shares, case: True`;
+      is_table(parameter name) -> bool: the tables are the parameters it selects that have more than one row and more
+          than one column (default: every feature embedding's, wherever the model keeps one);
+      finish(out, model, case, fmap) -> dict of further `meta` entries, after its own assertions on the arrays `out`
+          and the trained model;
+      make_spec(case) -> the schema (default: small_criteo_spec of `n_dense`, `cards`);
+      edit_batches(batches, spec, case): changes the seeded batches in place before anything reads them."""
+    import numpy as np
+    import torch
+    from fuxictr.features import FeatureMap
+    from fuxictr.pytorch.torch_utils import seed_everything
+    name = case["name"]
+    spec = make_spec(case) if make_spec else small_criteo_spec(name, case["n_dense"], case["cards"])
+    os.makedirs(os.path.join(TMP, name), exist_ok=True)
+    fm_path = os.path.join(TMP, name, "feature_map.json")
+    with open(fm_path, "w") as f:
+        json.dump(spec, f)
+    seed_everything(case["seed"])
+    torch.set_num_threads(8)
+    fmap = FeatureMap(name, os.path.join(TMP, name))
+    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
+    model = build_reference(case, fmap)
+    model._max_gradient_norm = case["max_norm"]          # what fit() would set (rank_model.py:251)
+    batches = make_batches(np.random.default_rng(case["seed"]), spec, case["B"], case["steps"] + 1)
+    if edit_batches:
+        edit_batches(batches, spec, case)
+
+    def to_torch(b):
+        return {k: torch.from_numpy(v) for k, v in b.items()}
+    # make the (1e-4 std) tables matter: scale the tables, not the weights, until the fixture is not vacuous
+    tables = [p for k, p in model.named_parameters()
+              if is_table(k) and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1]
+    model.eval()
+    scale, factor = case["emb_scale"], case["emb_scale"]
+    while True:
+        with torch.no_grad():
+            for p in tables:
+                p.mul_(factor)
+        logit0, p0, shares = probe(model, to_torch(batches[-1]), case)
+        if accept(shares, case):
+            break
+        assert scale * 2.0 <= case.get("emb_scale_max", scale), (name, scale, shares)
+        scale, factor = scale * 2.0, 2.0
+    out = {}
+    for k, v in model.state_dict().items():
+        out["state0/" + k] = v.detach().cpu().numpy().copy()
+    logits = []
+    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
+    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
+    out["expect/logit0"] = logit0.numpy().reshape(-1).copy()
+    model.train()
+    losses = [float(model.train_step(to_torch(batches[i])).item()) for i in range(case["steps"])]
+    assert all(a != b for a, b in zip(losses, losses[1:])), losses
+    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
+    model.eval()
+    with torch.no_grad():
+        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
+    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
+    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
+    for k, v in model.state_dict().items():
+        out["state1/" + k] = v.detach().cpu().numpy().copy()
+    for i, b in enumerate(batches):
+        for k, v in b.items():
+            out["batch%d/%s" % (i, k)] = v
+    meta = dict(case)
+    meta["spec"] = spec
+    meta["torch"] = torch.__version__
+    if "emb_scale_max" in case:
+        meta["emb_scale_used"] = scale
+    meta.update({k: _rounded(v) for k, v in shares.items()})
+    extra = finish(out, model, case, fmap) if finish else {}
+    meta.update(extra)
+    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    path = os.path.join(OUT_DIR, name + ".npz")
+    np.savez_compressed(path, **out)
+    print(name, "loss", losses, "scale", scale, dict(shares), extra, "->", path, os.path.getsize(path) // 1024, "KiB")
+
+
+@contextlib.contextmanager
+def probing(model, batch):
+    """For a family's probe: -> forward(), which runs the eval forward of `batch` as the model stands at that moment,
+    without gradients, and returns (logits, y_pred)."""
+    import torch
+    logits = []
+    handle = model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
+
+    def forward():
+        pred = model.forward(batch)["y_pred"]
+        return logits[-1].clone(), pred
+    with torch.no_grad():
+        yield forward
+    handle.remove()
+
+
+def logit_share(logit, logit0):
+    """How far a changed forward moved the logits, as a share of their largest magnitude."""
+    return float((logit - logit0).abs().max() / logit0.abs().max())
+
+
+def main(cases, run):
+    """The `__main__` of every generator: the cases named on the command line, or all."""
+    _import_reference()
+    only = sys.argv[1:]
+    for case in cases:
+        if not only or case["name"] in only:
+            run(case)
 
 
 def run_case(case):
@@ -475,11 +601,5 @@ CASES = [
 ]
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
-    for name in DEMOS:
-        if not only or name in only:
-            run_demo(name)
+    main(CASES, run_case)
+    main([dict(name=name) for name in DEMOS], lambda demo: run_demo(demo["name"]))

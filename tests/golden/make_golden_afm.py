@@ -21,16 +21,13 @@ gradient, so of these only the `weight_p` share, the losses and weight_p's chang
 `afm_noatt` does not run the attention: there the pair sum itself must matter (zeroing the tables' second-order
 part is the `pair_share`) and the losses differ.
 """
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
-from make_golden import TMP, _import_reference, make_batches, small_criteo_spec  # noqa: E402
-
-OUT_DIR = os.environ.get("FX_GOLDEN_OUT") or HERE
+from make_golden import TMP, logit_share, main, probing, record_case  # noqa: E402
 
 CARDS = [37, 13, 1500, 900, 11, 5, 211]
 _BASE = dict(model="AFM", n_dense=3, cards=CARDS, B=64, steps=3, lr=1e-2, max_norm=10.0, seed=23, emb_scale=2e3,
@@ -59,128 +56,49 @@ def build_reference(case, fmap):
                attention_dropout=[0, 0], use_attention=case["use_attention"])
 
 
-def _probe(model, batch, case):
-    """-> (logit0, pred0, shares) of one eval forward of `batch`"""
+def probe(model, batch, case):
     import torch
-    logits, att = [], []
-    h_logit = model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    shares = {}
-    with torch.no_grad():
+    att, shares = [], {}
+    with probing(model, batch) as forward:
         h_att = model.attention.register_forward_hook(lambda m, i, r: att.append(r.detach().clone()))
-        p0 = model.forward(batch)["y_pred"]
+        logit0, p0 = forward()
         h_att.remove()
-        logit0 = logits[-1].clone()
-        top = float(logit0.abs().max())
         if case["use_attention"]:
             a = att[-1].squeeze(-1)                                     # [B, P]
             if a.shape[1] > 1:
                 ratio = a.max(dim=1).values / a.min(dim=1).values
                 shares["att_ratio_share"] = float((ratio >= 2.0).float().mean())
                 h_uni = model.attention.register_forward_hook(lambda m, i, r: torch.full_like(r, 1.0 / r.shape[1]))
-                model.forward(batch)
+                shares["att_share"] = logit_share(forward()[0], logit0)
                 h_uni.remove()
-                shares["att_share"] = float((logits[-1] - logit0).abs().max() / top)
             kept = model.weight_p.weight.detach().clone()
             model.weight_p.weight.zero_()
-            model.forward(batch)
+            shares["wp_share"] = logit_share(forward()[0], logit0)
             model.weight_p.weight.copy_(kept)
-            shares["wp_share"] = float((logits[-1] - logit0).abs().max() / top)
         else:
             # without the pair sum: the linear part alone
-            shares["pair_share"] = float((model.lr_layer(model.get_inputs(batch)) - logit0).abs().max() / top)
-    h_logit.remove()
+            shares["pair_share"] = logit_share(model.lr_layer(model.get_inputs(batch)), logit0)
     return logit0, p0, shares
 
 
-def _enough(shares):
+def accept(shares, case):
     floors = {"att_ratio_share": 0.5, "att_share": 0.05, "wp_share": 0.05, "pair_share": 0.05}
     return all(v >= floors[k] for k, v in shares.items())
 
 
-def run_case(case):
+def finish(out, model, case, fmap):
     import numpy as np
-    import torch
-    from fuxictr.features import FeatureMap
-    from fuxictr.pytorch.torch_utils import seed_everything
-    name = case["name"]
-    spec = small_criteo_spec(name, case["n_dense"], case["cards"])
-    os.makedirs(os.path.join(TMP, name), exist_ok=True)
-    fm_path = os.path.join(TMP, name, "feature_map.json")
-    with open(fm_path, "w") as f:
-        json.dump(spec, f)
-    seed_everything(case["seed"])
-    torch.set_num_threads(8)
-    fmap = FeatureMap(name, os.path.join(TMP, name))
-    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
-    model = build_reference(case, fmap)
-    model._max_gradient_norm = case["max_norm"]
-    rng = np.random.default_rng(case["seed"])
-    batches = make_batches(rng, spec, case["B"], case["steps"] + 1)
-
-    def to_torch(b):
-        return {k: torch.from_numpy(v) for k, v in b.items()}
-    tables = [p for k, p in model.named_parameters()
-              if k.startswith("embedding_layer.") and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1]
-    model.eval()
-    scale = case["emb_scale"]
-    with torch.no_grad():
-        for p in tables:
-            p.mul_(scale)
-    while True:
-        logit0, p0, shares = _probe(model, to_torch(batches[-1]), case)
-        if _enough(shares):
-            break
-        assert scale * 2.0 <= case["emb_scale_max"], (name, scale, shares)
-        scale *= 2.0
-        with torch.no_grad():
-            for p in tables:
-                p.mul_(2.0)
-    out = {}
-    for k, v in model.state_dict().items():
-        out["state0/" + k] = v.detach().cpu().numpy().copy()
-    logits = []
-    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
-    out["expect/logit0"] = logit0.numpy().reshape(-1).copy()
-    model.train()
-    losses = []
-    for i in range(case["steps"]):
-        losses.append(float(model.train_step(to_torch(batches[i])).item()))
-    assert all(a != b for a, b in zip(losses, losses[1:])), losses
-    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
-    model.eval()
-    with torch.no_grad():
-        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
-    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
-    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
-    for k, v in model.state_dict().items():
-        out["state1/" + k] = v.detach().cpu().numpy().copy()
     n_pairs = fmap.num_fields * (fmap.num_fields - 1) // 2
     moved = [k for k in ATT_KEYS if not np.array_equal(out["state1/" + k], out["state0/" + k])]
     if case["use_attention"]:
         want = ATT_KEYS if n_pairs > 1 else ["weight_p.weight"]
-        assert all(k in moved for k in want), (name, moved)
-    for i, b in enumerate(batches):
-        for k, v in b.items():
-            out["batch%d/%s" % (i, k)] = v
-    meta = dict(case)
-    meta["spec"] = spec
-    meta["torch"] = torch.__version__
-    meta["emb_scale_used"] = scale
-    meta["n_pairs"] = n_pairs
-    meta["moved"] = moved
-    for k, v in shares.items():
-        meta[k] = round(v, 3)
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(OUT_DIR, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(name, "loss", losses, "scale", scale, shares, "moved", moved, "->", path, os.path.getsize(path) // 1024,
-          "KiB")
+        assert all(k in moved for k in want), (case["name"], moved)
+    return {"n_pairs": n_pairs, "moved": moved}
+
+
+def run_case(case):
+    record_case(case, build_reference, probe, accept, finish)
 
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
+    main(CASES, run_case)

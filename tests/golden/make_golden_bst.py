@@ -15,16 +15,13 @@ recorded forward and records in `meta`:
   * every batch holds an all-padding history, a full one and one with padding (rows 0 and 1 are overwritten).
 The tables are rescaled (`emb_scale`) for that, never the weights.
 """
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
-from make_golden import TMP, _import_reference, make_batches, pair_seq_spec, small_seq_spec  # noqa: E402
-
-OUT_DIR = os.environ.get("FX_GOLDEN_OUT") or HERE
+from make_golden import TMP, main, pair_seq_spec, probing, record_case, small_seq_spec  # noqa: E402
 
 _BASE = dict(model="BST", B=64, steps=3, lr=1e-2, max_norm=10.0, seed=7, emb_scale=3e4, optimizer="adam",
              schema="small_seq", embedding_dim=8, heads=2, layers=1, pooling="mean", causal=False, layer_norm=True,
@@ -62,39 +59,39 @@ def fields_of(case):
     return ["adgroup_id"], ["click_sequence"]
 
 
-def run_case(case):
-    import numpy as np
-    import torch
-    from fuxictr.features import FeatureMap
-    from fuxictr.pytorch.torch_utils import seed_everything
+def build_reference(case, fmap):
     from model_zoo import BST
-    name = case["name"]
-    spec = pair_seq_spec(name) if case["schema"] == "pair_seq" else small_seq_spec(name)
-    os.makedirs(os.path.join(TMP, name), exist_ok=True)
-    fm_path = os.path.join(TMP, name, "feature_map.json")
-    with open(fm_path, "w") as f:
-        json.dump(spec, f)
-    seed_everything(case["seed"])
-    torch.set_num_threads(8)
-    fmap = FeatureMap(name, os.path.join(TMP, name))
-    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
     target, sequence = fields_of(case)
     as_field = lambda f: tuple(f) if isinstance(f, list) else f      # noqa: E731
-    model = BST(fmap, model_id=name, gpu=-1, embedding_dim=case["embedding_dim"], learning_rate=case["lr"],
-                optimizer=case["optimizer"], loss="binary_crossentropy", task="binary_classification",
-                metrics=["logloss", "AUC"], verbose=0, model_root=TMP, embedding_regularizer=0, net_regularizer=0,
-                dnn_hidden_units=case["hidden"], dnn_activations="relu", num_heads=case["heads"],
-                stacked_transformer_layers=case["layers"], layer_norm=case["layer_norm"],
-                use_residual=case["use_residual"], bst_target_field=[as_field(f) for f in target],
-                bst_sequence_field=[as_field(f) for f in sequence], seq_pooling_type=case["pooling"],
-                use_position_emb=case["use_position_emb"], use_causal_mask=case["causal"])
-    with torch.no_grad():        # make the (1e-4 std) tables matter: scale the tables, not the weights
-        for k, p in model.named_parameters():
-            if "embedding_layers" in k and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1:
-                p.mul_(case["emb_scale"])
-    model._max_gradient_norm = case["max_norm"]
-    logits, seen = [], {}
-    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
+    return BST(fmap, model_id=case["name"], gpu=-1, embedding_dim=case["embedding_dim"], learning_rate=case["lr"],
+               optimizer=case["optimizer"], loss="binary_crossentropy", task="binary_classification",
+               metrics=["logloss", "AUC"], verbose=0, model_root=TMP, embedding_regularizer=0, net_regularizer=0,
+               dnn_hidden_units=case["hidden"], dnn_activations="relu", num_heads=case["heads"],
+               stacked_transformer_layers=case["layers"], layer_norm=case["layer_norm"],
+               use_residual=case["use_residual"], bst_target_field=[as_field(f) for f in target],
+               bst_sequence_field=[as_field(f) for f in sequence], seq_pooling_type=case["pooling"],
+               use_position_emb=case["use_position_emb"], use_causal_mask=case["causal"])
+
+
+def make_spec(case):
+    return pair_seq_spec(case["name"]) if case["schema"] == "pair_seq" else small_seq_spec(case["name"])
+
+
+def edit_batches(batches, spec, case):
+    import numpy as np
+    seq_names = [n for item in spec["features"] for n, fs in item.items() if fs["type"] == "sequence"]
+    for b in batches:            # row 0: an all-padding history, row 1: a full one
+        for n in seq_names:
+            b[n][0, :] = 0
+            b[n][1, :] = np.where(b[n][1] == 0, 1 + (np.arange(b[n].shape[1]) % 5), b[n][1])
+        lens = (b["click_sequence"] != 0).sum(axis=1)
+        L = b["click_sequence"].shape[1]
+        assert (lens == 0).any() and (lens == L).any() and ((lens > 0) & (lens < L)).any(), case["name"]
+
+
+def probe(model, batch, case):
+    import torch
+    name, seen = case["name"], {}
     block0 = model.transformer_encoders[0].transformer_blocks[0]
 
     def attention_hook(module, args, kwargs, result):
@@ -106,87 +103,47 @@ def run_case(case):
         seen["busy"] = False
         seen["P"], seen["mask"] = P.detach().clone(), kwargs["attn_mask"].detach().clone()
         return None
-    block0.attention.register_forward_hook(attention_hook, with_kwargs=True)
 
     def lrelu_hook(module, inp):     # (returns None: a pre-hook's return value would replace the input)
         seen.setdefault("neg", float((inp[0] < 0).float().mean()))
-    block0.ffn[1].register_forward_pre_hook(lrelu_hook)
-    rng = np.random.default_rng(case["seed"])
-    batches = make_batches(rng, spec, case["B"], case["steps"] + 1)
-    seq_names = [n for item in spec["features"] for n, fs in item.items() if fs["type"] == "sequence"]
-    first = seq_names[0] if case["schema"] != "pair_seq" else "click_sequence"
-    for b in batches:            # row 0: an all-padding history, row 1: a full one
-        for n in seq_names:
-            b[n][0, :] = 0
-            b[n][1, :] = np.where(b[n][1] == 0, 1 + (np.arange(b[n].shape[1]) % 5), b[n][1])
-        lens = (b[first] != 0).sum(axis=1)
-        L = b[first].shape[1]
-        assert (lens == 0).any() and (lens == L).any() and ((lens > 0) & (lens < L)).any(), name
-    out = {}
-    for k, v in model.state_dict().items():
-        out["state0/" + k] = v.detach().cpu().numpy().copy()
-
-    def to_torch(b):
-        return {k: torch.from_numpy(v) for k, v in b.items()}
-    model.eval()
-    with torch.no_grad():
-        p0 = model.forward(to_torch(batches[-1]))["y_pred"]
+    handles = [block0.attention.register_forward_hook(attention_hook, with_kwargs=True),
+               block0.ffn[1].register_forward_pre_hook(lrelu_hook)]
+    with probing(model, batch) as forward:
+        logit0, p0 = forward()
+    for h in handles:
+        h.remove()
     # the fixture is not vacuous
     H = case["heads"]
     P, mask = seen["P"], seen["mask"]                       # [B, H, L1, L1], [B * H, L1, L1] (True = masked)
     B, L1 = P.shape[0], P.shape[-1]
     open_keys = (~mask).view(B, H, L1, L1).sum(dim=-1)      # [B, H, L1]
-    pad = torch.cat([torch.from_numpy(batches[-1][first] == 0), torch.zeros(B, 1, dtype=torch.bool)], dim=1)
+    pad = torch.cat([batch["click_sequence"] == 0, torch.zeros(B, 1, dtype=torch.bool)], dim=1)
     rows = (~pad).unsqueeze(1).expand(B, H, L1) & (open_keys >= 3)
     peak = float((P.max(dim=-1).values - 1.0 / open_keys.float())[rows].median())
     assert int(rows.sum()) >= 32, (name, int(rows.sum()))
     assert 0.05 <= peak <= 0.5, (name, peak)
     assert 0.1 <= seen["neg"] <= 0.9, (name, seen["neg"])
-    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
-    out["expect/logit0"] = logits[-1].numpy().reshape(-1).copy()
-    model.train()
-    losses = []
-    for i in range(case["steps"]):
-        losses.append(float(model.train_step(to_torch(batches[i])).item()))
-    assert all(a != b for a, b in zip(losses, losses[1:])), losses
-    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
+    return logit0, p0, {"attention_peak_median": peak, "attention_rows": int(rows.sum()),
+                        "lrelu_negative_share": seen["neg"]}
+
+
+def finish(out, model, case, fmap):
     # the residue claim above, shown on the reference's own last gradient (as clipped; the ratio does not depend on
     # the clip): the K third of in_proj_bias against the Q third
-    bias_grad = block0.attention.in_proj_bias.grad
+    bias_grad = model.transformer_encoders[0].transformer_blocks[0].attention.in_proj_bias.grad
     third = bias_grad.numel() // 3
     k_res, q_max = float(bias_grad[third:2 * third].abs().max()), float(bias_grad[:third].abs().max())
-    assert k_res <= 1e-4 * q_max, (name, k_res, q_max)
-    model.eval()
-    with torch.no_grad():
-        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
-    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
-    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
-    for k, v in model.state_dict().items():
-        out["state1/" + k] = v.detach().cpu().numpy().copy()
-    for i, b in enumerate(batches):
-        for k, v in b.items():
-            out["batch%d/%s" % (i, k)] = v
-    meta = dict(case)
-    meta["spec"] = spec
-    meta["torch"] = torch.__version__
-    meta["bst_target"], meta["bst_sequence"] = target, sequence
-    meta["attention_peak_median"] = round(peak, 3)
+    assert k_res <= 1e-4 * q_max, (case["name"], k_res, q_max)
+    target, sequence = fields_of(case)
     # what departs from the reference's defaults, spelled out: fit()'s clip is 10
-    meta["max_norm_default"] = 10.0
-    meta["max_norm_reached"] = bool(case["max_norm"] < 10.0)
-    meta["k_bias_grad_residue"] = [k_res, q_max]          # max |grad| of in_proj_bias's K third, of its Q third
-    meta["attention_rows"] = int(rows.sum())
-    meta["lrelu_negative_share"] = round(seen["neg"], 3)
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(OUT_DIR, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(name, "loss", losses, "peak", round(peak, 3), "lrelu negatives", round(seen["neg"], 3), "->", path,
-          os.path.getsize(path) // 1024, "KiB")
+    return {"bst_target": target, "bst_sequence": sequence, "max_norm_default": 10.0,
+            "max_norm_reached": bool(case["max_norm"] < 10.0),
+            "k_bias_grad_residue": [k_res, q_max]}         # max |grad| of in_proj_bias's K third, of its Q third
+
+
+def run_case(case):
+    record_case(case, build_reference, probe, lambda shares, case: True, finish, make_spec=make_spec, edit_batches=edit_batches)
 
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
+    main(CASES, run_case)

@@ -15,16 +15,13 @@ A fixture must exercise the gates and the cross weights, so the generator assert
 The tables are rescaled (`emb_scale`, doubled until the assertions hold, at most `emb_scale_max`) for that, never
 the weights; the scale that was used is kept in `meta`.
 """
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
-from make_golden import TMP, _import_reference, make_batches, small_criteo_spec  # noqa: E402
-
-OUT_DIR = os.environ.get("FX_GOLDEN_OUT") or HERE
+from make_golden import TMP, logit_share, main, probing, record_case  # noqa: E402
 
 CARDS = [37, 13, 1500, 900, 11, 5, 211]
 _BASE = dict(model="GDCN", n_dense=3, cards=CARDS, B=64, steps=3, lr=1e-2, max_norm=10.0, seed=17, emb_scale=2e3,
@@ -55,119 +52,43 @@ def build_reference(case, fmap):
                num_cross_layers=case["n_cross"])
 
 
-def _probe(model, batch, n_cross):
-    """-> (logit0, pred0, gate spread per layer, gate share, w share) of one eval forward of `batch`"""
+def probe(model, batch, case):
     import torch
-    logits, gates = [], []
-    h_logit = model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    h_gate = model.cross_net.activation.register_forward_hook(lambda m, i, r: gates.append(r.detach().clone()))
-    with torch.no_grad():
-        p0 = model.forward(batch)["y_pred"]
-        logit0 = logits[-1].clone()
-        top = float(logit0.abs().max())
-        spread = [float(g.max() - g.min()) for g in gates[:n_cross]]
+    gates = []
+    with probing(model, batch) as forward:
+        h_gate = model.cross_net.activation.register_forward_hook(lambda m, i, r: gates.append(r.detach().clone()))
+        logit0, p0 = forward()
         h_gate.remove()
+        spread = [float(g.max() - g.min()) for g in gates[:case["n_cross"]]]
+        assert len(spread) == case["n_cross"], (case["name"], spread)
         # the same forward with every gate replaced by 0.5
         h_half = model.cross_net.activation.register_forward_hook(lambda m, i, r: torch.full_like(r, 0.5))
-        model.forward(batch)
+        gate_share = logit_share(forward()[0], logit0)
         h_half.remove()
-        gate_share = float((logits[-1] - logit0).abs().max() / top)
         # ... and with every cross weight zeroed
         kept = [lin.weight.detach().clone() for lin in model.cross_net.w]
         for lin in model.cross_net.w:
             lin.weight.zero_()
-        model.forward(batch)
+        w_share = logit_share(forward()[0], logit0)
         for lin, k in zip(model.cross_net.w, kept):
             lin.weight.copy_(k)
-        w_share = float((logits[-1] - logit0).abs().max() / top)
-    h_logit.remove()
-    return logit0, p0, spread, gate_share, w_share
+    return logit0, p0, {"gate_spread": spread, "gate_share": gate_share, "w_share": w_share}
+
+
+def accept(shares, case):
+    return min(shares["gate_spread"]) >= 0.2 and shares["gate_share"] >= 0.05 and shares["w_share"] >= 0.05
+
+
+def finish(out, model, case, fmap):
+    import numpy as np
+    for k in [k[7:] for k in out if k.startswith("state1/cross_net.b.")]:
+        assert not np.array_equal(out["state1/" + k], out["state0/" + k]), (case["name"], k)
+    return {}
 
 
 def run_case(case):
-    import numpy as np
-    import torch
-    from fuxictr.features import FeatureMap
-    from fuxictr.pytorch.torch_utils import seed_everything
-    name = case["name"]
-    spec = small_criteo_spec(name, case["n_dense"], case["cards"])
-    os.makedirs(os.path.join(TMP, name), exist_ok=True)
-    fm_path = os.path.join(TMP, name, "feature_map.json")
-    with open(fm_path, "w") as f:
-        json.dump(spec, f)
-    seed_everything(case["seed"])
-    torch.set_num_threads(8)
-    fmap = FeatureMap(name, os.path.join(TMP, name))
-    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
-    model = build_reference(case, fmap)
-    model._max_gradient_norm = case["max_norm"]
-    rng = np.random.default_rng(case["seed"])
-    batches = make_batches(rng, spec, case["B"], case["steps"] + 1)
-
-    def to_torch(b):
-        return {k: torch.from_numpy(v) for k, v in b.items()}
-    tables = [p for k, p in model.named_parameters()
-              if "embedding_layers" in k and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1]
-    model.eval()
-    # make the (1e-4 std) tables matter: scale the tables, not the weights, until the fixture is not vacuous
-    scale = case["emb_scale"]
-    with torch.no_grad():
-        for p in tables:
-            p.mul_(scale)
-    while True:
-        logit0, p0, spread, gate_share, w_share = _probe(model, to_torch(batches[-1]), case["n_cross"])
-        if min(spread) >= 0.2 and gate_share >= 0.05 and w_share >= 0.05:
-            break
-        assert scale * 2.0 <= case["emb_scale_max"], (name, scale, spread, gate_share, w_share)
-        scale *= 2.0
-        with torch.no_grad():
-            for p in tables:
-                p.mul_(2.0)
-    assert len(spread) == case["n_cross"] and min(spread) >= 0.2, (name, "gate spread", spread)
-    assert gate_share >= 0.05, (name, "gate share", gate_share)
-    assert w_share >= 0.05, (name, "w share", w_share)
-    out = {}
-    for k, v in model.state_dict().items():
-        out["state0/" + k] = v.detach().cpu().numpy().copy()
-    logits = []
-    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
-    out["expect/logit0"] = logit0.numpy().reshape(-1).copy()
-    model.train()
-    losses = []
-    for i in range(case["steps"]):
-        losses.append(float(model.train_step(to_torch(batches[i])).item()))
-    assert all(a != b for a, b in zip(losses, losses[1:])), losses
-    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
-    model.eval()
-    with torch.no_grad():
-        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
-    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
-    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
-    for k, v in model.state_dict().items():
-        out["state1/" + k] = v.detach().cpu().numpy().copy()
-        if k.startswith("cross_net.b."):
-            assert not np.array_equal(out["state1/" + k], out["state0/" + k]), (name, k)
-    for i, b in enumerate(batches):
-        for k, v in b.items():
-            out["batch%d/%s" % (i, k)] = v
-    meta = dict(case)
-    meta["spec"] = spec
-    meta["torch"] = torch.__version__
-    meta["emb_scale_used"] = scale
-    meta["gate_spread"] = [round(s, 3) for s in spread]
-    meta["gate_share"] = round(gate_share, 3)
-    meta["w_share"] = round(w_share, 3)
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(OUT_DIR, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(name, "loss", losses, "scale", scale, "gate spread", meta["gate_spread"], "gate share", meta["gate_share"],
-          "w share", meta["w_share"], "->", path, os.path.getsize(path) // 1024, "KiB")
+    record_case(case, build_reference, probe, accept, finish)
 
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
+    main(CASES, run_case)

@@ -3,6 +3,7 @@
 
 Run in the build container only (the reference does not travel to the GPU box):
     python tests/golden/make_golden_group_metrics.py
+FX_GOLDEN_OUT=<dir> writes somewhere else (tests/golden/check_regen.py compares with the committed file).
 
 Case A: ~6000 samples, power-law group sizes, ids of the form c * 7 - 50 (negative ids) and, in a second copy,
 the same shifted by 10^12 (ids wider than 32 bits); predictions are distinct inside every group, so the
@@ -75,7 +76,7 @@ def main():
     y64 = y.astype(np.float64)
     ref_a = evaluate_metrics(y64, p_a.astype(np.float64), METRICS_A, g)
     ref_b = evaluate_metrics(y64, p_b.astype(np.float64), METRICS_B, g)
-    out = os.path.join(HERE, "group_metrics.npz")
+    out = os.path.join(os.environ.get("FX_GOLDEN_OUT") or HERE, "group_metrics.npz")
     np.savez_compressed(out, y_true=y, y_pred_a=p_a, y_pred_b=p_b, group_id=g,
                         names_a=np.asarray(METRICS_A), values_a=np.asarray([ref_a[m] for m in METRICS_A]),
                         names_b=np.asarray(METRICS_B), values_b=np.asarray([ref_b[m] for m in METRICS_B]))

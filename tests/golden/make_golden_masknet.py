@@ -16,16 +16,13 @@ forward:
   * consecutive losses differ.
 The tables are rescaled (`emb_scale`) for that, never the weights.
 """
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
-from make_golden import TMP, _import_reference, make_batches, small_criteo_spec  # noqa: E402
-
-OUT_DIR = os.environ.get("FX_GOLDEN_OUT") or HERE
+from make_golden import TMP, logit_share, main, probing, record_case  # noqa: E402
 
 CARDS = [37, 13, 1500, 900, 11, 5, 211]
 _BASE = dict(model="MaskNet", n_dense=3, cards=CARDS, B=64, steps=3, lr=1e-2, max_norm=10.0, seed=11,
@@ -44,68 +41,40 @@ CASES = [
 ]
 
 
-def run_case(case):
-    import numpy as np
-    import torch
-    from fuxictr.features import FeatureMap
-    from fuxictr.pytorch.torch_utils import seed_everything
+def build_reference(case, fmap):
     from model_zoo import MaskNet
-    name = case["name"]
-    spec = small_criteo_spec(name, case["n_dense"], case["cards"])
-    os.makedirs(os.path.join(TMP, name), exist_ok=True)
-    fm_path = os.path.join(TMP, name, "feature_map.json")
-    with open(fm_path, "w") as f:
-        json.dump(spec, f)
-    seed_everything(case["seed"])
-    torch.set_num_threads(8)
-    fmap = FeatureMap(name, os.path.join(TMP, name))
-    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
-    model = MaskNet(fmap, model_id=name, gpu=-1, embedding_dim=case["embedding_dim"],
-                    learning_rate=case["lr"], optimizer=case["optimizer"], loss="binary_crossentropy",
-                    task="binary_classification", metrics=["logloss", "AUC"], verbose=0, model_root=TMP,
-                    embedding_regularizer=case.get("emb_reg", 0), net_regularizer=case.get("net_reg", 0),
-                    dnn_hidden_units=case["hidden"], model_type=case["model_type"],
-                    parallel_num_blocks=case["num_blocks"], parallel_block_dim=case["block_dim"],
-                    reduction_ratio=case["ratio"], emb_layernorm=case["emb_layernorm"],
-                    net_layernorm=case["net_layernorm"])
-    with torch.no_grad():        # make the (1e-4 std) tables matter: scale the tables, not the weights
-        for k, p in model.named_parameters():
-            if "embedding_layers" in k and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1:
-                p.mul_(case["emb_scale"])
-    model._max_gradient_norm = case["max_norm"]
-    logits, seen = [], {}
-    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
+    return MaskNet(fmap, model_id=case["name"], gpu=-1, embedding_dim=case["embedding_dim"],
+                   learning_rate=case["lr"], optimizer=case["optimizer"], loss="binary_crossentropy",
+                   task="binary_classification", metrics=["logloss", "AUC"], verbose=0, model_root=TMP,
+                   embedding_regularizer=case.get("emb_reg", 0), net_regularizer=case.get("net_reg", 0),
+                   dnn_hidden_units=case["hidden"], model_type=case["model_type"],
+                   parallel_num_blocks=case["num_blocks"], parallel_block_dim=case["block_dim"],
+                   reduction_ratio=case["ratio"], emb_layernorm=case["emb_layernorm"],
+                   net_layernorm=case["net_layernorm"])
 
-    def keep(key, pick):
+
+def probe(model, batch, case):
+    import torch
+    name, seen = case["name"], {}
+
+    def keep(key):
         def hook(module, inp, result):      # (returns None: a hook's return value would replace the output)
-            if key not in seen:
-                seen[key] = pick(inp, result).detach().clone()
+            seen[key] = result.detach().clone()
         return hook
-    model.embedding_layer.register_forward_hook(keep("emb", lambda i, r: r))
-    relu_keys = []
-    for bi, block in enumerate(model.mask_net.mask_blocks):
-        if case["net_layernorm"]:
-            block.hidden_layer[2].register_forward_hook(keep("relu%d" % bi, lambda i, r: r))
-            relu_keys.append("relu%d" % bi)
-    rng = np.random.default_rng(case["seed"])
-    batches = make_batches(rng, spec, case["B"], case["steps"] + 1)
-    out = {}
-    for k, v in model.state_dict().items():
-        out["state0/" + k] = v.detach().cpu().numpy().copy()
-
-    def to_torch(b):
-        return {k: torch.from_numpy(v) for k, v in b.items()}
-    model.eval()
-    with torch.no_grad():
-        p0 = model.forward(to_torch(batches[-1]))["y_pred"]
-        logit0 = logits[-1].clone()
-        # the same forward with every V_mask replaced by ones
-        handles = [block.mask_layer.register_forward_hook(lambda m, i, r: torch.ones_like(r))
-                   for block in model.mask_net.mask_blocks]
-        model.forward(to_torch(batches[-1]))
+    blocks = model.mask_net.mask_blocks
+    handles = [model.embedding_layer.register_forward_hook(keep("emb"))]
+    relu_keys = ["relu%d" % bi for bi in range(len(blocks))] if case["net_layernorm"] else []
+    for key, block in zip(relu_keys, blocks):
+        handles.append(block.hidden_layer[2].register_forward_hook(keep(key)))
+    with probing(model, batch) as forward:
+        logit0, p0 = forward()
         for h in handles:
             h.remove()
-        mask_share = float((logits[-1] - logit0).abs().max() / logit0.abs().max())
+        # the same forward with every V_mask replaced by ones
+        handles = [block.mask_layer.register_forward_hook(lambda m, i, r: torch.ones_like(r)) for block in blocks]
+        mask_share = logit_share(forward()[0], logit0)
+        for h in handles:
+            h.remove()
     relu_zero = [float((seen[k] == 0).float().mean()) for k in relu_keys]
     emb = seen["emb"]                                                    # [B, F, D]
     emb_var_share = float((emb.var(dim=-1, unbiased=False) >= 100 * 1e-5).float().mean())
@@ -114,40 +83,12 @@ def run_case(case):
         assert 0.1 <= z <= 0.9, (name, k, z)
     assert emb_var_share >= 0.9, (name, emb_var_share)
     assert mask_share >= 0.05, (name, mask_share)
-    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
-    out["expect/logit0"] = logit0.numpy().reshape(-1).copy()
-    model.train()
-    losses = []
-    for i in range(case["steps"]):
-        losses.append(float(model.train_step(to_torch(batches[i])).item()))
-    assert all(a != b for a, b in zip(losses, losses[1:])), losses
-    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
-    model.eval()
-    with torch.no_grad():
-        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
-    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
-    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
-    for k, v in model.state_dict().items():
-        out["state1/" + k] = v.detach().cpu().numpy().copy()
-    for i, b in enumerate(batches):
-        for k, v in b.items():
-            out["batch%d/%s" % (i, k)] = v
-    meta = dict(case)
-    meta["spec"] = spec
-    meta["torch"] = torch.__version__
-    meta["relu_zero_share"] = [round(z, 3) for z in relu_zero]
-    meta["emb_var_share"] = round(emb_var_share, 3)
-    meta["mask_share"] = round(mask_share, 3)
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(OUT_DIR, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(name, "loss", losses, "relu zero", meta["relu_zero_share"], "emb var share", meta["emb_var_share"],
-          "mask share", meta["mask_share"], "->", path, os.path.getsize(path) // 1024, "KiB")
+    return logit0, p0, {"relu_zero_share": relu_zero, "emb_var_share": emb_var_share, "mask_share": mask_share}
+
+
+def run_case(case):
+    record_case(case, build_reference, probe, lambda shares, case: True)
 
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
+    main(CASES, run_case)

@@ -15,16 +15,13 @@ recorded forward and the recorded steps:
   * the interaction weight differs between state0 and state1; for FwFM so do interaction_weight.bias and the linear
     part's parameters.
 """
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
-from make_golden import TMP, _import_reference, make_batches, small_criteo_spec  # noqa: E402
-
-OUT_DIR = os.environ.get("FX_GOLDEN_OUT") or HERE
+from make_golden import TMP, logit_share, main, probing, record_case  # noqa: E402
 
 CARDS = [37, 13, 1500, 900, 11, 5, 211]
 _BASE = dict(n_dense=3, cards=CARDS, B=64, steps=3, lr=1e-2, max_norm=10.0, seed=23, emb_scale=1e3,
@@ -72,107 +69,31 @@ def must_move(case, keys):
         [k for k in keys if k.startswith("linear_weight_layer.")]
 
 
-def _probe(model, batch, case):
-    """-> (logit0, pred0, pair_share) of one eval forward of `batch`"""
-    import torch
-    logits = []
-    h_logit = model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    with torch.no_grad():
-        p0 = model.forward(batch)["y_pred"]
-        logit0 = logits[-1].clone()
-        top = float(logit0.abs().max())
+def probe(model, batch, case):
+    with probing(model, batch) as forward:
+        logit0, p0 = forward()
         w = interaction_weight(model, case)
         kept = w.detach().clone()
         w.zero_()
-        model.forward(batch)
+        share = logit_share(forward()[0], logit0)
         w.copy_(kept)
-        share = float((logits[-1] - logit0).abs().max() / top)
-    h_logit.remove()
-    return logit0, p0, share
+    return logit0, p0, {"pair_share": share}
+
+
+def finish(out, model, case, fmap):
+    import numpy as np
+    want = must_move(case, [k[7:] for k in out if k.startswith("state1/")])
+    moved = [k for k in want if not np.array_equal(out["state1/" + k], out["state0/" + k])]
+    assert moved == want, (case["name"], want, moved)
+    return {"n_pairs": fmap.num_fields * (fmap.num_fields - 1) // 2, "moved": moved}
 
 
 def run_case(case):
-    import numpy as np
-    import torch
-    from fuxictr.features import FeatureMap
-    from fuxictr.pytorch.torch_utils import seed_everything
-    name = case["name"]
-    spec = small_criteo_spec(name, case["n_dense"], case["cards"])
-    os.makedirs(os.path.join(TMP, name), exist_ok=True)
-    fm_path = os.path.join(TMP, name, "feature_map.json")
-    with open(fm_path, "w") as f:
-        json.dump(spec, f)
-    seed_everything(case["seed"])
-    torch.set_num_threads(8)
-    fmap = FeatureMap(name, os.path.join(TMP, name))
-    fmap.load(fm_path, {"embedding_dim": case["embedding_dim"]})
-    model = build_reference(case, fmap)
-    model._max_gradient_norm = case["max_norm"]
-    rng = np.random.default_rng(case["seed"])
-    batches = make_batches(rng, spec, case["B"], case["steps"] + 1)
-
-    def to_torch(b):
-        return {k: torch.from_numpy(v) for k, v in b.items()}
-    tables = [p for k, p in model.named_parameters()
-              if k.startswith("embedding_layer.") and p.dim() == 2 and p.shape[0] > 1 and p.shape[1] > 1]
-    model.eval()
-    scale = case["emb_scale"]
-    with torch.no_grad():
-        for p in tables:
-            p.mul_(scale)
-    while True:
-        logit0, p0, share = _probe(model, to_torch(batches[-1]), case)
-        if share >= 0.05:
-            break
-        assert scale * 2.0 <= case["emb_scale_max"], (name, scale, share)
-        scale *= 2.0
-        with torch.no_grad():
-            for p in tables:
-                p.mul_(2.0)
-    out = {}
-    for k, v in model.state_dict().items():
-        out["state0/" + k] = v.detach().cpu().numpy().copy()
-    logits = []
-    model.output_activation.register_forward_pre_hook(lambda m, inp: logits.append(inp[0].detach().clone()))
-    out["expect/pred0"] = p0.numpy().reshape(-1).copy()
-    out["expect/logit0"] = logit0.numpy().reshape(-1).copy()
-    model.train()
-    losses = []
-    for i in range(case["steps"]):
-        losses.append(float(model.train_step(to_torch(batches[i])).item()))
-    assert all(a != b for a, b in zip(losses, losses[1:])), losses
-    out["expect/loss"] = np.asarray(losses, dtype=np.float64)
-    model.eval()
-    with torch.no_grad():
-        p1 = model.forward(to_torch(batches[-1]))["y_pred"]
-    out["expect/pred1"] = p1.numpy().reshape(-1).copy()
-    out["expect/logit1"] = logits[-1].numpy().reshape(-1).copy()
-    keys = list(model.state_dict().keys())
-    for k, v in model.state_dict().items():
-        out["state1/" + k] = v.detach().cpu().numpy().copy()
-    want = must_move(case, keys)
-    moved = [k for k in want if not np.array_equal(out["state1/" + k], out["state0/" + k])]
-    assert moved == want, (name, want, moved)
-    for i, b in enumerate(batches):
-        for k, v in b.items():
-            out["batch%d/%s" % (i, k)] = v
-    meta = dict(case)
-    meta["spec"] = spec
-    meta["torch"] = torch.__version__
-    meta["emb_scale_used"] = scale
-    meta["n_pairs"] = fmap.num_fields * (fmap.num_fields - 1) // 2
-    meta["moved"] = moved
-    meta["pair_share"] = round(share, 3)
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(OUT_DIR, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(name, "loss", losses, "scale", scale, "pair_share", round(share, 3), "moved", moved, "->", path,
-          os.path.getsize(path) // 1024, "KiB")
+    # the interaction's tables alone: FwFM's FeLV keeps a second set of [V, D] tables under linear_weight_layer, which
+    # counts as a weight and keeps its scale
+    record_case(case, build_reference, probe, lambda shares, case: shares["pair_share"] >= 0.05, finish,
+                is_table=lambda k: k.startswith("embedding_layer."))
 
 
 if __name__ == "__main__":
-    _import_reference()
-    only = sys.argv[1:]
-    for case in CASES:
-        if not only or case["name"] in only:
-            run_case(case)
+    main(CASES, run_case)

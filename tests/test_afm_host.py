@@ -10,15 +10,17 @@ Stated tolerances (those of tests/test_gpu_models.py): logits 1e-4, pred atol 2e
 weights through conftest.assert_weights_close."""
 import os
 
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
 import _cpu_emul
 from conftest import GOLDEN, Golden, assert_weights_close
+from zoo_cases import LOGIT_TOL, allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 AFM_CASES = ["afm_adam", "afm_d10_sgd", "afm_noatt", "afm_two_fields", "afm_zoo_test"]
-LOGIT_TOL = 1e-4
 ATT_KEYS = ["attention.0.weight", "attention.0.bias", "attention.2.weight", "weight_p.weight"]
 
 
@@ -108,37 +110,15 @@ def _install(monkeypatch):
 
 def build_afm(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.AFM with a fixture's hyper-parameters and initial weights (shared with tests/test_gpu_afm.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact", attention_dim=m["attention_dim"],
-              use_attention=m["use_attention"])
-    kw.update(extra)
-    model = zoo.AFM(fmap, model_id=m["name"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.AFM, g, tmp_path, gpu=gpu, attention_dim=m["attention_dim"],
+                             use_attention=m["use_attention"], **extra)
 
 
 def _install_all(monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return zoo
 
 
@@ -146,8 +126,12 @@ def _build(g, tmp_path, monkeypatch, **extra):
     return build_afm(_install_all(monkeypatch), g, tmp_path, **extra)
 
 
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
+@contextlib.contextmanager
+def _launches(fwd, bwd):
+    """the launch counters over the block move by exactly (fwd, bwd)"""
+    before = dict(CALLS)
+    yield
+    assert [CALLS[k] - before[k] for k in ("afm_attn_fwd", "afm_attn_bwd")] == [fwd, bwd]
 
 
 def _expected_calls(g, fused):
@@ -200,13 +184,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
     assert g.state0["product_layer.triu_index"].shape == (2, F * (F - 1) // 2)
     assert g.state0["lr_layer.bias"].shape == (1,)
     assert not model.product_layer.triu_index.requires_grad
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert CALLS == {"afm_attn_fwd": _expected_calls(g, fused), "afm_attn_bwd": 0}
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    with _launches(_expected_calls(g, fused), 0):
+        check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -214,23 +193,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = []
-    for i in range(g.meta["steps"]):
-        before = dict(CALLS)
-        losses.append(float(model.train_step(tb(g.batches[i])).item()))
-        n = _expected_calls(g, fused)                                # one launch forward, one backward, per step
-        assert CALLS["afm_attn_fwd"] - before["afm_attn_fwd"] == n
-        assert CALLS["afm_attn_bwd"] - before["afm_attn_bwd"] == n
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred1"], atol=2e-5)
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    n = _expected_calls(g, fused)                                    # one launch forward, one backward, per step
+    check_trajectory(model, g, per_step=lambda i: _launches(n, n))
 
 
 def test_fused_switch_follows_the_environment_and_the_defaults_are_the_references(tmp_path, monkeypatch):

@@ -7,16 +7,15 @@ kernels themselves are held to an fp64 restatement in tests/test_gpu_mhsa.py.
 
 Stated tolerances (those of tests/test_gpu_models.py): logits 1e-4, losses 1e-4 per step, trained weights
 through conftest.assert_weights_close."""
-import numpy as np
 import pytest
 import torch
 
 import _cpu_emul
-from conftest import Golden, assert_weights_close
+from conftest import Golden
+from zoo_cases import allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory
 
 AUTOINT_CASES = ["autoint_adam", "autoint_zoo_test", "autoint_scale_wide_sgd", "autoint_nores_nodnn",
                  "autoint_layernorm"]
-LOGIT_TOL = 1e-4
 
 
 def _attend(X, Wq, Wk, Wv, Wres, H, use_scale, residual, relu):
@@ -74,40 +73,18 @@ def _install(monkeypatch):
 
 def build_autoint(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.AutoInt with a fixture's hyper-parameters and initial weights (shared with tests/test_gpu_autoint.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact")
-    kw.update(extra)
-    model = zoo.AutoInt(fmap, model_id=m["name"], dnn_hidden_units=m["hidden"],
-                        attention_layers=m["layers"], num_heads=m["heads"],
-                        attention_dim=m["attention_dim"], layer_norm=m["layer_norm"],
-                        use_scale=m["use_scale"], use_wide=m["use_wide"], use_residual=m["use_residual"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    assert sorted(model.state_dict().keys()) == sorted(sd.keys())         # the reference's checkpoint keys
-    model.load_state_dict(sd)
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.AutoInt, g, tmp_path, gpu=gpu, dnn_hidden_units=m["hidden"],
+                             attention_layers=m["layers"], num_heads=m["heads"], attention_dim=m["attention_dim"],
+                             layer_norm=m["layer_norm"], use_scale=m["use_scale"], use_wide=m["use_wide"],
+                             use_residual=m["use_residual"], **extra)
 
 
 def _build(g, tmp_path, monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return build_autoint(zoo, g, tmp_path)
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
 
 
 @pytest.mark.parametrize("case", AUTOINT_CASES)
@@ -115,28 +92,14 @@ def test_state_dict_keys_and_forward_logits(case, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch)            # (asserts the keys)
     assert any(k.startswith("self_attention.0.W_q.") for k in g.state0)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("case", AUTOINT_CASES)
 def test_training_trajectory_and_trained_weights(case, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g)
 
 
 def test_fixtures_exercise_softmax_and_relu():

@@ -16,10 +16,10 @@ import pytest
 import torch
 
 import _cpu_emul
-from conftest import Golden, assert_weights_close
+from conftest import Golden
+from zoo_cases import LOGIT_TOL, allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 BST_CASES = ["bst_pair_adam", "bst_zoo_test", "bst_single_causal_sgd", "bst_concat_two_layers", "bst_plain"]
-LOGIT_TOL = 1e-4
 POOLS = {"none": 0, "concat": 0, "mean": 1, "sum": 2, "target": 3}
 
 
@@ -129,40 +129,19 @@ def _field(f):
 
 def build_bst(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.BST with a fixture's hyper-parameters and initial weights (shared with tests/test_gpu_bst.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=0, net_regularizer=0, sparse_update="exact")
-    kw.update(extra)
-    model = zoo.BST(fmap, model_id=m["name"], dnn_hidden_units=m["hidden"], dnn_activations="relu",
-                    num_heads=m["heads"], stacked_transformer_layers=m["layers"], layer_norm=m["layer_norm"],
-                    use_residual=m["use_residual"], bst_target_field=[_field(f) for f in m["bst_target"]],
-                    bst_sequence_field=[_field(f) for f in m["bst_sequence"]], seq_pooling_type=m["pooling"],
-                    use_position_emb=m["use_position_emb"], use_causal_mask=m["causal"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    assert sorted(model.state_dict().keys()) == sorted(sd.keys())         # the reference's checkpoint keys
-    model.load_state_dict(sd)
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.BST, g, tmp_path, gpu=gpu, dnn_hidden_units=m["hidden"], dnn_activations="relu",
+                             num_heads=m["heads"], stacked_transformer_layers=m["layers"], layer_norm=m["layer_norm"],
+                             use_residual=m["use_residual"], bst_target_field=[_field(f) for f in m["bst_target"]],
+                             bst_sequence_field=[_field(f) for f in m["bst_sequence"]], seq_pooling_type=m["pooling"],
+                             use_position_emb=m["use_position_emb"], use_causal_mask=m["causal"], **extra)
 
 
 def _build(g, tmp_path, monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return build_bst(zoo, g, tmp_path)
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
 
 
 def test_zoo_bst_is_importable():
@@ -179,31 +158,17 @@ def test_state_dict_keys_and_forward_logits(case, tmp_path, monkeypatch):
     assert "transformer_encoders.0.transformer_blocks.0.attention.out_proj.bias" in g.state0
     assert "transformer_encoders.0.transformer_blocks.0.ffn.2.weight" in g.state0
     assert ("transformer_encoders.0.position_emb" in g.state0) == g.meta["use_position_emb"]
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("case", BST_CASES)
 def test_training_trajectory_and_trained_weights(case, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    sd = model.state_dict()
     if g.meta["use_position_emb"]:
         k = "transformer_encoders.0.position_emb"
         assert np.abs(g.state1[k] - g.state0[k]).max() > 0           # trained in the reference ...
-    for k, ref in g.state1.items():                                   # ... and held here with every other weight
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g)                                        # ... and held here with every other weight
 
 
 def test_fixtures_exercise_softmax_lrelu_and_padding():

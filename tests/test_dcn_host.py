@@ -9,15 +9,17 @@ tests/test_gpu_crossnet.py.
 
 Stated tolerances (those of tests/test_gpu_models.py): logits 1e-4, predictions atol 2e-5, losses 1e-4 per step,
 trained weights through conftest.assert_weights_close."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
 import _cpu_emul
-from conftest import Golden, assert_weights_close
+from conftest import Golden
+from zoo_cases import LOGIT_TOL, allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 DCN_CASES = ["dcn_adam", "dcn_d10_sgd", "dcn_cross_only", "dcn_one_layer", "dcn_zoo_test"]
-LOGIT_TOL = 1e-4
 
 
 # ---- the formulas, in the dtype of the arguments ----------------------------------------------------------
@@ -95,37 +97,15 @@ def _install(monkeypatch):
 
 def build_dcn(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.DCN with a fixture's hyper-parameters and initial weights (shared with tests/test_gpu_dcn.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact", dnn_hidden_units=m["dnn"],
-              dnn_activations="relu", num_cross_layers=m["n_cross"])
-    kw.update(extra)
-    model = zoo.DCN(fmap, model_id=m["name"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.DCN, g, tmp_path, gpu=gpu, dnn_hidden_units=m["dnn"], dnn_activations="relu",
+                             num_cross_layers=m["n_cross"], **extra)
 
 
 def _install_all(monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return zoo
 
 
@@ -133,8 +113,12 @@ def _build(g, tmp_path, monkeypatch, **extra):
     return build_dcn(_install_all(monkeypatch), g, tmp_path, **extra)
 
 
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
+@contextlib.contextmanager
+def _counted(want):
+    """the launch counters over the block: reset before, `want` after"""
+    _reset_calls()
+    yield
+    assert CALLS == want
 
 
 def _aliases_packed(layer):
@@ -191,14 +175,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
     assert (model.dnn is None) == (not m["dnn"])
     assert any(k.startswith("dnn.") for k in g.state0) == bool(m["dnn"])
     assert _aliases_packed(model.crossnet)                           # still, after load_state_dict
-    model.eval()
-    _reset_calls()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert CALLS == {"cross_net_fwd": 1 if fused else 0, "cross_net_bwd": 0}
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    with _counted({"cross_net_fwd": 1 if fused else 0, "cross_net_bwd": 0}):
+        check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -206,22 +184,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = []
-    for i in range(g.meta["steps"]):
-        _reset_calls()
-        losses.append(float(model.train_step(tb(g.batches[i])).item()))
-        # the whole stack: exactly one launch-pair per step, or none of either
-        assert CALLS == ({"cross_net_fwd": 1, "cross_net_bwd": 1} if fused else {"cross_net_fwd": 0, "cross_net_bwd": 0})
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred1"], atol=2e-5)
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    n = 1 if fused else 0                  # the whole stack: exactly one launch-pair per step, or none of either
+    check_trajectory(model, g, per_step=lambda i: _counted({"cross_net_fwd": n, "cross_net_bwd": n}))
     assert _aliases_packed(model.crossnet)                           # the optimizer updated the packed storage
     for i in range(g.meta["n_cross"]):                               # ... and it moved
         assert not np.array_equal(model.crossnet._w[i].numpy(), g.state0["crossnet.cross_net.%d.weight.weight" % i][0])

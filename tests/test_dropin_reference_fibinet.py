@@ -4,48 +4,22 @@ the reference's unmodified `model_zoo.FiBiNET` is constructed from layers.Squeez
 layers.BilinearInteractionV2 (the unfused composition: V, the two branch tensors and their cat) and — with the
 kernels replaced by the CPU emulations of tests/_cpu_emul.py and tests/test_fibinet_host.py — reproduces the
 fixtures the same class produced on the stock torch layers."""
-import numpy as np
 import pytest
-import torch
 
-from conftest import Golden, assert_weights_close
+from conftest import Golden
 from test_dropin_reference_zoo import pytestmark, patched_reference  # noqa: F401  (skip rule, fixture)
-from test_fibinet_host import FIBINET_CASES, _install, tb
+from test_fibinet_host import FIBINET_CASES, _install
+from zoo_cases import check_dropin
 
 
 @pytest.mark.parametrize("case", FIBINET_CASES)
 def test_reference_fibinet_runs_on_the_native_layers(case, patched_reference, monkeypatch, tmp_path):  # noqa: F811
     _install(monkeypatch)
     from fuxictr_amd import layers
-    from fuxictr_amd.features import FeatureMap
     from model_zoo import FiBiNET
     g = Golden(case)
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    model = FiBiNET(fmap, model_id=m["name"], gpu=-1, embedding_dim=m["embedding_dim"], learning_rate=m["lr"],
-                    optimizer=m["optimizer"], loss="binary_crossentropy", task="binary_classification",
-                    metrics=["logloss", "AUC"], verbose=0, model_root=str(tmp_path),
-                    embedding_regularizer=m.get("emb_reg", 0), net_regularizer=m.get("net_reg", 0),
-                    hidden_units=m["hidden"], excitation_activation=m["excitation"],
-                    reduction_ratio=m["ratio"], bilinear_type=m["bilinear_type"])
-    assert type(model.senet_layer) is layers.SqueezeExcitation
-    assert type(model.bilinear_interaction1) is layers.BilinearInteractionV2
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    assert sorted(model.state_dict().keys()) == sorted(sd.keys())
-    model.load_state_dict(sd, strict=True)
-    model._max_gradient_norm = m["max_norm"]
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(m["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    out = model.state_dict()
-    for k, ref in g.state1.items():
-        if ref.dtype.kind == "i":
-            assert np.array_equal(out[k].numpy(), ref), k
-        else:
-            assert_weights_close(out[k].numpy(), ref, m["lr"], m["steps"], k)
+    check_dropin(FiBiNET, g, tmp_path, [("senet_layer", layers.SqueezeExcitation),
+                                        ("bilinear_interaction1", layers.BilinearInteractionV2)],
+                 hidden_units=m["hidden"], excitation_activation=m["excitation"], reduction_ratio=m["ratio"],
+                 bilinear_type=m["bilinear_type"])

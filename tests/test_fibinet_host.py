@@ -8,15 +8,14 @@ themselves are held to an fp64 restatement in tests/test_gpu_bilinear.py.
 
 Stated tolerances (those of tests/test_gpu_models.py): logits 1e-4, losses 1e-4 per step, trained weights
 through conftest.assert_weights_close."""
-import numpy as np
 import pytest
 import torch
 
 import _cpu_emul
 from conftest import Golden, assert_weights_close
+from zoo_cases import allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 FIBINET_CASES = ["fibinet_adam", "fibinet_zoo_test", "fibinet_each_sigmoid_sgd", "fibinet_all_nodnn"]
-LOGIT_TOL = 1e-4
 
 
 def senet_reference(X, W1, W2, act):
@@ -102,43 +101,17 @@ def _install(monkeypatch):
 
 def build_fibinet(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.FiBiNET with a fixture's hyper-parameters and initial weights (shared with tests/test_gpu_fibinet.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact")
-    kw.update(extra)
-    model = zoo.FiBiNET(fmap, model_id=m["name"], hidden_units=m["hidden"],
-                        excitation_activation=m["excitation"], reduction_ratio=m["ratio"],
-                        bilinear_type=m["bilinear_type"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.FiBiNET, g, tmp_path, gpu=gpu, hidden_units=m["hidden"],
+                             excitation_activation=m["excitation"], reduction_ratio=m["ratio"],
+                             bilinear_type=m["bilinear_type"], **extra)
 
 
 def _build(g, tmp_path, monkeypatch, **extra):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return build_fibinet(zoo, g, tmp_path, **extra)
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -151,12 +124,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
         assert k in g.state0, k
     tri = model.bilinear_interaction1.triu_index
     assert tri.dtype == torch.int64 and not tri.requires_grad
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -164,19 +132,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        if ref.dtype.kind == "i":
-            assert np.array_equal(sd[k].numpy(), ref), k             # triu_index: untouched by the optimizer
-        else:
-            assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g)
 
 
 @pytest.mark.parametrize("case", FIBINET_CASES)

@@ -15,10 +15,10 @@ import torch
 
 import _cpu_emul
 from conftest import Golden, assert_weights_close
+from zoo_cases import allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 FINALMLP_CASES = ["finalmlp_adam", "finalmlp_ctx_sgd", "finalmlp_mixed", "finalmlp_nofs_heads4",
                   "finalmlp_zoo_test", "dualmlp_adam"]
-LOGIT_TOL = 1e-4
 
 
 # ---- the formulas, in the dtype of the arguments ----------------------------------------------------------
@@ -108,48 +108,21 @@ def _install(monkeypatch):
 def build_finalmlp(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.FinalMLP / zoo.DualMLP with a fixture's hyper-parameters and initial weights (shared with
     tests/test_gpu_finalmlp.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact", mlp1_hidden_units=m["mlp1"],
-              mlp2_hidden_units=m["mlp2"])
-    kw.update(extra)
+    kw = dict(extra, mlp1_hidden_units=m["mlp1"], mlp2_hidden_units=m["mlp2"])
     if m["model"] == "DualMLP":
         kw.pop("fused", None)
-        model = zoo.DualMLP(fmap, model_id=m["name"], **kw)
-    else:
-        model = zoo.FinalMLP(fmap, model_id=m["name"], use_fs=m["use_fs"], fs_hidden_units=m["fs_hidden"],
+        return build_from_golden(zoo.DualMLP, g, tmp_path, gpu=gpu, **kw)
+    return build_from_golden(zoo.FinalMLP, g, tmp_path, gpu=gpu, use_fs=m["use_fs"], fs_hidden_units=m["fs_hidden"],
                              fs1_context=m["fs1_context"], fs2_context=m["fs2_context"], num_heads=m["num_heads"],
                              **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
 
 
 def _build(g, tmp_path, monkeypatch, **extra):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return build_finalmlp(zoo, g, tmp_path, **extra)
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -171,12 +144,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
     else:
         assert "mlp1.mlp.0.weight" in g.state0 and "mlp2.mlp.0.weight" in g.state0
         assert not any("fusion_module" in k or "fs_module" in k for k in g.state0)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -184,16 +152,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g)
 
 
 @pytest.mark.parametrize("case", [c for c in FINALMLP_CASES if c != "dualmlp_adam"])

@@ -15,9 +15,9 @@ import torch
 
 import _cpu_emul
 from conftest import Golden, assert_weights_close
+from zoo_cases import allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 GDCN_CASES = ["gdcn_adam", "gdcnp_adam", "gdcn_d10_sgd", "gdcnp_one_layer", "gdcnp_zoo_test"]
-LOGIT_TOL = 1e-4
 
 
 # ---- the formulas, in the dtype of the arguments ----------------------------------------------------------
@@ -86,46 +86,20 @@ def _install(monkeypatch):
 def build_gdcn(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.GDCN / zoo.GDCNP with a fixture's hyper-parameters and initial weights (shared with
     tests/test_gpu_gdcn.py)."""
-    from fuxictr_amd.features import FeatureMap
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-              net_regularizer=m.get("net_reg", 0), sparse_update="exact", dnn_hidden_units=m["dnn"],
-              dnn_activations="relu", num_cross_layers=m["n_cross"])
-    kw.update(extra)
-    model = (zoo.GDCNP if m["model"] == "GDCNP" else zoo.GDCN)(fmap, model_id=m["name"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    return build_from_golden(zoo.GDCNP if m["model"] == "GDCNP" else zoo.GDCN, g, tmp_path, gpu=gpu,
+                             dnn_hidden_units=m["dnn"], dnn_activations="relu", num_cross_layers=m["n_cross"], **extra)
 
 
 def _install_all(monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return zoo
 
 
 def _build(g, tmp_path, monkeypatch, **extra):
     return build_gdcn(_install_all(monkeypatch), g, tmp_path, **extra)
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
 
 
 def _aliases_packed(layer):
@@ -156,12 +130,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
     if m["model"] == "GDCNP":
         assert g.state0["fc.weight"].shape == (1, width + m["dnn"][-1])
     assert _aliases_packed(model.cross_net)                          # still, after load_state_dict
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -169,16 +138,7 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g)
     assert _aliases_packed(model.cross_net)                          # the optimizer updated the packed storage
 
 

@@ -7,18 +7,17 @@ The attention layer alone (layers.afm_attention and the module-by-module composi
 with the yardstick of tests/test_gpu_layernorm.py: 4 * e32 + 1e-6 * max|ref| per tensor, e32 the error of the fp32
 torch composition on the CPU.
 """
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from conftest import Golden, assert_weights_close  # noqa: E402
+from conftest import Golden  # noqa: E402
 from fuxictr_amd import layers, zoo  # noqa: E402
-from test_afm_host import AFM_CASES, afm_pairs, afm_reference, build_afm, tb  # noqa: E402
+from test_afm_host import AFM_CASES, afm_pairs, afm_reference, build_afm  # noqa: E402
 from test_gpu_layernorm import compare, f32_exact  # noqa: E402
+from zoo_cases import check_forward, check_graph_replay, check_trajectory  # noqa: E402
 
-LOGIT_TOL = 1e-4
 DEV = "cuda:0"
 
 
@@ -31,13 +30,7 @@ def build_native(g, tmp_path, hip_graph=False, fused=True):
 def test_forward_logits_match_reference(case, fused, tmp_path):
     g = Golden(case)
     model = build_native(g, tmp_path, fused=fused)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    err = np.abs(p._fx_logit.reshape(-1).cpu().numpy() - g.expect["logit0"]).max()
-    print(case, "max |logit - reference| %.3e" % err)
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).cpu().numpy(), g.expect["pred0"], atol=2e-5)
+    check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -45,19 +38,7 @@ def test_forward_logits_match_reference(case, fused, tmp_path):
 def test_training_trajectory_matches_reference(case, fused, tmp_path):
     g = Golden(case)
     model = build_native(g, tmp_path, fused=fused)
-    model.train()
-    losses = [float(model.train_step(tb(g.batches[i])).item()) for i in range(g.meta["steps"])]
-    print(case, "max |loss - reference| %.3e" % np.abs(np.asarray(losses) - g.expect["loss"]).max())
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()                                   # flushes pending zero-gradient steps
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).cpu().numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    np.testing.assert_allclose(p.reshape(-1).cpu().numpy(), g.expect["pred1"], atol=2e-5)
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].cpu().numpy(), ref, g.meta["lr"], g.meta["steps"], k)
-    model.optimizer.check_errors()
+    check_trajectory(model, g)
 
 
 def _torch_results(inp, dtype):
@@ -124,20 +105,4 @@ def test_hip_graph_replay_is_bit_identical_to_eager(tmp_path):
     """`hip_graph: true` replays the captured step: same kernels, same order -> same bits (no atomics in the two
     kernels); the capture really happened (`_graph_state`), it did not fall back to eager."""
     g = Golden("afm_adam")
-    eager = build_native(g, tmp_path, hip_graph=False)
-    graph = build_native(g, tmp_path, hip_graph=True)
-    eager.train()
-    graph.train()
-    n = len(g.batches)
-    for i in range(9):                       # eager warm-ups + probe + replays
-        b = tb(g.batches[i % n])
-        le = float(eager.train_step(b).item())
-        lg = float(graph.train_step(b).item())
-        assert le == lg, (i, le, lg)
-    assert graph._graph_state is not None
-    eager.eval()
-    graph.eval()
-    se, sg = eager.state_dict(), graph.state_dict()
-    for k in se:
-        assert torch.equal(se[k], sg[k]), k
-    graph.optimizer.check_errors()
+    check_graph_replay(lambda hip_graph: build_native(g, tmp_path, hip_graph=hip_graph), g)

@@ -13,83 +13,45 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from conftest import Golden, assert_weights_close, _din_fields  # noqa: E402
+from conftest import Golden, _din_fields  # noqa: E402
 from fuxictr_amd import synthetic, zoo  # noqa: E402
-from fuxictr_amd.features import FeatureMap  # noqa: E402
 from oracle import ctr_oracle as O  # noqa: E402
-
-LOGIT_TOL = 1e-4
+from zoo_cases import build_from_golden, check_forward, check_graph_replay, check_trajectory, tb  # noqa: E402
 
 
 def build_native(g, tmp_path, sparse_update="exact", optimizer=None, hip_graph=False):
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    common = dict(gpu=0, embedding_dim=m["embedding_dim"], learning_rate=m["lr"],
-                  optimizer=optimizer or m["optimizer"], loss="binary_crossentropy",
-                  task="binary_classification", metrics=["logloss", "AUC"], verbose=0,
-                  model_root=str(tmp_path), embedding_regularizer=m.get("emb_reg", 0),
-                  net_regularizer=m.get("net_reg", 0),
-                  sparse_update=sparse_update, hip_graph=hip_graph)
     if m["model"] == "DeepFM":
-        model = zoo.DeepFM(fmap, model_id=m["name"], hidden_units=m["hidden"],
-                           batch_norm=m.get("batch_norm", False), **common)
+        cls, own = zoo.DeepFM, dict(hidden_units=m["hidden"], batch_norm=m.get("batch_norm", False))
     elif m["model"] == "xDeepFM":
-        model = zoo.xDeepFM(fmap, model_id=m["name"], dnn_hidden_units=m["hidden"],
-                            cin_hidden_units=m["cin"], **common)
+        cls, own = zoo.xDeepFM, dict(dnn_hidden_units=m["hidden"], cin_hidden_units=m["cin"])
     elif m["model"] == "DLRM":
-        model = zoo.DLRM(fmap, model_id=m["name"], top_mlp_units=m["hidden"],
-                         bottom_mlp_units=m["bottom"], interaction_op=m.get("interaction_op", "dot"), **common)
+        cls, own = zoo.DLRM, dict(top_mlp_units=m["hidden"], bottom_mlp_units=m["bottom"],
+                                  interaction_op=m.get("interaction_op", "dot"))
     elif m["model"] == "DIN":
-        model = zoo.DIN(fmap, model_id=m["name"], dnn_hidden_units=m["hidden"],
-                        dnn_activations="relu", attention_hidden_units=m["att_hidden"],
-                        attention_hidden_activations="Dice", din_target_field=_din_fields(m, "din_target", "adgroup_id"),
-                        din_sequence_field=_din_fields(m, "din_sequence", "click_sequence"),
-                        din_use_softmax=m.get("din_softmax", False), **common)
+        cls, own = zoo.DIN, dict(dnn_hidden_units=m["hidden"], dnn_activations="relu",
+                                 attention_hidden_units=m["att_hidden"], attention_hidden_activations="Dice",
+                                 din_target_field=_din_fields(m, "din_target", "adgroup_id"),
+                                 din_sequence_field=_din_fields(m, "din_sequence", "click_sequence"),
+                                 din_use_softmax=m.get("din_softmax", False))
     else:
-        model = zoo.DCNv2(fmap, model_id=m["name"], model_structure=m.get("structure", "parallel"),
-                          num_cross_layers=m["n_cross"], parallel_dnn_hidden_units=m["hidden"], stacked_dnn_hidden_units=m.get("stacked", []),
-                          **common)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    assert sorted(model.state_dict().keys()) == sorted(sd.keys())   # reference checkpoint keys
-    model.load_state_dict(sd)
-    model._max_gradient_norm = m["max_norm"]
-    return model
-
-
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
+        cls, own = zoo.DCNv2, dict(model_structure=m.get("structure", "parallel"), num_cross_layers=m["n_cross"],
+                                   parallel_dnn_hidden_units=m["hidden"], stacked_dnn_hidden_units=m.get("stacked", []))
+    return build_from_golden(cls, g, tmp_path, gpu=0, optimizer=optimizer or m["optimizer"],
+                             sparse_update=sparse_update, hip_graph=hip_graph, **own)
 
 
 def test_forward_logits_match_reference(golden, tmp_path):
     model = build_native(golden, tmp_path)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(golden.batches[-1]))["y_pred"]
-    logit = p._fx_logit.reshape(-1).cpu().numpy()
-    err = np.abs(logit - golden.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
+    err, pred = check_forward(model, golden, "0")
     assert err <= 2e-5, "fp32 MFMA path is expected to be far inside the 1e-4 budget: %g" % err
-    np.testing.assert_allclose(p.reshape(-1).cpu().numpy(), golden.expect["pred0"], atol=2e-6)
+    np.testing.assert_allclose(pred, golden.expect["pred0"], atol=2e-6)
 
 
 def test_training_trajectory_matches_reference(golden, tmp_path):
     """`exact` sparse update == the reference's dense clip + Adam/SGD over every parameter."""
     model = build_native(golden, tmp_path)
-    model.train()
-    losses = []
-    for i in range(golden.meta["steps"]):
-        losses.append(float(model.train_step(tb(golden.batches[i])).item()))
-    np.testing.assert_allclose(losses, golden.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()                                   # flushes pending zero-gradient steps
-    with torch.no_grad():
-        p = model.forward(tb(golden.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).cpu().numpy() - golden.expect["logit1"]).max() <= LOGIT_TOL
-    np.testing.assert_allclose(p.reshape(-1).cpu().numpy(), golden.expect["pred1"], atol=2e-5)
-    sd = model.state_dict()
-    for k, ref in golden.state1.items():
-        assert_weights_close(sd[k].cpu().numpy(), ref, golden.meta["lr"], golden.meta["steps"], k)
-    model.optimizer.check_errors()
+    check_trajectory(model, golden)
 
 
 def test_auc_matches_oracle_to_4_decimals(tmp_path):
@@ -154,23 +116,7 @@ def test_lazy_mode_runs_and_differs_only_on_idle_rows(tmp_path):
 def test_hip_graph_replay_is_bit_identical_to_eager(case, tmp_path):
     """`hip_graph: true` replays the captured step; same kernels, same order -> same bits."""
     g = Golden(case)
-    eager = build_native(g, tmp_path, hip_graph=False)
-    graph = build_native(g, tmp_path, hip_graph=True)
-    eager.train()
-    graph.train()
-    n = len(g.batches)
-    for i in range(9):                       # 3 eager warm-ups + probe + replays
-        b = tb(g.batches[i % n])
-        le = float(eager.train_step(b).item())
-        lg = float(graph.train_step(b).item())
-        assert le == lg, (i, le, lg)
-    assert graph._graph_state is not None
-    eager.eval()
-    graph.eval()
-    se, sg = eager.state_dict(), graph.state_dict()
-    for k in se:
-        assert torch.equal(se[k], sg[k]), k
-    graph.optimizer.check_errors()
+    check_graph_replay(lambda hip_graph: build_native(g, tmp_path, hip_graph=hip_graph), g)
 
 
 def test_bad_id_raises_like_the_reference(tmp_path):

@@ -11,17 +11,19 @@ Stated tolerances (those of tests/test_gpu_models.py): logits 1e-4, pred atol 2e
 weights through conftest.assert_weights_close."""
 import os
 
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
 import _cpu_emul
 from conftest import GOLDEN, Golden, assert_weights_close
+from zoo_cases import OMIT, allow_cpu_optimizer, build_from_golden, check_forward, check_trajectory, tb
 
 FMFM_CASES = ["fmfm_matrixed_adam", "fmfm_matrixed_d10_sgd", "fmfm_vectorized", "fmfm_two_fields", "fmfm_zoo_test"]
 FWFM_CASES = ["fwfm_filv_adam", "fwfm_felv_sgd", "fwfm_lw", "fwfm_zoo_test"]
 PAIRFM_CASES = FMFM_CASES + FWFM_CASES
-LOGIT_TOL = 1e-4
 
 
 # ---- the formulas, in the dtype of the arguments ----------------------------------------------------------
@@ -115,40 +117,18 @@ def _install(monkeypatch):
 
 def build_pairfm(zoo, g, tmp_path, gpu=-1, **extra):
     """zoo.FwFM / zoo.FmFM with a fixture's hyper-parameters and initial weights (shared with
-    tests/test_gpu_pairfm.py)."""
-    from fuxictr_amd.features import FeatureMap
+    tests/test_gpu_pairfm.py).  Both take one `regularizer`, which feeds the embedding and the net regularizer."""
     m = g.meta
-    fmap = FeatureMap(g.spec["dataset_id"], str(tmp_path))
-    fmap.load_dict(g.spec, {"embedding_dim": m["embedding_dim"]})
-    kw = dict(gpu=gpu, embedding_dim=m["embedding_dim"], learning_rate=m["lr"], optimizer=m["optimizer"],
-              loss="binary_crossentropy", task="binary_classification", metrics=["logloss", "AUC"],
-              verbose=0, model_root=str(tmp_path), regularizer=m["regularizer"], sparse_update="exact")
-    if m["model"] == "FmFM":
-        kw["field_interaction_type"] = m["field_interaction_type"]
-    else:
-        kw["linear_type"] = m["linear_type"]
-    kw.update(extra)
-    model = getattr(zoo, m["model"])(fmap, model_id=m["name"], **kw)
-    sd = {k: torch.from_numpy(v) for k, v in g.state0.items()}
-    got = model.state_dict()
-    assert sorted(got.keys()) == sorted(sd.keys())                        # the reference's checkpoint keys
-    for k, v in sd.items():
-        assert tuple(got[k].shape) == tuple(v.shape) and got[k].dtype == v.dtype, k
-    result = model.load_state_dict(sd, strict=True)
-    assert not result.missing_keys and not result.unexpected_keys
-    model._max_gradient_norm = m["max_norm"]
-    return model
+    own = {"field_interaction_type": m["field_interaction_type"]} if m["model"] == "FmFM" else \
+        {"linear_type": m["linear_type"]}
+    return build_from_golden(getattr(zoo, m["model"]), g, tmp_path, gpu=gpu, regularizer=m["regularizer"],
+                             embedding_regularizer=OMIT, net_regularizer=OMIT, **own, **extra)
 
 
 def _install_all(monkeypatch):
     _install(monkeypatch)
-    from fuxictr_amd import optim, zoo
-    orig = optim._NativeOptimizer.__init__
-
-    def init(self, params, lr, model=None, **kw):      # the product optimizer refuses CPU parameters
-        self._require_cuda = False
-        orig(self, params, lr, model=model, **kw)
-    monkeypatch.setattr(optim._NativeOptimizer, "__init__", init)
+    allow_cpu_optimizer(monkeypatch)
+    from fuxictr_amd import zoo
     return zoo
 
 
@@ -156,8 +136,12 @@ def _build(g, tmp_path, monkeypatch, **extra):
     return build_pairfm(_install_all(monkeypatch), g, tmp_path, **extra)
 
 
-def tb(b):
-    return {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
+@contextlib.contextmanager
+def _launches(fwd, bwd):
+    """the launch counters over the block move by exactly (fwd, bwd)"""
+    before = dict(CALLS)
+    yield
+    assert [CALLS[k] - before[k] for k in ("pairfm_fwd", "pairfm_bwd")] == [fwd, bwd]
 
 
 @pytest.mark.parametrize("mode", ["scalar", "vector", "matrix"])
@@ -232,13 +216,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
         assert g.state0["inner_product_layer.triu_mask"].shape == (F, F)
         if m["linear_type"] == "FiLV":
             assert g.state0["linear_weight_layer.weight"].shape == (1, F * D)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert CALLS == {"pairfm_fwd": 1 if fused else 0, "pairfm_bwd": 0}
-    err = np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit0"]).max()
-    assert err <= LOGIT_TOL, err
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred0"], atol=2e-5)
+    with _launches(1 if fused else 0, 0):
+        check_forward(model, g, "0")
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -246,23 +225,8 @@ def test_state_dict_keys_and_forward_logits(case, fused, tmp_path, monkeypatch):
 def test_training_trajectory_and_trained_weights(case, fused, tmp_path, monkeypatch):
     g = Golden(case)
     model = _build(g, tmp_path, monkeypatch, fused=fused)
-    model.train()
-    losses = []
     n = 1 if fused else 0                                            # one launch forward, one backward, per step
-    for i in range(g.meta["steps"]):
-        before = dict(CALLS)
-        losses.append(float(model.train_step(tb(g.batches[i])).item()))
-        assert CALLS["pairfm_fwd"] - before["pairfm_fwd"] == n
-        assert CALLS["pairfm_bwd"] - before["pairfm_bwd"] == n
-    np.testing.assert_allclose(losses, g.expect["loss"], rtol=0, atol=1e-4)
-    model.eval()
-    with torch.no_grad():
-        p = model.forward(tb(g.batches[-1]))["y_pred"]
-    assert np.abs(p._fx_logit.reshape(-1).numpy() - g.expect["logit1"]).max() <= LOGIT_TOL
-    np.testing.assert_allclose(p.reshape(-1).numpy(), g.expect["pred1"], atol=2e-5)
-    sd = model.state_dict()
-    for k, ref in g.state1.items():
-        assert_weights_close(sd[k].numpy(), ref, g.meta["lr"], g.meta["steps"], k)
+    check_trajectory(model, g, per_step=lambda i: _launches(n, n))
 
 
 def test_fused_switch_follows_the_environment_and_the_defaults_are_the_references(tmp_path, monkeypatch):
