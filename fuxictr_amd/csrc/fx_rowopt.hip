@@ -329,6 +329,20 @@ static int fx_fill_tables(const fx_row_state* tables_host, int32_t n_tables, FxT
         out[t].vec = g.vec;
         out[t].lanes_log2 = ll;
         if (ll > gl) gl = ll;
+        // every lane moves `vec` elements of a field in one access (float4 / float2, uint2 / uint32 of a bf16
+        // table) at row * ld + sub * vec: the field's base and its row stride must be whole multiples of that
+        const struct { const char* name; const void* p; int64_t ld; int eb; } fields[4] = {
+            {"table", h.table, out[t].tld, out[t].bf16 ? 2 : 4}, {"m", h.m, out[t].mld, 4},
+            {"v", h.v, out[t].vld, 4}, {"G", h.G, h.D, 4}};
+        for (const auto& f : fields) {
+            if (f.p == nullptr) continue;
+            if (reinterpret_cast<uintptr_t>(f.p) % (uintptr_t)(g.vec * f.eb) != 0 || f.ld % g.vec != 0) {
+                fx_set_error("%s: table %d field %s (D=%d) is not aligned for %d-element accesses: the pointer "
+                             "must be a multiple of %d bytes and the row stride %lld a multiple of %d",
+                             who, t, f.name, h.D, g.vec, g.vec * f.eb, (long long)f.ld, g.vec);
+                return FX_ERR_INVALID;
+            }
+        }
     }
     *group_log2 = gl;
     return FX_OK;

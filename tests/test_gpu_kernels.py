@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from fuxictr_amd import _lib, ops  # noqa: E402
 from oracle import ctr_oracle as O  # noqa: E402
+from rowopt_cases import within_yardstick  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -218,15 +219,7 @@ def _adam_ref_step(p, g, m, v, t, lr):
     O.adam_dense(p, g, m, v, t, lr)
 
 
-def _within_yardstick(native, ref32, ref64, floor, what):
-    """|native - fp64 Adam| <= max(floor, 1.5 x |torch-fp32 Adam - fp64 Adam|): the reference itself rounds p
-    at every step (k roundings of up to half an ulp each); the native path is held to being as close to the
-    exact trajectory as the reference's own fp32 stepping is, on the same rows, not to a fixed number that one
-    rounding sequence happens to meet."""
-    e_nat = (native.double() - ref64).abs().max().item()
-    e_ref = (ref32.double() - ref64).abs().max().item()
-    assert e_nat <= max(floor, 1.5 * e_ref), (what, e_nat, e_ref)
-    return e_nat, e_ref
+_within_yardstick = within_yardstick      # (tests/rowopt_cases.py: shared with the row-optimizer arm tests)
 
 
 @pytest.mark.parametrize("series", [False, True])
