@@ -10,12 +10,14 @@
 //                      walks sample tiles; the left / right vectors of a tile are gathered into LDS.  The forward
 //                      stores 16 bytes per lane, consecutive lanes consecutive addresses; the dW pass keeps a
 //                      4 x 4 block of one matrix' gradient per thread in registers and writes one partial per
-//                      (sample slab, pair); two fixed-order launches sum them (slabs, then the pairs of a matrix).
+//                      (sample slab, pair); two fixed-order launches sum them: the slabs (fx_rowsum.h's shared
+//                      row sum, as for the squeeze-excitation's weights), then the pairs of a matrix.
 //   dX / dA pass     : a workgroup owns a sample tile with V and dV of all fields in LDS and streams the matrices
 //                      chunk by chunk (pairs of one left field): every (sample, field) sum is formed by one
 //                      workgroup in a fixed order.
 // No atomics anywhere: two launches on the same inputs give the same bits.
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 #define BL_T 256
 #define BL_MAX 64                 // F, D, R
@@ -290,21 +292,8 @@ __global__ __launch_bounds__(BL_T) void k_bl_dw(BlArgs p) {
     }
 }
 
-// dst[o] = sum_t src[t * stride + o], t < nterms: four interleaved slices in fp64, then (s0 + s1) + (s2 + s3)
-__global__ __launch_bounds__(BL_T) void k_bl_reduce_terms(const float* src, int nterms, int64_t stride, int64_t n,
-                                                          float* dst) {
-    __shared__ double red[4][64];
-    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int64_t o = (int64_t)blockIdx.x * 64 + lane;
-    double s = 0.0;
-    if (o < n)
-        for (int t = slice; t < nterms; t += 4) s += (double)src[(int64_t)t * stride + o];
-    red[slice][lane] = s;
-    __syncthreads();
-    if (slice == 0 && o < n) dst[o] = (float)((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
-}
-
 // field_all / field_each: dW[w] = sum over the pairs of matrix w of perpair[p] (blockIdx.y = w), 16 slices in fp64
+// (not fx_rowsum: the rows it adds are a per-matrix range of pairs, in 16 slices)
 __global__ __launch_bounds__(BL_T) void k_bl_reduce_pairs(const float* perpair, int F, int P, int DD, int type,
                                                           float* dW) {
     __shared__ double red[16][16];
@@ -527,9 +516,7 @@ extern "C" int fx_bilinear_bwd(const float* X, int64_t x_ld, int64_t B, int32_t 
     FX_CHECK_LAUNCH();
     const int64_t n = (int64_t)P * DD;
     float* per_pair = type == 2 ? dW : workspace;        // (in place: entry o of slab 0 is read and written by one thread)
-    hipLaunchKernelGGL(k_bl_reduce_terms, dim3((unsigned)fx_ceil_div(n, 64)), dim3(BL_T), 0, s, workspace, q.nslab, n,
-                       n, per_pair);
-    FX_CHECK_LAUNCH();
+    if (int st = fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, q.nslab, n, fx_rowsum_out(per_pair, n))) return st;
     if (type != 2) {
         const dim3 rg((unsigned)fx_ceil_div(DD, 16), (unsigned)(type == 0 ? 1 : F));
         hipLaunchKernelGGL(k_bl_reduce_pairs, rg, dim3(BL_T), 0, s, workspace, F, P, DD, type, dW);
@@ -767,12 +754,7 @@ extern "C" int fx_senet_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, 
     hipLaunchKernelGGL(k_senet_bwd, dim3(grid), dim3(BL_T), lds, s, p);
     FX_CHECK_LAUNCH();
     const int FR = F * R;
-    // partial[g] = [dW1 | dW2]: one reduction over the workgroups for both, then dW1 and dW2 are its halves
-    hipLaunchKernelGGL(k_bl_reduce_terms, dim3((unsigned)fx_ceil_div(FR, 64)), dim3(BL_T), 0, s, workspace, (int)grid,
-                       (int64_t)2 * FR, (int64_t)FR, dW1);
-    FX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_bl_reduce_terms, dim3((unsigned)fx_ceil_div(FR, 64)), dim3(BL_T), 0, s, workspace + FR,
-                       (int)grid, (int64_t)2 * FR, (int64_t)FR, dW2);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    // partial[g] = [dW1 | dW2], rows 2 FR floats apart: one sum over the workgroups for each half
+    if (int st = fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, (int)grid, 2 * FR, fx_rowsum_out(dW1, FR))) return st;
+    return fx_rowsum<double, FX_ROWS_SLICES>(s, workspace + FR, (int)grid, 2 * FR, fx_rowsum_out(dW2, FR));
 }

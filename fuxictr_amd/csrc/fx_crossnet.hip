@@ -294,7 +294,7 @@ __global__ __launch_bounds__(CN_THREADS) void k_cross_net_bwd(CnArgs p) {
 // The G rows of `partial` -> dw, db.  grid (ceil(cols / CN_RED_COLS), L + 1), block (CN_RED_COLS, CN_RED_PARTS):
 // blockIdx.y = j < L sums the column sums of u_j x_0 and writes dw_j; blockIdx.y = L sums those of dout and writes
 // every db_l.  Group y of the block adds the rows y, y + CN_RED_PARTS, ... in that order; the groups and the G sums
-// of t_k meet in a fixed order.
+// of t_k meet in a fixed order.  (Not fx_rowsum.h's row sum: the sums are combined with b and T_k before they leave.)
 __global__ __launch_bounds__(CN_RED_COLS * CN_RED_PARTS) void k_cross_net_reduce(CnArgs p) {
     __shared__ double red[CN_RED_PARTS][CN_RED_COLS];
     __shared__ double tred[CN_MAX_L][CN_RED_PARTS];

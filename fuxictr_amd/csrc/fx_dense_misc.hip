@@ -2,9 +2,10 @@
 // backward mask, the CrossNetV2 backward glue, sigmoid + BCE, and the fused head of the training step
 // (Linear(K -> 1) forward + sigmoid + BCE + the head's backward in one pass).
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 // ---------------------------------------------------------------------------------------------
-// column sums (bias gradient), two deterministic stages
+// column sums (bias gradient), two deterministic stages: FX_COLSUM_CHUNKS row chunks, then fx_rowsum over them
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_colsum_stage1(const float* X, int64_t ldx, int64_t M,
                                                        int64_t N, int64_t rows_per_chunk,
@@ -51,19 +52,6 @@ __global__ __launch_bounds__(256) void k_colsum_stage1_v4(const float* X, int64_
     }
 }
 
-__global__ __launch_bounds__(256) void k_colsum_stage2(const float* ws, int64_t N, int chunks,
-                                                       float* out) {
-    __shared__ float red[256];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int64_t n = (int64_t)blockIdx.x * 64 + tx;
-    float s = 0.f;
-    if (n < N)
-        for (int c = ty; c < chunks; c += 4) s += ws[(int64_t)c * N + n];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (ty == 0 && n < N) out[n] = (red[tx] + red[tx + 64]) + (red[tx + 128] + red[tx + 192]);
-}
-
 extern "C" int fx_colsum(const float* X, int64_t ldx, int64_t M, int64_t N, float* out,
                          float* workspace, fx_stream_t stream) {
     FX_CHECK_ARG(M >= 0 && N >= 0, "fx_colsum: negative dimension");
@@ -81,10 +69,7 @@ extern "C" int fx_colsum(const float* X, int64_t ldx, int64_t M, int64_t N, floa
         hipLaunchKernelGGL(k_colsum_stage1, dim3((unsigned)fx_ceil_div(N, 64), FX_COLSUM_CHUNKS),
                            dim3(256), 0, s, X, ldx, M, N, rpc, workspace);
     FX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_colsum_stage2, dim3((unsigned)fx_ceil_div(N, 64)), dim3(256), 0, s,
-                       workspace, N, (int)FX_COLSUM_CHUNKS, out);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    return fx_rowsum<float, FX_ROWS_SLICES>(s, workspace, (int)FX_COLSUM_CHUNKS, N, fx_rowsum_out(out, N));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -315,6 +300,7 @@ __global__ __launch_bounds__(256) void k_head_train(HeadTrainArgs a) {
 
 // dW[k] = sum over the G slabs (8 elements x 32 slab lanes per workgroup, 8 loads in flight, fixed LDS
 // tree); workgroup 0 also adds the G db / loss partials (G <= 256: one per thread, fixed tree).
+// (not fx_rowsum: 32 slab lanes per column, the 1 / B scale and the db / loss sums ride in the same launch)
 __global__ __launch_bounds__(256) void k_head_reduce(const float* ws, int64_t G, int64_t K, float invB,
                                                      float* dW, float* db, float* loss) {
     __shared__ float red[256];

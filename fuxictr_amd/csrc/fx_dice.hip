@@ -165,6 +165,7 @@ __global__ __launch_bounds__(256) void k_dice_reduce_v4(const float* Z, const fl
 // t[j] = sum over the chunks of term k0 + j of column h = 16 blockIdx.x + (threadIdx.x & 15): every chunk
 // lane (threadIdx.x >> 4) adds the chunks lane, lane + 16, ... with 8 independent loads in flight, then the
 // 16 lane sums are added in lane order.  Valid in the threads of chunk lane 0 with h < H.  One barrier.
+// (not fx_rowsum.h's row sum: 16 chunk lanes and NT terms at once, an order the DIN attention pipeline shares)
 template <int NT>
 __device__ __forceinline__ void fx_chunk_sums(const float* partial, int chunks, int nt, int k0, int64_t H,
                                               int64_t h, float (*red)[16][17], float (&t)[NT]) {

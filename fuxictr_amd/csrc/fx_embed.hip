@@ -8,6 +8,7 @@
 //   :230-259 (stack/cat), fuxictr/pytorch/layers/blocks/logistic_regression.py:55-58,
 //   fuxictr/pytorch/layers/interactions/inner_product.py:55-62.
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 #include <stdlib.h>
 
@@ -347,15 +348,6 @@ __global__ __launch_bounds__(1024) void k_emb_numeric_grad(const float* dout, in
         partial[((int64_t)blockIdx.y * gridDim.x + j) * D + d] = red[d];
 }
 
-__global__ __launch_bounds__(256) void k_emb_numeric_grad_final(const float* partial, int64_t n,
-                                                                int chunks, float* out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int c = 0; c < chunks; ++c) s += partial[(int64_t)c * n + i];
-    out[i] = s;
-}
-
 extern "C" int fx_emb_numeric_grad(const float* dout, int64_t dout_ld,
                                    const int64_t* num_out_off, const float* dense,
                                    int64_t dense_ld, int32_t Fd, int32_t D, int64_t B,
@@ -369,13 +361,13 @@ extern "C" int fx_emb_numeric_grad(const float* dout, int64_t dout_ld,
         hipLaunchKernelGGL(k_emb_numeric_grad, dim3(Fd, FX_NUMGRAD_CHUNKS), dim3(1024), 0,
                            fx_hip_stream(stream), dout, dout_ld, num_out_off, dense, dense_ld,
                            (int)D, Dp, B, workspace);
+        FX_CHECK_LAUNCH();
         const int64_t n = (int64_t)Fd * D;
-        hipLaunchKernelGGL(k_emb_numeric_grad_final, dim3((unsigned)fx_ceil_div(n, 256)), dim3(256),
-                           0, fx_hip_stream(stream), workspace, n, (int)FX_NUMGRAD_CHUNKS, dnum_w);
-    } else {
-        hipLaunchKernelGGL(k_emb_numeric_grad, dim3(Fd, 1), dim3(1024), 0, fx_hip_stream(stream),
-                           dout, dout_ld, num_out_off, dense, dense_ld, (int)D, Dp, B, dnum_w);
+        return fx_rowsum<float, FX_ROWS_SERIAL>(fx_hip_stream(stream), workspace, (int)FX_NUMGRAD_CHUNKS, n,
+                                                fx_rowsum_out(dnum_w, n));
     }
+    hipLaunchKernelGGL(k_emb_numeric_grad, dim3(Fd, 1), dim3(1024), 0, fx_hip_stream(stream),
+                       dout, dout_ld, num_out_off, dense, dense_ld, (int)D, Dp, B, dnum_w);
     FX_CHECK_LAUNCH();
     return FX_OK;
 }

@@ -17,9 +17,11 @@
 // Backward of both: a thread per column chunk and a slab of rows per workgroup row (fm_slabs).  The thread walks the
 // rows of its slab, writes the per-sample gradients (dE, per-sample dZ; dT, dY, g w_x^T) and keeps the sums over
 // the batch (broadcast dZ; dw_x, dw_y, db) in registers: one partial per slab into caller workspace, then
-// k_fm_reduce sums the slabs in a fixed order.  No atomics anywhere: two launches on the same inputs give the same
-// bits.  The sigmoid is recomputed from Z in the backward; nothing is stashed by the forward.
+// fx_rowsum.h's shared row sum adds the slabs in a fixed order (four runs of consecutive slabs, fp32).  No atomics
+// anywhere: two launches on the same inputs give the same bits.  The sigmoid is recomputed from Z in the backward;
+// nothing is stashed by the forward.
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 #define FM_T 256
 #define FM_MAX_WG 2048            // 8 workgroups per CU
@@ -185,37 +187,15 @@ __global__ __launch_bounds__(FM_T) void k_gate2_bwd(GateArgs p) {
     }
 }
 
-// Column i of partial[nslab, C] summed over the slabs: four runs of consecutive slabs, each in slab order by one
-// wave, then the four runs in their order.  The columns are three consecutive segments of n[0], n[1], n[2]; a
-// segment whose pointer is null is skipped (its partials were never written); dup_last writes the last segment's
-// single column twice.
-struct FmOut {
-    float* p[3];
-    int64_t n[3];
-    int dup_last;
-};
-
-__global__ __launch_bounds__(FM_T) void k_fm_reduce(const float* partial, int nslab, int64_t C, FmOut o) {
-    __shared__ float red[4][64];
-    const int col = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 64 + col;
-    float* dst = nullptr;
-    if (i < C) {
-        if (i < o.n[0]) dst = o.p[0] ? o.p[0] + i : nullptr;
-        else if (i < o.n[0] + o.n[1]) dst = o.p[1] ? o.p[1] + (i - o.n[0]) : nullptr;
-        else dst = o.p[2] ? o.p[2] + (i - o.n[0] - o.n[1]) : nullptr;
-    }
-    const int per = (nslab + 3) / 4;
-    const int s0 = q * per, s1 = s0 + per < nslab ? s0 + per : nslab;
-    float t = 0.f;
-    if (dst)
-        for (int s = s0; s < s1; ++s) t += partial[(int64_t)s * C + i];
-    red[q][col] = t;
-    __syncthreads();
-    if (q == 0 && dst) {
-        t = ((red[0][col] + red[1][col]) + red[2][col]) + red[3][col];
+// The head's k_fx_rowsum: [dw_x | dw_y | db] over the slabs, with db, the last column, written twice
+// (db[0] = db[1] = sum g: one for b_x, one for b_y)
+__global__ __launch_bounds__(FM_T) void k_biagg_reduce(const float* partial, int nslab, int64_t C, FxRowsumOut o) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    float* dst = fx_rowsum_dst(o, i);
+    const float t = fx_rowsum_col<float, FX_ROWS_RUNS>(partial, nslab, C, i, dst != nullptr);
+    if (threadIdx.x < 64 && dst) {
         dst[0] = t;
-        if (o.dup_last && i >= o.n[0] + o.n[1]) dst[1] = t;
+        if (i == C - 1) dst[1] = t;
     }
 }
 
@@ -335,12 +315,6 @@ __global__ __launch_bounds__(FM_T) void k_biagg_bwd(AggArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static int fm_reduce(hipStream_t s, const float* partial, int nslab, int64_t C, const FmOut& o) {
-    hipLaunchKernelGGL(k_fm_reduce, dim3((unsigned)fx_ceil_div(C, 64)), dim3(FM_T), 0, s, partial, nslab, C, o);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
-}
-
 extern "C" int64_t fx_finalmlp_slab_rows(int64_t B) { return fm_slabs(B).rows_per_slab; }
 
 extern "C" int64_t fx_gate2_workspace_floats(int64_t B, int32_t W) {
@@ -429,13 +403,9 @@ extern "C" int fx_gate2_bwd(const float* dF1, int64_t df1_ld, const float* dF2, 
     if (vec4) hipLaunchKernelGGL(k_gate2_bwd<4>, grid, dim3(FM_T), 0, s, p);
     else hipLaunchKernelGGL(k_gate2_bwd<1>, grid, dim3(FM_T), 0, s, p);
     FX_CHECK_LAUNCH();
-    if (bc1 || bc2) {
-        FmOut o;
-        memset(&o, 0, sizeof(o));
-        o.p[0] = bc1 ? dZ1 : nullptr; o.n[0] = W;
-        o.p[1] = bc2 ? dZ2 : nullptr; o.n[1] = W;
-        return fm_reduce(s, workspace, sl.nslab, 2 * (int64_t)W, o);
-    }
+    if (bc1 || bc2)     // (a per-sample gate's half of the partials was never written: a null segment)
+        return fx_rowsum<float, FX_ROWS_RUNS>(s, workspace, sl.nslab, 2 * (int64_t)W,
+                                              fx_rowsum_out(bc1 ? dZ1 : nullptr, W, bc2 ? dZ2 : nullptr, W));
     return FX_OK;
 }
 
@@ -505,11 +475,9 @@ extern "C" int fx_biagg_bwd(const float* g, const float* X, int64_t x_ld, const 
     if (vec4) hipLaunchKernelGGL(k_biagg_bwd<4>, grid, dim3(FM_T), 0, s, p);
     else hipLaunchKernelGGL(k_biagg_bwd<1>, grid, dim3(FM_T), 0, s, p);
     FX_CHECK_LAUNCH();
-    FmOut o;
-    memset(&o, 0, sizeof(o));
-    o.p[0] = dw_x; o.n[0] = dx;
-    o.p[1] = dw_y; o.n[1] = dy;
-    o.p[2] = db; o.n[2] = 1;
-    o.dup_last = 1;
-    return fm_reduce(s, workspace, sl.nslab, (int64_t)dx + dy + 1, o);
+    const int64_t C = (int64_t)dx + dy + 1;
+    hipLaunchKernelGGL(k_biagg_reduce, dim3((unsigned)fx_ceil_div(C, 64)), dim3(FM_T), 0, s, workspace, sl.nslab, C,
+                       fx_rowsum_out(dw_x, dx, dw_y, dy, db, 1));
+    FX_CHECK_LAUNCH();
+    return FX_OK;
 }

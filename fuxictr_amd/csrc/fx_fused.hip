@@ -982,6 +982,7 @@ __global__ __launch_bounds__(256) void k_emb_fm_bwd(EmbFmBwdArgs a) {
 
 // launch 2.  Workgroups [0, ncomb): lane group q combines the run whose head is the edgeL of launch-1
 // workgroup q (+ the edgeF of the workgroups after it); last workgroup: numeric finals.
+// (not fx_rowsum.h's row sum: it joins runs of equal rows across workgroup edges, the numeric finals in the same launch)
 template <int VEC, bool LR>
 __global__ __launch_bounds__(256) void k_emb_fm_bwd_finish(EmbFmBwdArgs a, int ncomb) {
     __shared__ float red4[4];

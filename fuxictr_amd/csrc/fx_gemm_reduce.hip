@@ -1,7 +1,7 @@
 // fx_gemm_reduce.hip — the slab reduces of the split-K GEMMs: every kernel that writes K slabs to a workspace
 // (fx_gemm_tile.hip, fx_gemm_x6.hip, fx_gemm_skinny.hip) is followed by one of these, which adds the slabs in
 // slab order and applies the epilogue.  Exports fx_launch_splitk_reduce / fx_launch_splitk_reduces
-// (fx_gemm_int.h).
+// (fx_gemm_int.h).  (Not fx_rowsum.h's row sum: these apply the GEMM's epilogue and serve several problems a launch.)
 #include "fx_common.h"
 #include "fx_gemm_int.h"
 

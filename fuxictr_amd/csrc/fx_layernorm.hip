@@ -19,9 +19,10 @@
 //                                  VEC = 1: CH = 4, 8, 32 (N <= 1024, 2048, 8192); sums through LDS
 // Backward: dX in the same geometry (x, dY, Y's sign and gamma in registers, two sums per segment);
 // dgamma / dbeta in a second pass, a thread per column of the [G * N] affine pair and a slab of rows per
-// workgroup row, partial sums into caller workspace and a fixed-order sum over the slabs.  No atomics anywhere:
-// two launches on the same inputs give the same bits.
+// workgroup row, partial sums into caller workspace and a fixed-order sum over the slabs (fx_rowsum.h's shared row
+// sum, serial in fp32).  No atomics anywhere: two launches on the same inputs give the same bits.
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 #define LN_T 256
 #define LN_MAX_N 8192
@@ -292,17 +293,6 @@ __global__ __launch_bounds__(LN_T) void k_ln_dparam(LnArgs p) {
     part[C + c] = db;
 }
 
-// out[j][c] = sum over the slabs, in their order, of partial[s][j][c];  j = 0: dgamma, 1: dbeta
-__global__ __launch_bounds__(LN_T) void k_ln_reduce(const float* partial, int nslab, int64_t C, float* dgamma,
-                                                    float* dbeta) {
-    const int64_t i = (int64_t)blockIdx.x * LN_T + threadIdx.x;
-    if (i >= 2 * C) return;
-    float t = 0.f;
-    for (int s = 0; s < nslab; ++s) t += partial[(int64_t)s * 2 * C + i];
-    if (i < C) dgamma[i] = t;
-    else dbeta[i - C] = t;
-}
-
 // out[r, h] (+)= sum_{k < nb} dM[r, k H + h] * Vmask[r, k H + h]
 template <int VEC>
 __global__ __launch_bounds__(LN_T) void k_mask_grad(const float* dM, int64_t dm_ld, const float* Vm, int64_t vm_ld,
@@ -436,10 +426,8 @@ extern "C" int fx_layernorm_bwd(const float* X, int64_t x_ld, int64_t rows, int3
     if (int st = ln_launch<true>(ln_plan(N, vec4), s, p)) return st;
     hipLaunchKernelGGL(k_ln_dparam, dim3((unsigned)fx_ceil_div(C, LN_T), (unsigned)sl.nslab), dim3(LN_T), 0, s, p);
     FX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ln_reduce, dim3((unsigned)fx_ceil_div(2 * C, LN_T)), dim3(LN_T), 0, s, workspace, sl.nslab, C,
-                       dgamma, dbeta);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    // partial[s] = [dgamma | dbeta]: the slabs in their order
+    return fx_rowsum<float, FX_ROWS_SERIAL>(s, workspace, sl.nslab, 2 * C, fx_rowsum_out(dgamma, C, dbeta, C));
 }
 
 extern "C" int fx_mask_grad(const float* dM, int64_t dm_ld, const float* Vmask, int64_t vm_ld, int64_t rows,

@@ -6,10 +6,12 @@
 // heads live in LDS, nothing but Y goes to HBM.  The backward recomputes Q, K, V and P with the forward's own
 // instruction sequence, so the same bits (a log-sum-exp saved per row was tried first: at scores of +-80 it costs P
 // half an ulp of 80, 4e-6 relative), keeps the weight gradients of its samples in registers (entry e of a matrix
-// belongs to thread e % 256: no atomics), writes them as one partial per workgroup and a second launch sums the partials in a fixed order.
+// belongs to thread e % 256: no atomics), writes them as one partial per workgroup and a second launch, the shared
+// fx_rowsum (fx_rowsum.h: four interleaved slices in fp64), sums the partials in a fixed order.
 // fp32 FMAs out of LDS; every LDS row has an odd stride so that both the row-wise and the column-wise walks of
 // a phase are free of bank conflicts.
 #include "fx_common.h"
+#include "fx_rowsum.h"
 
 #define MH_T 256            // threads per workgroup
 #define MH_MAX 64           // F, D_in, A
@@ -301,20 +303,6 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
     }
 }
 
-// out[e] = sum_g partial[g][e], fixed order: 4 interleaved slices of g per entry (summed in fp64), then
-// (s0 + s1) + (s2 + s3).  64 entries per workgroup.
-__global__ __launch_bounds__(MH_T) void k_mhsa_reduce(const float* partial, int G, int n, float* out) {
-    __shared__ double red[4][64];
-    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
-    double s = 0.0;
-    if (e < n)
-        for (int g = slice; g < G; g += 4) s += (double)partial[(int64_t)g * n + e];
-    red[slice][lane] = s;
-    __syncthreads();
-    if (slice == 0 && e < n) out[e] = (float)((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
-}
-
 static int mh_check(const char* who, const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* Wq,
                     const float* Wk, const float* Wv, int32_t A, int32_t H) {
     FX_CHECK_ARG(F >= 1 && F <= MH_MAX, "%s: F=%d, limit 1 <= F <= 64", who, F);
@@ -413,8 +401,5 @@ extern "C" int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, i
     hipStream_t s = fx_hip_stream(stream);
     if (int st = wlds ? mh_launch_bwd<true>(p, grid, lds, s) : mh_launch_bwd<false>(p, grid, lds, s)) return st;
     const int n = p.nW * A * D_in;
-    hipLaunchKernelGGL(k_mhsa_reduce, dim3((unsigned)fx_ceil_div(n, 64)), dim3(MH_T), 0, s, workspace, (int)grid, n,
-                       dW);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    return fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, (int)grid, n, fx_rowsum_out(dW, n));
 }

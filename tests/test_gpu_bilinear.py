@@ -115,9 +115,14 @@ def bilinear_hip(X, W, A, dOut, kind, record_pad=0, col=0, tail=0, accumulate=Fa
     return got
 
 
+# dW's sum over the sample slabs (16 samples each at these sizes) has P D D columns, 64 per workgroup of four waves:
+# two and five slabs (SHAPES has 1, 3, 4 and 9), one column, one workgroup's 64 missed by four and passed by two
+ROWSUM_SHAPES = [(17, 2, 1), (65, 6, 2), (17, 12, 1)]
+
+
 @pytest.mark.parametrize("scaled", [False, True], ids=["plain", "scaled"])
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+@pytest.mark.parametrize("shape", SHAPES + ROWSUM_SHAPES, ids=_ids)
 def test_bilinear_forward_and_gradients_within_the_fp32_yardstick(shape, kind, scaled):
     X, W, A, dOut = bilinear_inputs(shape, kind, scaled, seed=sum(shape) + 7 * KINDS.index(kind) + scaled)
     ref = bilinear_torch(X, W, A, dOut, kind, torch.float64)
@@ -243,6 +248,21 @@ def test_senet_forward_and_gradients_within_the_fp32_yardstick(shape, act):
         b = senet_hip(X, W1, W2, dA, dV, act)
         for name in a:
             assert torch.equal(a[name], b[name]), name
+
+
+#                B  F  D  R    dW1 / dW2: a row sum over ceil(B / 4) partials of F R columns, 64 per workgroup
+SENET_ROWSUM = [(9, 1, 4, 1),       # 3 rows, 1 column
+                (13, 9, 4, 7),      # 4 rows, 63 columns
+                (17, 13, 4, 5)]     # 5 rows, 65 columns     (the shapes above: 1, 2, 9, 13, 17 rows; 64 and 507 columns)
+
+
+@pytest.mark.parametrize("case", SENET_ROWSUM, ids=lambda c: "B%d-F%d-D%d-R%d" % c)
+def test_senet_weight_gradients_over_few_partial_rows_and_columns(case):
+    B, F, D, R = case
+    assert ops.senet_workspace_floats(B, F, R) == -(-B // 4) * 2 * F * R
+    X, W1, W2, dA, dV, keep, dropped = senet_case((B, F, D), 1, R, seed=SENET_SEED + sum(case))
+    assert dropped == 0                                         # so that dW1 and dW2 are compared
+    senet_check("senet rowsum %s" % (case,), X, W1, W2, dA, dV, 1, keep, dropped)
 
 
 def test_shapes_beyond_the_limits_are_rejected_with_a_message():

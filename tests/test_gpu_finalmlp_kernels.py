@@ -29,6 +29,9 @@ SLAB = ops.finalmlp_slab_rows(64)          # rows of one slab of the backward's 
 GATE_SHAPES = [(1, 1), (3, 3), (5, 4), (7, 5), (33, 65), (65, 624), (2, 4100)]
 # one below, at and one above a slab, and two slabs: the scalar and the 16-byte arm
 GATE_SHAPES += [(r, w) for r in (SLAB - 1, SLAB, SLAB + 1, 2 * SLAB) for w in (6, 8)]
+# a broadcast gate's dZ is a row sum over the slabs, 2 W columns and 64 of them per workgroup of four waves: four and
+# nine slabs (the shapes above have 1, 2, 3 and 5), 62, 64 and 66 columns
+GATE_SHAPES += [(SLAB + 1, 31), (3 * SLAB + 1, 32), (8 * SLAB + 1, 33)]
 # gate 1 / gate 2: b = one broadcast row, p = per sample, - = no second gate
 GATE_MODES = ["bb", "bp", "pb", "pp", "b-", "p-"]
 
@@ -145,6 +148,9 @@ HEAD_SHAPES += [(5, w, w, 1) for w in (15, 17, 63, 65)] + [(5, 3, 5, 1), (5, 16,
 HEAD_SHAPES += [(5, w, w, 1) for w in (12, 16, 20, 60, 64, 68, 252, 256, 260)]
 # row counts around a slab of the backward's batch sums
 HEAD_SHAPES += [(r, 8, 12, 2) for r in (SLAB - 1, SLAB, SLAB + 1, 2 * SLAB)]
+# dw_x | dw_y | db: a row sum over the slabs of dx + dy + 1 columns, 64 per workgroup of four waves: 63, 64 and 65
+# columns (db the last of a workgroup, alone in the next), four and nine slabs (the shapes above have 1, 2, 3 and 5)
+HEAD_SHAPES += [(5, 31, 31, 1), (3 * SLAB + 1, 31, 32, 1), (8 * SLAB + 1, 32, 32, 2)]
 HEAD_NAMES = ["out", "dX", "dY", "dw_x", "dw_y", "db_x", "db_y", "dw_xy", "dadd"]
 
 

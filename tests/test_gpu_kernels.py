@@ -203,8 +203,19 @@ def test_grad_reduce_matches_index_add(D, vocabs):
 
 
 def test_numeric_grad():
+    _numeric_grad_case(13, 16)
+
+
+# Fd D columns leave through a row sum over the FX_NUMGRAD_CHUNKS batch chunks, 64 columns per workgroup (13 * 16
+# above: three full workgroups and a part): one column, one short of a workgroup, exactly one, one more
+@pytest.mark.parametrize("Fd,D", [(1, 1), (7, 9), (4, 16), (5, 13)])
+def test_numeric_grad_column_counts_around_a_workgroup(Fd, D):
+    _numeric_grad_case(Fd, D)
+
+
+def _numeric_grad_case(Fd, D):
     g = torch.Generator().manual_seed(3)
-    B, Fd, D, n_slots = 4096, 13, 16, 39
+    B, n_slots = 4096, 2 * Fd + 13
     dout = torch.randn(B, n_slots * D, generator=g)
     dense = torch.rand(B, Fd, generator=g)
     offs = [2 * j * D for j in range(Fd)]
@@ -741,6 +752,17 @@ def test_gemm_fused_rowsum_is_the_bias_gradient(M, N, K, sk):
     assert (dW.cpu().double() - ref).abs().max().item() <= 3e-6 * (dz.abs().double().t() @ x.abs().double()).max().item()
     refb = dz.double().sum(0)
     assert (db.cpu().double() - refb).abs().max().item() <= 1e-6 * dz.abs().double().sum(0).max().item()
+
+
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 130])
+def test_colsum_column_counts_around_a_workgroup(N):
+    """The second stage handles 64 columns per workgroup (N = 1000 below: 15 full ones and a part); the first takes
+    16-byte loads when N % 4 == 0.  M, the inputs' distribution and the tolerance are those of the test below."""
+    g = torch.Generator().manual_seed(8 + N)
+    X = torch.randn(4096, N, generator=g)
+    out = torch.empty(N, device=DEV)
+    ops.colsum(_dev(X), out, torch.empty(_lib.FX_COLSUM_CHUNKS * N, device=DEV))
+    assert (out.cpu().double() - X.double().sum(0)).abs().max().item() <= 2e-4
 
 
 def test_colsum_mask_cross_prep_bce():

@@ -38,6 +38,9 @@ SHAPES += [(257, 1, n) for n in (3, 63, 64, 65, 255, 256, 257, 1000, 1028)]
 SHAPES += [(257, 1, n) for n in (127, 128, 129, 511, 512, 513, 516, 1023, 1024, 1025)]
 SHAPES += [(9, 1, n) for n in (2044, 2047, 2048, 2049, 2052, 4096, 4100)]
 SHAPES += [(3, 1, 8192)]        # the width limit
+# dgamma | dbeta leave through a row sum over the slabs (one per row here), 64 columns per workgroup: two slabs (the
+# shapes above have 1, 3, 4, 5, 7, 9 and more) and 2 G N = 62, 64 and 66 columns
+SHAPES += [(2, 1, 31), (2, 1, 32), (2, 3, 11)]
 
 
 def _ids(s):

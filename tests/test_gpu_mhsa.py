@@ -148,6 +148,24 @@ def test_forward_and_gradients_within_the_fp32_yardstick(shape, flags):
     check_against_fp64("mhsa %s %s" % (shape, flags), X, W, dY, shape[4], flags)
 
 
+# The weight gradients leave through a row sum over min(B, 512) per-workgroup partials of 3 (4 with W_res) * A * D
+# columns, 64 columns per workgroup of four waves: fewer rows than waves, as many, one and five more; the fewest
+# columns the layer has, one short of a workgroup's, exactly its 64 (W_res: 4 * 8 * 2), and more than one workgroup
+ROWSUM_CASES = [((1, 2, 1, 1, 1), (True, False, False)),        # 1 row, 3 columns
+                ((2, 3, 1, 21, 3), (True, False, True)),        # 2 rows, 63 columns
+                ((3, 2, 2, 8, 2), (False, True, False)),        # 3 rows, 64 columns
+                ((4, 3, 2, 11, 1), (True, False, True)),        # 4 rows, 66 columns
+                ((9, 2, 2, 22, 2), (True, False, False))]       # 9 rows, 132 columns
+
+
+@pytest.mark.parametrize("shape,flags", ROWSUM_CASES, ids=lambda v: "-".join(str(int(x)) for x in v))
+def test_weight_gradients_over_few_partial_rows_and_columns(shape, flags):
+    X, W, dY = make_inputs(shape, flags[1], seed=5000 + sum(shape))
+    n_w = 3 if W[3] is None else 4
+    assert ops.mhsa_workspace_floats(shape[0], shape[2], shape[3], n_w == 4) == shape[0] * n_w * shape[3] * shape[2]
+    check_against_fp64("mhsa rowsum %s %s" % (shape, flags), X, W, dY, shape[4], flags)
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "B%d-F%d-D%d-A%d-H%d" % s)
 @pytest.mark.parametrize("flags", [(False, True, True), (True, False, False)],
                          ids=lambda f: "scale%d-res%d-relu%d" % tuple(int(v) for v in f))
