@@ -18,7 +18,7 @@ SOURCES = ["fx_api.cpp", "fx_embed.hip", "fx_sparse.hip", "fx_gemm.hip", "fx_gem
            "fx_mhsa.hip", "fx_group_metrics.hip", "fx_bilinear.hip", "fx_layernorm.hip", "fx_finalmlp.hip", "fx_gatecross.hip",
            "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip"]
 HEADERS = [os.path.join(CSRC, "fx_common.h"), os.path.join(CSRC, "fx_cin.h"), os.path.join(CSRC, "fx_gemm_int.h"),
-           os.path.join(CSRC, "fx_dice_int.h"), os.path.join(CSRC, "fx_rowsum.h"),
+           os.path.join(CSRC, "fx_dice_int.h"), os.path.join(CSRC, "fx_rowsum.h"), os.path.join(CSRC, "fx_attn_lds.h"),
            os.path.join(HERE, "..", "include", "fxctr.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

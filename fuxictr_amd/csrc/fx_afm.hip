@@ -104,12 +104,6 @@ static inline int af_waves(int F, int D, int A, int P) {
     return 1;
 }
 
-__device__ __forceinline__ float af_wave_max(float x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
-    return x;
-}
-
 // weights and pair table -> LDS, all threads of the workgroup; the caller synchronises
 __device__ __forceinline__ void af_stage_weights(const AfArgs& p, const AfLds& L, float* smem, bool bwd) {
     const int T = blockDim.x, t = threadIdx.x;
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(64 * AF_WAVES) void k_afm_attn_fwd(AfArgs p) {
                 m = mn;
             }
         }
-        const float M = af_wave_max(m);     // P >= 1: finite
+        const float M = fx_wave_max(m);     // P >= 1: finite
         const float sc = expf(m - M);       // a lane without a pair: exp(-inf) = 0
         den = fx_wave_sum(den * sc);
         num = fx_wave_sum(num * sc);

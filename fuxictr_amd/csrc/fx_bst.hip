@@ -6,12 +6,15 @@
 //     s    = concat_h(O_h) out_w^T + out_b (+ X);  s = LN1(s)
 //     out  = W2 lrelu(W1 s + b1) + b2 (+ s);       out = LN2(out);   pooled over the positions or written whole
 //     masked(i, j) = (pad[j] and i != j) or (causal and j > i),  pad[j] = (ids[j] == 0) for j < L, pad[L] = false
-// House style of fx_mhsa.hip: one workgroup of 256 threads works on one sample at a time in a grid-stride loop; X,
-// Q, K, V, the scores of a group of heads and every intermediate live in LDS with odd row strides; fp32 FMAs; no
-// atomics, so two launches give the same bits.  ONE launch forward, ONE launch backward per block (+ fx_colsum over
-// the per-workgroup rows of weight gradients).  The backward recomputes the forward with the forward's own device
-// functions (the same bits; neither P nor a log-sum-exp is kept: fx_mhsa.hip says why), and Q, K, V a second time
-// after the FFN half has used their LDS (6 L1 dm^2 flops, which keeps the image inside 160 KiB at L1 = dm = 64).
+// One workgroup of 256 threads works on one sample at a time in a grid-stride loop; X, Q, K, V, the scores of a group
+// of heads and every intermediate live in LDS with odd row strides; fp32 FMAs; no atomics, so two launches give the
+// same bits.  The attention (weight staging, P V, its backward loops, the per-thread weight-gradient sums) is
+// the in-LDS core of fx_attn_lds.h, shared with fx_mhsa.hip; this file owns the assembly of X, the projection, the
+// masked scores, the wave-cooperative soft-max, the FFN, LayerNorm, pooling, bias-gradient column sums and d position_emb.
+// ONE launch forward, ONE launch backward per block (+ fx_colsum over the per-workgroup rows of weight gradients).
+// The backward recomputes the forward with the forward's own device functions (the same bits; neither P nor a
+// log-sum-exp is kept: fx_mhsa.hip says why), and Q, K, V a second time after the FFN half has used their LDS
+// (6 L1 dm^2 flops, which keeps the image inside 160 KiB at L1 = dm = 64).
 // The six weight-gradient matrices stay in registers over the workgroup's samples (entry e of a matrix belongs to
 // thread e % 256), the bias / LayerNorm gradients and d position_emb in LDS (one owner thread per entry).
 // Soft-max and LayerNorm rows are wave-cooperative: a row per wave, a lane per column (L1, dm <= 64 = one wave).
@@ -23,17 +26,14 @@
 //   a5  dQ                                  a6  dK
 //   sp  P -> out before LN2 -> xhat2 -> dz1 -> P        sd  g -> d out -> ds -> d s -> dP / dS
 //   + rstd1, rstd2, pad (64 each), the bias gradients (10 dm), d position_emb (L1 * D), the weights when they fit.
-#include "fx_common.h"
+#include "fx_attn_lds.h"
 
-#define BT_T 256
-#define BT_MAX 64
-#define BT_SBUF (64 * 65)
+#define BT_T FX_ATTN_T
+#define BT_MAX FX_ATTN_MAX
 #define BT_FWD_GRID 1024
 #define BT_BWD_GRID 256      // = rows of the weight-gradient partials
-#define BT_LDS_MAX (160 * 1024)
 #define BT_SLOPE 0.01f       // nn.LeakyReLU()
 #define BT_EPS 1e-5f         // nn.LayerNorm
-#define BT_NEG_INF (-__builtin_huge_valf())
 
 enum { BT_POOL_NONE = 0, BT_POOL_MEAN = 1, BT_POOL_SUM = 2, BT_POOL_TARGET = 3 };
 
@@ -59,37 +59,6 @@ struct BstArgs {
     int64_t n_grad;
 };
 
-template <bool WLDS>
-struct BstW {
-    const float* w[6];
-    int ld;
-    __device__ __forceinline__ float operator()(int m, int a, int d) const { return w[m][a * ld + d]; }
-};
-
-template <bool WLDS>
-__device__ __forceinline__ BstW<WLDS> bt_weights(const BstArgs& p, float* sW) {
-    BstW<WLDS> w;
-    if constexpr (WLDS) {
-        const int WS = p.dm | 1, DD = p.dm * p.dm;
-        for (int idx = threadIdx.x; idx < 6 * DD; idx += BT_T) {
-            const int m = idx / DD, r = idx - m * DD, a = r / p.dm, d = r - a * p.dm;
-            sW[(m * p.dm + a) * WS + d] = p.W[m][r];
-        }
-        for (int m = 0; m < 6; ++m) w.w[m] = sW + m * p.dm * WS;
-        w.ld = WS;
-    } else {
-        for (int m = 0; m < 6; ++m) w.w[m] = p.W[m];
-        w.ld = p.dm;
-    }
-    return w;
-}
-
-__device__ __forceinline__ float bt_wave_max(float x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
-    return x;
-}
-
 // X of sample b, assembled from its parts, and the padding flags
 __device__ __forceinline__ void bt_load_x(const BstArgs& p, int64_t b, float* sX, int* sPad) {
     const int L1 = p.L1, L = L1 - 1, dm = p.dm, D = p.D, DS = dm | 1;
@@ -108,8 +77,11 @@ __device__ __forceinline__ void bt_load_x(const BstArgs& p, int64_t b, float* sX
         sPad[f] = (f < L && p.ids != nullptr && p.ids[b * p.ids_ld + f] == 0) ? 1 : 0;
 }
 
+__device__ __forceinline__ FxAttnDims bt_dims(const BstArgs& p) { return {p.L1, p.dm, p.dm, p.hd, p.HG, p.scale}; }
+
+// Q, K, V = X in_w^T + in_b.  Private like mh_project: shared, it cost k_bst_bwd<false, 16> 3.7 %.
 template <bool WLDS>
-__device__ __forceinline__ void bt_project(const BstArgs& p, const BstW<WLDS>& w, const float* sX, float* sQ,
+__device__ __forceinline__ void bt_project(const BstArgs& p, const FxAttnW<6, WLDS>& w, const float* sX, float* sQ,
                                            float* sK, float* sV) {
     const int L1 = p.L1, dm = p.dm, DS = dm | 1;
     for (int idx = threadIdx.x; idx < L1 * dm; idx += BT_T) {
@@ -127,7 +99,8 @@ __device__ __forceinline__ void bt_project(const BstArgs& p, const BstW<WLDS>& w
     }
 }
 
-// scores of the heads h0 .. h0+hg-1: sS[hh][i][j] = scale * Q_i . K_j, -inf where masked
+// scores of the heads h0 .. h0+hg-1: sS[hh][i][j] = scale * Q_i . K_j, -inf where masked.  Private: through
+// fx_attn_scores with the mask as a functor k_bst_fwd<false> measured 0.8 % slower.
 __device__ __forceinline__ void bt_scores(const BstArgs& p, int h0, int hg, const float* sQ, const float* sK,
                                           const int* sPad, float* sS) {
     const int L1 = p.L1, DS = p.dm | 1, LS = L1 | 1, hd = p.hd, LL = L1 * L1;
@@ -138,14 +111,16 @@ __device__ __forceinline__ void bt_scores(const BstArgs& p, int h0, int hg, cons
         float s = 0.f;
         for (int c = 0; c < hd; ++c) s = fmaf(q[c], k[c], s);
         const bool masked = (sPad[j] && i != j) || (p.causal && j > i);
-        sS[(hh * L1 + i) * LS + j] = masked ? BT_NEG_INF : s * p.scale;
+        sS[(hh * L1 + i) * LS + j] = masked ? FX_ATTN_NEG_INF : s * p.scale;
     }
 }
 
-// this lane's entry of the stable soft-max of one score row (the diagonal is never masked: the maximum is finite)
+// this lane's entry of the stable soft-max of one score row (the diagonal is never masked: the maximum is finite).
+// A wave per row, butterfly maximum and sum: fx_mhsa.hip's thread-per-row soft-max sums serially, so the two are
+// not one function.
 __device__ __forceinline__ float bt_softmax_lane(const float* row, int L1, int lane) {
-    const float v = lane < L1 ? row[lane] : BT_NEG_INF;
-    const float m = bt_wave_max(v);
+    const float v = lane < L1 ? row[lane] : FX_ATTN_NEG_INF;
+    const float m = fx_wave_max(v);
     const float e = lane < L1 ? expf(v - m) : 0.f;
     const float sum = fx_wave_sum(e);
     return e / sum;
@@ -154,7 +129,7 @@ __device__ __forceinline__ float bt_softmax_lane(const float* row, int L1, int l
 // the heads h0 .. h0+hg-1: P into sS, O = P V into this group's columns of sO
 __device__ __forceinline__ void bt_attend(const BstArgs& p, int h0, int hg, const float* sQ, const float* sK,
                                           const float* sV, const int* sPad, float* sS, float* sO) {
-    const int L1 = p.L1, DS = p.dm | 1, LS = L1 | 1, hd = p.hd;
+    const int L1 = p.L1, DS = p.dm | 1, LS = L1 | 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bt_scores(p, h0, hg, sQ, sK, sPad, sS);
     __syncthreads();
@@ -163,19 +138,12 @@ __device__ __forceinline__ void bt_attend(const BstArgs& p, int h0, int hg, cons
         if (lane < L1) sS[r * LS + lane] = pv;
     }
     __syncthreads();
-    const int GW = hg * hd, a0 = h0 * hd;
-    for (int idx = threadIdx.x; idx < L1 * GW; idx += BT_T) {
-        const int i = idx / GW, r = idx - i * GW, hh = r / hd, a = a0 + r;
-        const float* prow = sS + (hh * L1 + i) * LS;
-        float o = 0.f;
-        for (int j = 0; j < L1; ++j) o = fmaf(prow[j], sV[j * DS + a], o);
-        sO[i * DS + a] = o;
-    }
+    fx_attn_pv(bt_dims(p), h0, hg, sS, sV, [&](int i, int a, float o) { sO[i * DS + a] = o; });
 }
 
 // out[f][a] = in[f] . W_m[a] + bias[a] (+ add[f][a]), LeakyReLU on the way out when LRELU
 template <bool WLDS, bool LRELU>
-__device__ __forceinline__ void bt_linear(const BstW<WLDS>& w, int m, const float* bias, const float* in,
+__device__ __forceinline__ void bt_linear(const FxAttnW<6, WLDS>& w, int m, const float* bias, const float* in,
                                           const float* add, float* out, int L1, int dm) {
     const int DS = dm | 1;
     for (int idx = threadIdx.x; idx < L1 * dm; idx += BT_T) {
@@ -241,7 +209,7 @@ __device__ __forceinline__ void bt_colsum(const float* g, const float* xh, float
 
 // out[f][c] = sum_a in[f][a] W_m[a][c], times LeakyReLU' where h is given, onto out where add
 template <bool WLDS>
-__device__ __forceinline__ void bt_linear_t(const BstW<WLDS>& w, int m, const float* in, const float* h, bool add,
+__device__ __forceinline__ void bt_linear_t(const FxAttnW<6, WLDS>& w, int m, const float* in, const float* h, bool add,
                                             float* out, int L1, int dm) {
     const int DS = dm | 1;
     for (int idx = threadIdx.x; idx < L1 * dm; idx += BT_T) {
@@ -250,22 +218,6 @@ __device__ __forceinline__ void bt_linear_t(const BstW<WLDS>& w, int m, const fl
         for (int a = 0; a < dm; ++a) s = fmaf(in[f * DS + a], w(m, a, c), s);
         if (h != nullptr) s *= h[f * DS + c] > 0.f ? 1.f : BT_SLOPE;
         out[f * DS + c] = add ? out[f * DS + c] + s : s;
-    }
-}
-
-// acc[a][d] += sum_f dz[f][a] in[f][d]: this sample's sum first, then onto the running one
-template <int R>
-__device__ __forceinline__ void bt_acc_dw(float (&acc)[R], const float* dz, const float* in, int L1, int dm) {
-    const int DS = dm | 1;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = threadIdx.x + r * BT_T;
-        if (e < dm * dm) {
-            const int a = e / dm, d = e - a * dm;
-            float t = 0.f;
-            for (int f = 0; f < L1; ++f) t = fmaf(dz[f * DS + a], in[f * DS + d], t);
-            acc[r] += t;
-        }
     }
 }
 
@@ -297,7 +249,7 @@ __global__ __launch_bounds__(BT_T) void k_bst_fwd(BstArgs p) {
     float* sS = sO + N;
     int* sPad = reinterpret_cast<int*>(sS + p.S);
     float* sW = reinterpret_cast<float*>(sPad + BT_MAX);
-    const BstW<WLDS> w = bt_weights<WLDS>(p, sW);
+    const FxAttnW<6, WLDS> w = fx_attn_weights<6, WLDS>(p.W, 6, dm, dm, sW);
     for (int64_t b = blockIdx.x; b < p.B; b += gridDim.x) {
         __syncthreads();
         bt_load_x(p, b, sX, sPad);
@@ -351,7 +303,8 @@ __global__ __launch_bounds__(BT_T) void k_bst_fwd(BstArgs p) {
 template <bool WLDS, int R>
 __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int L1 = p.L1, dm = p.dm, DS = dm | 1, N = L1 * DS, LS = L1 | 1, hd = p.hd, LL = L1 * L1;
+    const FxAttnDims g = bt_dims(p);
+    const int L1 = p.L1, dm = p.dm, DS = dm | 1, N = L1 * DS, LS = L1 | 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* sX = smem;
     float* a1 = sX + N;
@@ -369,7 +322,7 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
     float* sDpos = sDB + 10 * dm;
     const int n_pos = p.in.pos != nullptr ? L1 * p.D : 0;
     float* sW = sDpos + n_pos;
-    const BstW<WLDS> w = bt_weights<WLDS>(p, sW);
+    const FxAttnW<6, WLDS> w = fx_attn_weights<6, WLDS>(p.W, 6, dm, dm, sW);
     for (int i = threadIdx.x; i < 10 * dm + n_pos; i += BT_T) sDB[i] = 0.f;
     float acc[6][R];
 #pragma unroll
@@ -424,11 +377,11 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
             __syncthreads();
         }
         // ---- FFN: sd = d out
-        bt_acc_dw<R>(acc[5], sd, a3, L1, dm);
+        fx_attn_acc_dw<R>(acc[5], sd, a3, L1, dm, dm);
         bt_colsum(sd, nullptr, nullptr, sDB + 5 * dm, L1, dm);
         bt_linear_t<WLDS>(w, 5, sd, a3, false, sp, L1, dm);                     // sp = dz1
         __syncthreads();
-        bt_acc_dw<R>(acc[4], sp, s_in, L1, dm);
+        fx_attn_acc_dw<R>(acc[4], sp, s_in, L1, dm, dm);
         bt_colsum(sp, nullptr, nullptr, sDB + 4 * dm, L1, dm);
         bt_linear_t<WLDS>(w, 4, sp, nullptr, p.residual != 0, sd, L1, dm);      // sd = ds
         __syncthreads();
@@ -439,7 +392,7 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
             __syncthreads();
         }
         // ---- output projection: sd = d s before LayerNorm 1
-        bt_acc_dw<R>(acc[3], sd, a4, L1, dm);
+        fx_attn_acc_dw<R>(acc[3], sd, a4, L1, dm, dm);
         bt_colsum(sd, nullptr, nullptr, sDB + 3 * dm, L1, dm);
         bt_linear_t<WLDS>(w, 3, sd, nullptr, false, a2, L1, dm);                // a2 = dO
         if (p.residual)       // the residual's share of dX; the same thread adds the rest below
@@ -452,18 +405,9 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
         bt_project<WLDS>(p, w, sX, a1, a3, a4);
         for (int h0 = 0; h0 < p.H; h0 += p.HG) {
             const int hg = p.H - h0 < p.HG ? p.H - h0 : p.HG;
-            const int GW = hg * hd, a0 = h0 * hd;
             __syncthreads();
             bt_scores(p, h0, hg, a1, a3, sPad, sp);
-            // dP[i][j] = dO_i . V_j
-            for (int idx = threadIdx.x; idx < hg * LL; idx += BT_T) {
-                const int hh = idx / LL, r = idx - hh * LL, i = r / L1, j = r - i * L1;
-                const float* g = a2 + i * DS + (h0 + hh) * hd;
-                const float* v = a4 + j * DS + (h0 + hh) * hd;
-                float s = 0.f;
-                for (int c = 0; c < hd; ++c) s = fmaf(g[c], v[c], s);
-                sd[(hh * L1 + i) * LS + j] = s;
-            }
+            fx_attn_dp(g, h0, hg, a2, a4, sd);
             __syncthreads();
             // row by row: P = softmax(S), then dS = P (dP - sum_j P dP) * scale
             for (int r = wave; r < hg * L1; r += BT_T / 64) {
@@ -476,45 +420,19 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
                 }
             }
             __syncthreads();
-            // dV[j][a] = sum_i P[i][j] dO[i][a], over V in place (dP is done with it)
-            for (int idx = threadIdx.x; idx < L1 * GW; idx += BT_T) {
-                const int j = idx / GW, r = idx - j * GW, hh = r / hd, a = a0 + r;
-                const float* pc = sp + hh * L1 * LS + j;
-                float s = 0.f;
-                for (int i = 0; i < L1; ++i) s = fmaf(pc[i * LS], a2[i * DS + a], s);
-                a4[j * DS + a] = s;
-            }
-            // dQ[i][a] = sum_j dS[i][j] K[j][a];  dK[i][a] = sum_j dS[j][i] Q[j][a]
-            for (int idx = threadIdx.x; idx < L1 * GW; idx += BT_T) {
-                const int i = idx / GW, r = idx - i * GW, hh = r / hd, a = a0 + r;
-                const float* ds = sd + hh * L1 * LS;
-                float dq = 0.f, dk = 0.f;
-                for (int j = 0; j < L1; ++j) {
-                    dq = fmaf(ds[i * LS + j], a3[j * DS + a], dq);
-                    dk = fmaf(ds[j * LS + i], a1[j * DS + a], dk);
-                }
-                a5[i * DS + a] = dq;
-                a6[i * DS + a] = dk;
-            }
+            fx_attn_dqkv(g, h0, hg, sp, sd, a2, a1, a3, a4, a5, a6);      // a4 = dV, a5 = dQ, a6 = dK
         }
         __syncthreads();
         // dX = dQ Wq + dK Wk + dV Wv (+ the residual's share, already there)
-        for (int idx = threadIdx.x; idx < L1 * dm; idx += BT_T) {
-            const int f = idx / dm, c = idx - f * dm;
-            float s = 0.f;
-            for (int a = 0; a < dm; ++a) {
-                s = fmaf(a5[f * DS + a], w(0, a, c), s);
-                s = fmaf(a6[f * DS + a], w(1, a, c), s);
-                s = fmaf(a4[f * DS + a], w(2, a, c), s);
-            }
+        fx_attn_dx(g, w, a5, a6, a4, [&](int f, int c, float s) {
             bt_put_dx(p, b, f, c, s, p.residual != 0 || p.dx_acc != 0, sDpos);
-        }
+        });
         bt_colsum(a5, nullptr, nullptr, sDB, L1, dm);
         bt_colsum(a6, nullptr, nullptr, sDB + dm, L1, dm);
         bt_colsum(a4, nullptr, nullptr, sDB + 2 * dm, L1, dm);
-        bt_acc_dw<R>(acc[0], a5, sX, L1, dm);
-        bt_acc_dw<R>(acc[1], a6, sX, L1, dm);
-        bt_acc_dw<R>(acc[2], a4, sX, L1, dm);
+        fx_attn_acc_dw<R>(acc[0], a5, sX, L1, dm, dm);
+        fx_attn_acc_dw<R>(acc[1], a6, sX, L1, dm, dm);
+        fx_attn_acc_dw<R>(acc[2], a4, sX, L1, dm, dm);
     }
     __syncthreads();
     float* part = p.partial + (int64_t)blockIdx.x * p.n_grad;
@@ -530,10 +448,6 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
     for (int i = threadIdx.x; i < 10 * dm + n_pos; i += BT_T) part[6 * DD + i] = sDB[i];
 }
 
-static inline int bt_heads_per_pass(int L1, int H) {
-    const int hg = BT_SBUF / (L1 * (L1 | 1));
-    return hg < H ? hg : H;
-}
 static inline int64_t bt_n_grad(int L1, int dm, int pos_D) {
     return 6 * (int64_t)dm * dm + 10 * (int64_t)dm + (int64_t)L1 * pos_D;
 }
@@ -575,7 +489,7 @@ static BstArgs bt_args(const fx_bst_input* in, const int32_t* ids, int64_t ids_l
     p.in = *in;
     p.ids = ids; p.ids_ld = ids_ld; p.B = B;
     p.L1 = L1; p.dm = dm; p.H = H; p.hd = dm / H; p.D = in->D; p.np = in->n_parts;
-    p.HG = bt_heads_per_pass(L1, H);
+    p.HG = fx_attn_heads_per_pass(L1, H);
     const int N = L1 * (dm | 1), SS = p.HG * L1 * (L1 | 1);
     p.S = N > SS ? N : SS;
     for (int m = 0; m < 3; ++m) p.W[m] = w->in_w + (int64_t)m * dm * dm;
@@ -590,11 +504,9 @@ static BstArgs bt_args(const fx_bst_input* in, const int32_t* ids, int64_t ids_l
     return p;
 }
 
-// floats of LDS: n_rows [L1, dm] arrays, n_score score buffers, the small arrays (+ the weights)
-static inline size_t bt_lds_floats(const BstArgs& p, int n_rows, int n_score, size_t small, bool wlds) {
-    size_t n = (size_t)n_rows * p.L1 * (p.dm | 1) + (size_t)n_score * p.S + small;
-    if (wlds) n += (size_t)6 * p.dm * (p.dm | 1);
-    return n;
+// LDS: X and n_rows more [L1, dm] arrays, n_score score buffers of S floats, the small arrays (+ the six weights)
+static inline FxAttnLds bt_lds(const BstArgs& p, int n_rows, int n_score, size_t small) {
+    return fx_attn_lds(fx_attn_lds_floats(p.L1, p.dm, p.dm, n_rows, n_score, p.S, small), 6, p.dm, p.dm);
 }
 
 extern "C" void fx_bst_limits(int32_t* limits) {
@@ -620,34 +532,20 @@ extern "C" int fx_bst_block_fwd(const fx_bst_input* in, const int32_t* ids, int6
     if (B == 0) return FX_OK;
     BstArgs p = bt_args(in, ids, ids_ld, B, L1, dm, H, w, layer_norm, residual, causal, pool);
     p.Y = Y;
-    const bool wlds = 4 * bt_lds_floats(p, 5, 1, BT_MAX, true) <= BT_LDS_MAX;
-    const size_t lds = 4 * bt_lds_floats(p, 5, 1, BT_MAX, wlds);
+    const FxAttnLds l = bt_lds(p, 4, 1, BT_MAX);      // (L1 = dm = 64 and 119 more shapes leave the weights in HBM)
     const unsigned grid = (unsigned)(B < BT_FWD_GRID ? B : BT_FWD_GRID);
-    static const hipError_t lds_ok[2] = {fx_allow_lds(k_bst_fwd<false>, BT_LDS_MAX),
-                                         fx_allow_lds(k_bst_fwd<true>, BT_LDS_MAX)};
-    FX_CHECK_HIP(lds_ok[wlds ? 1 : 0]);
-    if (wlds) hipLaunchKernelGGL(k_bst_fwd<true>, dim3(grid), dim3(BT_T), lds, fx_hip_stream(stream), p);
-    else hipLaunchKernelGGL(k_bst_fwd<false>, dim3(grid), dim3(BT_T), lds, fx_hip_stream(stream), p);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    hipStream_t s = fx_hip_stream(stream);
+    return l.wlds ? fx_attn_launch<k_bst_fwd<true>>(p, grid, l.bytes, s)
+                  : fx_attn_launch<k_bst_fwd<false>>(p, grid, l.bytes, s);
 }
 
 template <bool WLDS>
 static int bt_launch_bwd(const BstArgs& p, unsigned grid, size_t lds, hipStream_t s) {
     const int DD = p.dm * p.dm;
-#define FX_BST_BWD(RR)                                                                                  \
-    do {                                                                                                \
-        static const hipError_t lds_ok = fx_allow_lds(k_bst_bwd<WLDS, RR>, BT_LDS_MAX);                 \
-        FX_CHECK_HIP(lds_ok);                                                                           \
-        hipLaunchKernelGGL((k_bst_bwd<WLDS, RR>), dim3(grid), dim3(BT_T), lds, s, p);                   \
-    } while (0)
-    if (DD <= BT_T) FX_BST_BWD(1);
-    else if (DD <= 4 * BT_T) FX_BST_BWD(4);
-    else if (DD <= 9 * BT_T) FX_BST_BWD(9);
-    else FX_BST_BWD(16);
-#undef FX_BST_BWD
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    if (DD <= BT_T) return fx_attn_launch<k_bst_bwd<WLDS, 1>>(p, grid, lds, s);
+    if (DD <= 4 * BT_T) return fx_attn_launch<k_bst_bwd<WLDS, 4>>(p, grid, lds, s);
+    if (DD <= 9 * BT_T) return fx_attn_launch<k_bst_bwd<WLDS, 9>>(p, grid, lds, s);
+    return fx_attn_launch<k_bst_bwd<WLDS, 16>>(p, grid, lds, s);
 }
 
 extern "C" int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
@@ -675,12 +573,12 @@ extern "C" int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int6
     p.partial = workspace;
     p.n_grad = n4;
     const size_t small = 3 * BT_MAX + 10 * (size_t)dm + (size_t)L1 * pos_D;
-    const bool wlds = 4 * bt_lds_floats(p, 7, 2, small, true) <= BT_LDS_MAX;
-    const size_t lds = 4 * bt_lds_floats(p, 7, 2, small, wlds);
-    FX_CHECK_ARG(lds <= BT_LDS_MAX, "fx_bst_block_bwd: %zu bytes of LDS", lds);
+    const FxAttnLds l = bt_lds(p, 6, 2, small);
+    FX_CHECK_ARG(l.bytes <= FX_ATTN_LDS_MAX, "fx_bst_block_bwd: %zu bytes of LDS", l.bytes);
     const unsigned grid = (unsigned)(B < BT_BWD_GRID ? B : BT_BWD_GRID);
     hipStream_t s = fx_hip_stream(stream);
-    if (int st = wlds ? bt_launch_bwd<true>(p, grid, lds, s) : bt_launch_bwd<false>(p, grid, lds, s)) return st;
+    const int st = l.wlds ? bt_launch_bwd<true>(p, grid, l.bytes, s) : bt_launch_bwd<false>(p, grid, l.bytes, s);
+    if (st) return st;
     // the workgroups' rows -> grads, two fixed-order stages
     return fx_colsum(workspace, n4, grid, n, grads, workspace + (int64_t)grid * n4, stream);
 }

@@ -207,10 +207,27 @@ __device__ __forceinline__ void fx_store(float* p, const float (&r)[VEC]) {
     }
 }
 
-// full-wave (64 lanes) sum, result in every lane
-__device__ __forceinline__ float fx_wave_sum(float x) {
+// full-wave (64 lanes) sum of floats or doubles in a fixed butterfly, result in every lane
+template <typename T>
+__device__ __forceinline__ T fx_wave_sum(T x) {
+    static_assert(__is_same(T, float) || __is_same(T, double), "fx_wave_sum: float or double");
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+// full-wave maximum, result in every lane
+__device__ __forceinline__ float fx_wave_max(float x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
+    return x;
+}
+// inclusive scan over the wave's lanes
+__device__ __forceinline__ uint32_t fx_wave_incl_scan_u32(uint32_t x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
     return x;
 }
 

@@ -65,13 +65,6 @@ struct CnArgs {
     int cols, L, init, G;
 };
 
-// full-wave sum of doubles, result in every lane
-__device__ __forceinline__ double cn_wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 // grid (row tiles, capped), block (64, CN_ROWS).  NCH * VEC = CN_NREG: lane holds the chunks lane + 64 j of its row
 template <int VEC, int NCH>
 __global__ __launch_bounds__(CN_THREADS) void k_cross_net_fwd(CnArgs p) {
@@ -106,7 +99,7 @@ __global__ __launch_bounds__(CN_THREADS) void k_cross_net_fwd(CnArgs p) {
                     for (int k = 0; k < VEC; ++k) acc = fma((double)wv[k], (double)x[j][k], acc);
                 }
             }
-            const float s = (float)cn_wave_sum(acc);
+            const float s = (float)fx_wave_sum(acc);
             if (p.s != nullptr && lane == 0) p.s[r * p.L + l] = s;
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
@@ -179,13 +172,13 @@ __global__ __launch_bounds__(CN_THREADS) void k_cross_net_bwd(CnArgs p) {
                     }
                 }
             }
-            d = cn_wave_sum(d);
+            d = fx_wave_sum(d);
             double a[CN_MAX_L + 1];
             a[0] = 1.0;
 #pragma unroll
             for (int l = 0; l < CN_MAX_L; ++l) {
                 if (l < L) {
-                    qd[l] = cn_wave_sum(qd[l]);
+                    qd[l] = fx_wave_sum(qd[l]);
                     a[l + 1] = a[l] + (double)p.s[r * L + l];
                 } else {
                     a[l + 1] = a[l];
@@ -313,7 +306,7 @@ __global__ __launch_bounds__(CN_RED_COLS * CN_RED_PARTS) void k_cross_net_reduce
         double tk = 0.0;
         for (int g = tid; g < p.G; g += CN_RED_COLS * CN_RED_PARTS)
             tk += (double)p.partial[(int64_t)g * p.pstride + (int64_t)(L + 1) * cols + k];
-        tk = cn_wave_sum(tk);                        // (CN_RED_COLS = 64: a group is a wave)
+        tk = fx_wave_sum(tk);                        // (CN_RED_COLS = 64: a group is a wave)
         if (lane == 0) tred[k][part] = tk;
     }
     __syncthreads();

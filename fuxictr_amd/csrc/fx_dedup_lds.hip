@@ -29,15 +29,6 @@ constexpr int BK_IPT = 8;                 // items per thread and chunk
 constexpr int BK_TILE = BK_T * BK_IPT;    // 8192 items: a partition tile, and the LDS capacity of a bucket
 constexpr int BK_NB = 256;                // buckets
 
-__device__ __forceinline__ uint32_t bk_wave_incl_scan(uint32_t x, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-
 // rank of a lane's digit among the valid lanes of its wave that hold the same digit and come before it, on top
 // of the wave's running count of that digit (hist_row: the wave's private 256-entry row in LDS; every lane of
 // a match group reads the same word, the group's lowest lane bumps it).  All 64 lanes call this.
@@ -143,7 +134,7 @@ __global__ __launch_bounds__(T) void k_bk_partition(const uint32_t* __restrict__
             before += part[0][q][d];
             total += part[1][q][d];
         }
-        const uint32_t inc = bk_wave_incl_scan(total, lane);
+        const uint32_t inc = fx_wave_incl_scan_u32(total, lane);
         if (lane == 63) wtot[w] = inc;
         dbase[d] = inc - total + before;
         if (blockIdx.x == 0) btot[d] = total;
@@ -216,7 +207,7 @@ __device__ __forceinline__ void bk_sort_bucket(const BkSortArgs& a, uint32_t lo,
             __syncthreads();
             if (threadIdx.x < BK_NB) {
                 const uint32_t t = dbase[threadIdx.x];
-                const uint32_t inc = bk_wave_incl_scan(t, lane);
+                const uint32_t inc = fx_wave_incl_scan_u32(t, lane);
                 if (lane == 63) wtot[w] = inc;
                 dbase[threadIdx.x] = inc - t;
             }
@@ -267,7 +258,7 @@ __device__ __forceinline__ void bk_sort_bucket(const BkSortArgs& a, uint32_t lo,
                 }
                 ctot = run;
                 if (FITS) {                                   // one chunk: its totals are the bucket's
-                    const uint32_t inc = bk_wave_incl_scan(run, lane);
+                    const uint32_t inc = fx_wave_incl_scan_u32(run, lane);
                     if (lane == 63) wtot[w] = inc;
                     dbase[dd] = inc - run;
                 }
@@ -325,7 +316,7 @@ __device__ __forceinline__ void bk_sort_bucket(const BkSortArgs& a, uint32_t lo,
             }
         }
         if (!FITS) __syncthreads();                 // (every read of the source chunk before any write below)
-        const uint32_t inc = bk_wave_incl_scan(h, lane);
+        const uint32_t inc = fx_wave_incl_scan_u32(h, lane);
         if (lane == 63) hist[0][w] = inc;           // (the histogram rows are free now)
         __syncthreads();
         uint32_t before = carry + inc - h, total = 0;
@@ -386,7 +377,7 @@ __global__ __launch_bounds__(256) void k_bk_finish(uint32_t* __restrict__ sorted
     {
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         const uint32_t bi = btot[threadIdx.x], bu = col_cnt[threadIdx.x];
-        const uint32_t ii = bk_wave_incl_scan(bi, lane), iu = bk_wave_incl_scan(bu, lane);
+        const uint32_t ii = fx_wave_incl_scan_u32(bi, lane), iu = fx_wave_incl_scan_u32(bu, lane);
         if (lane == 63) {
             ws[0][w] = ii;
             ws[1][w] = iu;

@@ -41,15 +41,6 @@
 // running unique count.  Block 0 also opens the optimizer step (fx_opt_begin_step fused).
 // (Round 2 used rocprim::block_radix_sort here — 4 bits a pass, 23 us for the 26 Criteo columns.)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t fx_wave_incl_scan_u32(uint32_t x, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-
 template <int IPT>
 __global__ __launch_bounds__(1024) void k_sort_columns3(const int32_t* ids, int64_t ids_ld, int64_t B,
                                                         const int64_t* col_row_base,

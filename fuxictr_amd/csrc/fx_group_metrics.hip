@@ -221,19 +221,12 @@ __device__ __forceinline__ void gm_finalize(const GmPart& p, int S, int E, const
     }
 }
 
-// sum of x over the wave in a fixed tree, result in every lane
-__device__ __forceinline__ double gm_wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 // v summed over the workgroup's lanes in a fixed order -> out[FX_GM_NV] (thread 0 writes)
 __device__ __forceinline__ void gm_block_sum(double (&v)[FX_GM_NV], double (*red)[FX_GM_NV], double* out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < FX_GM_NV; ++c) {
-        const double s = gm_wave_sum(v[c]);
+        const double s = fx_wave_sum(v[c]);
         if (lane == 0) red[wave][c] = s;
     }
     __syncthreads();
@@ -370,10 +363,10 @@ __global__ __launch_bounds__(FX_GM_TILE) void k_gm_fixup(GmKs ks, const double* 
             p.a += __shfl_xor(p.a, off, 64);
             p.np += __shfl_xor(p.np, off, 64);
         }
-        p.mrr = gm_wave_sum(p.mrr);
+        p.mrr = fx_wave_sum(p.mrr);
 #pragma unroll
         for (int k = 0; k < FX_GM_MAX_K; ++k)
-            if (k < ks.nk) p.dcg[k] = gm_wave_sum(p.dcg[k]);
+            if (k < ks.nk) p.dcg[k] = fx_wave_sum(p.dcg[k]);
         if (lane == 0) {
             const GmPart q = c_own[chunk];
             p.a += q.a;

@@ -3,22 +3,21 @@
 //     Q = X Wq^T, K = X Wk^T, V = X Wv^T;  per head: P = softmax_rows(Q_h K_h^T [/ sqrt(head_dim)]);  O_h = P V_h
 //     Y = concat_h(O_h) (+ X Wres^T | + X);  Y = relu(Y)
 // One workgroup of 256 threads works on one sample at a time: X, Q, K, V and the score matrices of a group of
-// heads live in LDS, nothing but Y goes to HBM.  The backward recomputes Q, K, V and P with the forward's own
-// instruction sequence, so the same bits (a log-sum-exp saved per row was tried first: at scores of +-80 it costs P
-// half an ulp of 80, 4e-6 relative), keeps the weight gradients of its samples in registers (entry e of a matrix
-// belongs to thread e % 256: no atomics), writes them as one partial per workgroup and a second launch, the shared
-// fx_rowsum (fx_rowsum.h: four interleaved slices in fp64), sums the partials in a fixed order.
-// fp32 FMAs out of LDS; every LDS row has an odd stride so that both the row-wise and the column-wise walks of
-// a phase are free of bank conflicts.
-#include "fx_common.h"
+// heads live in LDS, nothing but Y goes to HBM.  The attention itself (weight staging, scores, P V and the loops of
+// its backward) is the in-LDS core of fx_attn_lds.h, which fx_bst.hip uses too; this file owns the loading of X with
+// the projection, the serial soft-max, the residual / ReLU epilogue and the fused weight-gradient loop.  The backward
+// recomputes Q, K, V and P with the forward's own instruction sequence, so the same bits (a log-sum-exp saved per row
+// was tried first: at scores of +-80 it costs P half an ulp of 80, 4e-6 relative), keeps the weight gradients of its
+// samples in registers (entry e of a matrix belongs to thread e % 256: no atomics), writes them as one partial per
+// workgroup and a second launch, the shared fx_rowsum (fx_rowsum.h: four interleaved slices in fp64), sums the
+// partials in a fixed order.
+#include "fx_attn_lds.h"
 #include "fx_rowsum.h"
 
-#define MH_T 256            // threads per workgroup
-#define MH_MAX 64           // F, D_in, A
-#define MH_SBUF (64 * 65)   // floats of one score buffer: the heads of a group share it
+#define MH_T FX_ATTN_T
+#define MH_MAX FX_ATTN_MAX  // F, D_in, A
 #define MH_BWD_GRID 512     // workgroups of the backward = rows of the weight-gradient partials
 #define MH_FWD_GRID 2048
-#define MH_LDS_MAX (160 * 1024)
 
 struct MhsaArgs {
     const float* X;
@@ -36,46 +35,12 @@ struct MhsaArgs {
     float* partial;         // [grid, nW * A * D]
 };
 
-static inline int mh_odd(int n) { return n | 1; }
-static inline int mh_heads_per_pass(int F, int H) {
-    const int hg = MH_SBUF / (F * mh_odd(F));
-    return hg < H ? hg : H;
-}
-// floats of LDS: X + n_rows [F, A] arrays + n_score score buffers (+ the weights)
-static inline size_t mh_lds_floats(int F, int D, int A, int HG, int nW, int n_rows, int n_score, bool wlds) {
-    size_t n = (size_t)F * mh_odd(D) + (size_t)n_rows * F * mh_odd(A) + (size_t)n_score * HG * F * mh_odd(F);
-    if (wlds) n += (size_t)nW * A * mh_odd(D);
-    return n;
-}
+__device__ __forceinline__ FxAttnDims mh_dims(const MhsaArgs& p) { return {p.F, p.D, p.A, p.hd, p.HG, p.scale}; }
 
+// X of sample b -> sX, then Q, K, V = X Wq^T, X Wk^T, X Wv^T.  Private: as a helper of fx_attn_lds.h next to a separate
+// load it cost k_mhsa_bwd<false, 16>, which sits at 256 VGPRs, 5.4 %; in this form nothing is slower.
 template <bool WLDS>
-struct MhsaW {
-    const float* w[4];
-    int ld;
-    __device__ __forceinline__ float operator()(int m, int a, int d) const { return w[m][a * ld + d]; }
-};
-
-template <bool WLDS>
-__device__ __forceinline__ MhsaW<WLDS> mh_weights(const MhsaArgs& p, float* sW) {
-    MhsaW<WLDS> w;
-    if constexpr (WLDS) {
-        const int WS = p.D | 1, AD = p.A * p.D;
-        for (int idx = threadIdx.x; idx < p.nW * AD; idx += MH_T) {
-            const int m = idx / AD, r = idx - m * AD, a = r / p.D, d = r - a * p.D;
-            sW[(m * p.A + a) * WS + d] = p.W[m][r];
-        }
-        for (int m = 0; m < 4; ++m) w.w[m] = sW + m * p.A * WS;
-        w.ld = WS;
-    } else {
-        for (int m = 0; m < 4; ++m) w.w[m] = p.W[m];
-        w.ld = p.D;
-    }
-    return w;
-}
-
-// X of sample b -> sX, then Q, K, V
-template <bool WLDS>
-__device__ __forceinline__ void mh_project(const MhsaArgs& p, const MhsaW<WLDS>& w, int64_t b, float* sX,
+__device__ __forceinline__ void mh_project(const MhsaArgs& p, const FxAttnW<4, WLDS>& w, int64_t b, float* sX,
                                            float* sQ, float* sK, float* sV) {
     const int F = p.F, D = p.D, A = p.A, XS = D | 1, AS = A | 1;
     const float* x = p.X + b * p.x_ld;
@@ -99,7 +64,8 @@ __device__ __forceinline__ void mh_project(const MhsaArgs& p, const MhsaW<WLDS>&
     }
 }
 
-// stable soft-max of one score row in place (row maximum subtracted)
+// stable soft-max of one score row in place (row maximum subtracted).  A thread per row, serial maximum and sum:
+// fx_bst.hip's wave-per-row soft-max sums in another order, so the two are not one function.
 __device__ __forceinline__ void mh_softmax_row(float* row, int F) {
     float m = row[0];
     for (int j = 1; j < F; ++j) m = fmaxf(m, row[j]);
@@ -112,48 +78,31 @@ __device__ __forceinline__ void mh_softmax_row(float* row, int F) {
     for (int j = 0; j < F; ++j) row[j] = row[j] / sum;
 }
 
-// scores of the heads h0 .. h0+hg-1: sS[hh][i][j] = scale * Q_i . K_j
-__device__ __forceinline__ void mh_scores(const MhsaArgs& p, int h0, int hg, const float* sQ, const float* sK,
-                                          float* sS) {
-    const int F = p.F, AS = p.A | 1, FS = F | 1, hd = p.hd, FF = F * F;
-    for (int idx = threadIdx.x; idx < hg * FF; idx += MH_T) {
-        const int hh = idx / FF, r = idx - hh * FF, i = r / F, j = r - i * F;
-        const float* q = sQ + i * AS + (h0 + hh) * hd;
-        const float* k = sK + j * AS + (h0 + hh) * hd;
-        float s = 0.f;
-        for (int c = 0; c < hd; ++c) s = fmaf(q[c], k[c], s);
-        sS[(hh * F + i) * FS + j] = s * p.scale;
-    }
-}
-
-template <bool WLDS>
+// (the weights always fit into LDS next to the forward's image: at most 149 760 bytes, at F = D = A = 64 with a
+// W_res, over every F, D, A <= 64 — so the forward has no instantiation that reads them from HBM)
 __global__ __launch_bounds__(MH_T) void k_mhsa_fwd(MhsaArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int F = p.F, D = p.D, A = p.A, XS = D | 1, AS = A | 1, FS = F | 1, hd = p.hd;
+    const FxAttnDims g = mh_dims(p);
+    const int F = p.F, D = p.D, A = p.A, XS = D | 1, AS = A | 1, FS = F | 1;
     float* sX = smem;
     float* sQ = sX + F * XS;
     float* sK = sQ + F * AS;
     float* sV = sK + F * AS;
     float* sS = sV + F * AS;
     float* sW = sS + p.HG * F * FS;
-    const MhsaW<WLDS> w = mh_weights<WLDS>(p, sW);
+    const FxAttnW<4, true> w = fx_attn_weights<4, true>(p.W, p.nW, A, D, sW);
     for (int64_t b = blockIdx.x; b < p.B; b += gridDim.x) {
         __syncthreads();
-        mh_project<WLDS>(p, w, b, sX, sQ, sK, sV);
+        mh_project<true>(p, w, b, sX, sQ, sK, sV);
         for (int h0 = 0; h0 < p.H; h0 += p.HG) {
             const int hg = p.H - h0 < p.HG ? p.H - h0 : p.HG;
             __syncthreads();
-            mh_scores(p, h0, hg, sQ, sK, sS);
+            fx_attn_scores(g, h0, hg, sQ, sK, sS);
             __syncthreads();
-            for (int idx = threadIdx.x; idx < hg * F; idx += MH_T) mh_softmax_row(sS + idx * FS, F);   // a thread per row
+            for (int idx = threadIdx.x; idx < hg * F; idx += MH_T) mh_softmax_row(sS + idx * FS, F);
             __syncthreads();
-            const int GW = hg * hd;                // this group's columns of Y: a0 .. a0 + GW
-            const int a0 = h0 * hd;
-            for (int idx = threadIdx.x; idx < F * GW; idx += MH_T) {
-                const int i = idx / GW, r = idx - i * GW, hh = r / hd, a = a0 + r;
-                const float* prow = sS + (hh * F + i) * FS;
-                float o = 0.f;
-                for (int j = 0; j < F; ++j) o = fmaf(prow[j], sV[j * AS + a], o);
+            // this file's epilogue: the residual and the ReLU on the way to Y
+            fx_attn_pv(g, h0, hg, sS, sV, [&](int i, int a, float o) {
                 if (p.residual) {
                     if (p.W[3] != nullptr) {
                         float r2 = 0.f;
@@ -165,7 +114,7 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_fwd(MhsaArgs p) {
                 }
                 if (p.relu) o = fmaxf(o, 0.f);
                 p.Y[(b * F + i) * A + a] = o;
-            }
+            });
         }
     }
 }
@@ -174,7 +123,8 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_fwd(MhsaArgs p) {
 template <bool WLDS, int R>
 __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int F = p.F, D = p.D, A = p.A, XS = D | 1, AS = A | 1, FS = F | 1, hd = p.hd, FF = F * F;
+    const FxAttnDims g = mh_dims(p);
+    const int F = p.F, D = p.D, A = p.A, XS = D | 1, AS = A | 1, FS = F | 1;
     float* sX = smem;
     float* sQ = sX + F * XS;
     float* sK = sQ + F * AS;
@@ -185,7 +135,7 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
     float* sP = sdK + F * AS;
     float* sD = sP + p.HG * F * FS;   // dP, then dS
     float* sW = sD + p.HG * F * FS;
-    const MhsaW<WLDS> w = mh_weights<WLDS>(p, sW);
+    const FxAttnW<4, WLDS> w = fx_attn_weights<4, WLDS>(p.W, p.nW, A, D, sW);
     const bool wres = p.W[3] != nullptr;
     float acc[4][R];
 #pragma unroll
@@ -197,25 +147,16 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
         __syncthreads();
         for (int idx = threadIdx.x; idx < F * A; idx += MH_T) {
             const int f = idx / A, a = idx - f * A;
-            float g = p.dY[b * F * A + idx];
-            if (p.relu && !(p.Y[b * F * A + idx] > 0.f)) g = 0.f;
-            sG[f * AS + a] = g;
+            float gy = p.dY[b * F * A + idx];
+            if (p.relu && !(p.Y[b * F * A + idx] > 0.f)) gy = 0.f;
+            sG[f * AS + a] = gy;
         }
         mh_project<WLDS>(p, w, b, sX, sQ, sK, sV);
         for (int h0 = 0; h0 < p.H; h0 += p.HG) {
             const int hg = p.H - h0 < p.HG ? p.H - h0 : p.HG;
-            const int GW = hg * hd, a0 = h0 * hd;
             __syncthreads();
-            mh_scores(p, h0, hg, sQ, sK, sP);
-            // dP[i][j] = dO_i . V_j
-            for (int idx = threadIdx.x; idx < hg * FF; idx += MH_T) {
-                const int hh = idx / FF, r = idx - hh * FF, i = r / F, j = r - i * F;
-                const float* g = sG + i * AS + (h0 + hh) * hd;
-                const float* v = sV + j * AS + (h0 + hh) * hd;
-                float s = 0.f;
-                for (int c = 0; c < hd; ++c) s = fmaf(g[c], v[c], s);
-                sD[(hh * F + i) * FS + j] = s;
-            }
+            fx_attn_scores(g, h0, hg, sQ, sK, sP);
+            fx_attn_dp(g, h0, hg, sG, sV, sD);
             __syncthreads();
             // row by row: P = softmax(S), then dS = P (dP - sum_j P dP) * scale
             for (int idx = threadIdx.x; idx < hg * F; idx += MH_T) {
@@ -227,37 +168,11 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
                 for (int j = 0; j < F; ++j) dr[j] = pr[j] * (dr[j] - delta) * p.scale;
             }
             __syncthreads();
-            // dV[j][a] = sum_i P[i][j] dO[i][a], over V in place (dP is done with it)
-            for (int idx = threadIdx.x; idx < F * GW; idx += MH_T) {
-                const int j = idx / GW, r = idx - j * GW, hh = r / hd, a = a0 + r;
-                const float* pc = sP + hh * F * FS + j;
-                float s = 0.f;
-                for (int i = 0; i < F; ++i) s = fmaf(pc[i * FS], sG[i * AS + a], s);
-                sV[j * AS + a] = s;
-            }
-            // dQ[i][a] = sum_j dS[i][j] K[j][a];  dK[i][a] = sum_j dS[j][i] Q[j][a]
-            for (int idx = threadIdx.x; idx < F * GW; idx += MH_T) {
-                const int i = idx / GW, r = idx - i * GW, hh = r / hd, a = a0 + r;
-                const float* ds = sD + hh * F * FS;
-                float dq = 0.f, dk = 0.f;
-                for (int j = 0; j < F; ++j) {
-                    dq = fmaf(ds[i * FS + j], sK[j * AS + a], dq);
-                    dk = fmaf(ds[j * FS + i], sQ[j * AS + a], dk);
-                }
-                sdQ[i * AS + a] = dq;
-                sdK[i * AS + a] = dk;
-            }
+            fx_attn_dqkv(g, h0, hg, sP, sD, sG, sQ, sK, sV, sdQ, sdK);
         }
         __syncthreads();
         // dX = dQ Wq + dK Wk + dV Wv (+ dO Wres | + dO)
-        for (int idx = threadIdx.x; idx < F * D; idx += MH_T) {
-            const int f = idx / D, d = idx - f * D;
-            float s = 0.f;
-            for (int a = 0; a < A; ++a) {
-                s = fmaf(sdQ[f * AS + a], w(0, a, d), s);
-                s = fmaf(sdK[f * AS + a], w(1, a, d), s);
-                s = fmaf(sV[f * AS + a], w(2, a, d), s);
-            }
+        fx_attn_dx(g, w, sdQ, sdK, sV, [&](int f, int d, float s) {
             if (p.residual) {
                 if (wres) {
                     float r2 = 0.f;
@@ -267,10 +182,11 @@ __global__ __launch_bounds__(MH_T) void k_mhsa_bwd(MhsaArgs p) {
                     s += sG[f * AS + d];
                 }
             }
-            float* dx = p.dX + b * p.dx_ld + idx;
+            float* dx = p.dX + b * p.dx_ld + (f * D + d);
             *dx = p.dx_acc ? *dx + s : s;
-        }
-        // dW*[a][d] += sum_f d*[f][a] X[f][d]: this sample's sum first, then onto the running one
+        });
+        // dW*[a][d] += sum_f d*[f][a] X[f][d], all four in one loop over f.  fx_attn_acc_dw per matrix (same bits) timed
+        // 13 % faster at R = 16 but 0.3 % slower at the Criteo shape (R = 4), outside its spread: the fused loop stays.
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int e = threadIdx.x + r * MH_T;
@@ -322,13 +238,19 @@ static MhsaArgs mh_args(const float* X, int64_t x_ld, int64_t B, int32_t F, int3
     memset(&p, 0, sizeof(p));
     p.X = X; p.x_ld = x_ld; p.B = B;
     p.F = F; p.D = D; p.A = A; p.H = H; p.hd = A / H;
-    p.HG = mh_heads_per_pass(F, H);
+    p.HG = fx_attn_heads_per_pass(F, H);
     p.W[0] = Wq; p.W[1] = Wk; p.W[2] = Wv; p.W[3] = (residual && Wres) ? Wres : nullptr;
     p.nW = p.W[3] ? 4 : 3;
     p.scale = use_scale ? (float)(1.0 / sqrt((double)p.hd)) : 1.f;
     p.residual = residual ? 1 : 0;
     p.relu = relu ? 1 : 0;
     return p;
+}
+
+// LDS: X and n_rows [F, A] arrays, n_score score buffers (+ the weights)
+static inline FxAttnLds mh_lds(const MhsaArgs& p, int n_rows, int n_score) {
+    const size_t n = fx_attn_lds_floats(p.F, p.D, p.A, n_rows, n_score, fx_attn_score_floats(p.F, p.HG), 0);
+    return fx_attn_lds(n, p.nW, p.A, p.D);
 }
 
 extern "C" int64_t fx_mhsa_workspace_floats(int64_t B, int32_t D_in, int32_t A, int32_t has_wres) {
@@ -346,34 +268,19 @@ extern "C" int fx_mhsa_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, i
     if (B == 0) return FX_OK;
     MhsaArgs p = mh_args(X, x_ld, B, F, D_in, Wq, Wk, Wv, Wres, A, H, use_scale, residual, relu);
     p.Y = Y;
-    const bool wlds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 3, 1, true) <= MH_LDS_MAX;
-    const size_t lds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 3, 1, wlds);
+    // Q, K, V, one score buffer and the weights: see k_mhsa_fwd (the check only guards a later change of the limits)
+    const FxAttnLds l = mh_lds(p, 3, 1);
+    FX_CHECK_ARG(l.wlds, "fx_mhsa_fwd: %zu bytes of LDS without the weights", l.bytes);
     const unsigned grid = (unsigned)(B < MH_FWD_GRID ? B : MH_FWD_GRID);
-    // (once per process: both instantiations may use the whole 160 KiB, the largest image any shape needs)
-    static const hipError_t lds_ok[2] = {fx_allow_lds(k_mhsa_fwd<false>, MH_LDS_MAX),
-                                         fx_allow_lds(k_mhsa_fwd<true>, MH_LDS_MAX)};
-    FX_CHECK_HIP(lds_ok[wlds ? 1 : 0]);
-    if (wlds) hipLaunchKernelGGL(k_mhsa_fwd<true>, dim3(grid), dim3(MH_T), lds, fx_hip_stream(stream), p);
-    else hipLaunchKernelGGL(k_mhsa_fwd<false>, dim3(grid), dim3(MH_T), lds, fx_hip_stream(stream), p);
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    return fx_attn_launch<k_mhsa_fwd>(p, grid, l.bytes, fx_hip_stream(stream));
 }
 
 template <bool WLDS>
 static int mh_launch_bwd(const MhsaArgs& p, unsigned grid, size_t lds, hipStream_t s) {
     const int AD = p.A * p.D;
-#define FX_MHSA_BWD(RR)                                                                                  \
-    do {                                                                                                 \
-        static const hipError_t lds_ok = fx_allow_lds(k_mhsa_bwd<WLDS, RR>, MH_LDS_MAX);                 \
-        FX_CHECK_HIP(lds_ok);                                                                            \
-        hipLaunchKernelGGL((k_mhsa_bwd<WLDS, RR>), dim3(grid), dim3(MH_T), lds, s, p);                   \
-    } while (0)
-    if (AD <= MH_T) FX_MHSA_BWD(1);
-    else if (AD <= 4 * MH_T) FX_MHSA_BWD(4);
-    else FX_MHSA_BWD(16);
-#undef FX_MHSA_BWD
-    FX_CHECK_LAUNCH();
-    return FX_OK;
+    if (AD <= MH_T) return fx_attn_launch<k_mhsa_bwd<WLDS, 1>>(p, grid, lds, s);
+    if (AD <= 4 * MH_T) return fx_attn_launch<k_mhsa_bwd<WLDS, 4>>(p, grid, lds, s);
+    return fx_attn_launch<k_mhsa_bwd<WLDS, 16>>(p, grid, lds, s);
 }
 
 extern "C" int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in, const float* Wq,
@@ -395,11 +302,11 @@ extern "C" int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, i
     p.dx_acc = dx_accumulate ? 1 : 0;
     p.partial = workspace;
     // six [F, A] arrays and two score buffers (P, dP | dS); the weights join them in LDS when all of it fits
-    const bool wlds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 6, 2, true) <= MH_LDS_MAX;
-    const size_t lds = 4 * mh_lds_floats(F, D_in, A, p.HG, p.nW, 6, 2, wlds);
+    const FxAttnLds l = mh_lds(p, 6, 2);
     const unsigned grid = (unsigned)(B < MH_BWD_GRID ? B : MH_BWD_GRID);
     hipStream_t s = fx_hip_stream(stream);
-    if (int st = wlds ? mh_launch_bwd<true>(p, grid, lds, s) : mh_launch_bwd<false>(p, grid, lds, s)) return st;
+    const int st = l.wlds ? mh_launch_bwd<true>(p, grid, l.bytes, s) : mh_launch_bwd<false>(p, grid, l.bytes, s);
+    if (st) return st;
     const int n = p.nW * A * D_in;
     return fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, (int)grid, n, fx_rowsum_out(dW, n));
 }

@@ -11,7 +11,7 @@ initialisation and inputs of std 0.5: 0 to 3 of 33 samples at L1 = 51, dm = 48 (
 sets), 0 to 2 of 1027 at L1 = 3, dm = 8, and 0 or 1 of 7 at L1 = dm = 64, where one sample is already over the cap.
 After LayerNorm the pre-activation's scale does not follow the input's, so the inputs are fixed by SEEDS instead: one
 seed per shape, picked once on the CPU as the first of 100 + shape, + 10, .. whose fp64 reference is under the cap for
-all five flag sets (only L1 = dm = 64 needed a second and third try)."""
+all five flag sets (only L1 = dm = 64 needed a second and third try; L1 = 40, dm = 12 drops 0 or 1 of 20 at its first)."""
 import numpy as np
 import pytest
 import torch
@@ -144,17 +144,18 @@ def check(tag, case, H, flags, dev):
     return worst
 
 
-SEEDS = (100, 101, 122, 103, 104)      # per shape; see the module docstring
+SEEDS = (100, 101, 122, 103, 104, 105)      # per shape; see the module docstring
 
 
 def shapes():
+    """The last: L1 = 40 holds two heads per pass (4160 // (40 * 41)), H = 3, so a ragged last head group (2 + 1)."""
     grid = ops.bst_limits()[2]
     return [(33, 50, 2, 16, 2, True), (5, 1, 1, 4, 1, False), (7, 63, 1, 32, 64, True), (9, 6, 3, 5, 4, True),
-            (grid + 3, 2, 1, 4, 2, True)]
+            (grid + 3, 2, 1, 4, 2, True), (20, 39, 2, 4, 3, True)]
 
 
 @pytest.mark.parametrize("flags", FLAGS, ids=lambda f: "ln%d_res%d_causal%d_%s" % (f[0], f[1], f[2], f[3]))
-@pytest.mark.parametrize("shape", range(5))
+@pytest.mark.parametrize("shape", range(6))
 def test_block_against_fp64(shape, flags):
     B, L, n_parts, D, H, pos = shapes()[shape]
     case = make_case(B, L, n_parts, D, H, pos, flags[0], seed=SEEDS[shape])

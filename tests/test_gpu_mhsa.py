@@ -148,6 +148,38 @@ def test_forward_and_gradients_within_the_fp32_yardstick(shape, flags):
     check_against_fp64("mhsa %s %s" % (shape, flags), X, W, dY, shape[4], flags)
 
 
+# The arms of the in-LDS core that SHAPES does not reach (the host's arithmetic, csrc/fx_attn_lds.h: heads per pass
+# = min(H, 4160 // (F * (F | 1))); the backward's weights stay in HBM when six [F, A] arrays, X, two score buffers
+# and the weights exceed 160 KiB; 16 gradient entries per thread when A * D > 1024):
+#   F = 40, H = 3: two heads per pass, so a ragged last group (2 + 1), without and with a W_res;
+#   F = D = A = 64: weights in HBM, 16 entries per thread, three matrices; D = 32 with a W_res: four matrices
+ARM_CASES = [((5, 40, 6, 12, 3), (True, False, True)), ((5, 40, 6, 12, 3), (True, True, True)),
+             ((3, 64, 64, 64, 2), (True, True, True)), ((3, 64, 32, 64, 2), (True, True, True))]
+
+
+#            (heads per pass, weights in LDS, gradient entries per thread) of the backward
+ARM_OF = {(5, 40, 6, 12, 3): (2, True, 1), (3, 64, 64, 64, 2): (1, False, 16), (3, 64, 32, 64, 2): (1, False, 16)}
+
+
+def backward_arm(shape, n_w):
+    """The host's choice for the backward, restated from csrc/fx_attn_lds.h and fx_mhsa.hip: if a limit there moves,
+    the cases below stop being the arms they are named for and this says so."""
+    B, F, D, A, H = shape
+    hg = min(H, (64 * 65) // (F * (F | 1)))
+    floats = F * (D | 1) + 6 * F * (A | 1) + 2 * hg * F * (F | 1)
+    wlds = 4 * (floats + n_w * A * (D | 1)) <= 160 * 1024
+    return hg, wlds, 1 if A * D <= 256 else 4 if A * D <= 1024 else 16
+
+
+@pytest.mark.parametrize("shape,flags", ARM_CASES, ids=lambda v: "-".join(str(int(x)) for x in v))
+def test_ragged_head_groups_and_weights_left_in_hbm(shape, flags):
+    X, W, dY = make_inputs(shape, flags[1], seed=6000 + sum(shape) + flags[1])
+    assert (W[3] is not None) == (flags[1] and shape[2] != shape[3])
+    assert backward_arm(shape, 3 if W[3] is None else 4) == ARM_OF[shape]
+    assert shape[4] % ARM_OF[shape][0] != 0 or ARM_OF[shape][1] is False      # a ragged group, or weights in HBM
+    check_against_fp64("mhsa arm %s %s" % (shape, flags), X, W, dY, shape[4], flags)
+
+
 # The weight gradients leave through a row sum over min(B, 512) per-workgroup partials of 3 (4 with W_res) * A * D
 # columns, 64 columns per workgroup of four waves: fewer rows than waves, as many, one and five more; the fewest
 # columns the layer has, one short of a workgroup's, exactly its 64 (W_res: 4 * 8 * 2), and more than one workgroup
