@@ -201,7 +201,13 @@ def split_rows(src, n_rows, parts, zero_tail_rows=0):
         dst[n_rows:n_rows + zero_tail_rows] = 0
 
 
+def _check_parts(parts, who):
+    if len(parts) > _lib.FX_CLIP_MAX_PARTS:            # the argument check of fx_sum_parts / fx_clip_coef
+        raise _lib.FxError("%s: n_parts=%d > %d" % (who, len(parts), _lib.FX_CLIP_MAX_PARTS))
+
+
 def sum_parts(parts, out):
+    _check_parts(parts, "fx_sum_parts")
     out[0] = sum(float(p.double().sum()) for p in parts)
 
 
@@ -269,6 +275,7 @@ def opt_begin_step(scal):
 
 
 def clip_coef(parts, scal):
+    _check_parts(parts, "fx_clip_coef")
     total = math.sqrt(sum(float(p.double().sum()) for p in parts))
     mx = float(scal[SC.SC_MAX_NORM])
     scal[SC.SC_TOTAL_NORM] = total
@@ -434,7 +441,9 @@ def gemm_dw_dx(dz, x, W, dW, dx, split_k=1, workspace=None, rowsum=None, mask=No
 
 
 def colsum(X, out, workspace):
-    out.copy_(X.sum(0))
+    # (fx_colsum adds the rows in one order whatever the row stride; torch picks its order by the strides, so a
+    # strided X is summed as its packed copy: the same sum as before for every contiguous X)
+    out.copy_(X.contiguous().sum(0))
     return out
 
 
@@ -468,11 +477,23 @@ def head_train_workspace_floats(M, K):
 def head_train_ok(h, W, out_add=None):
     K = W.shape[1]
     return (W.shape[0] == 1 and K % 4 == 0 and 8 < K <= 2048 and h.dim() == 2 and h.stride(1) == 1
+            and h.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0 and W.is_contiguous()
+            and W.data_ptr() % 16 == 0
             and (out_add is None or (out_add.numel() == h.shape[0] and out_add.dim() <= 2)))
 
 
 def head_train(h, W, bias, out_add, y, mask_from, root_scale, logit, dlogit, dz, dW, db, loss, workspace):
-    M = h.shape[0]
+    M, K = h.shape
+    # the argument checks of fx_head_train
+    if not (K % 4 == 0 and 8 < K <= 2048):
+        raise _lib.FxError("fx_head_train: K must be a multiple of 4 in (8, 2048] (K=%d)" % K)
+    if (h.stride(0) % 4 or h.data_ptr() % 16 or W.data_ptr() % 16
+            or (workspace is not None and workspace.data_ptr() % 16)):
+        raise _lib.FxError("fx_head_train: h / w / workspace must be 16-byte aligned, ldh % 4 == 0")
+    if dz is not None and (dz.stride(0) % 4 or dz.data_ptr() % 16):
+        raise _lib.FxError("fx_head_train: dz must be 16-byte aligned, lddz % 4 == 0")
+    if mask_from >= 0 and mask_from % 4:
+        raise _lib.FxError("fx_head_train: mask_from must be a multiple of 4")
     z = h @ W.reshape(-1)
     if bias is not None:
         z = z + bias.reshape(())
