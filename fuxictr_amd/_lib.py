@@ -76,6 +76,16 @@ class BstWeights(C.Structure):
                                   "ln2_w", "ln2_b")]
 
 
+class GruInput(C.Structure):
+    """struct fx_gru_input"""
+    _fields_ = [("seq", vp * 2), ("seq_ld", i64 * 2), ("seq_row_ld", i64 * 2), ("n_parts", i32), ("D", i32)]
+
+
+class SeqTarget(C.Structure):
+    """struct fx_seq_target"""
+    _fields_ = [("tgt", vp * 2), ("tgt_ld", i64 * 2), ("n_parts", i32), ("D", i32)]
+
+
 SIGNATURES = {
     "fx_abi_version": (i32, []),
     "fx_last_error": (C.c_char_p, []),
@@ -195,6 +205,17 @@ SIGNATURES = {
                                i32, i32, vp, vp]),
     "fx_bst_block_bwd": (i32, [C.POINTER(BstInput), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
                                i32, i32, vp, C.POINTER(BstInput), i32, vp, vp, vp]),
+    "fx_gru_limits": (None, [vp]),
+    "fx_gru_tile_rows": (i32, [i32]),
+    "fx_gru_grad_floats": (i64, [i32]),
+    "fx_gru_workspace_floats": (i64, [i64, i32]),
+    "fx_gru_seq_fwd": (i32, [C.POINTER(GruInput), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "fx_gru_seq_bwd": (i32, [C.POINTER(GruInput), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                             C.POINTER(GruInput), vp, vp, vp, vp]),
+    "fx_seq_score_workspace_floats": (i64, [i64, i32]),
+    "fx_seq_score_fwd": (i32, [vp, C.POINTER(SeqTarget), vp, i64, i64, i32, i32, vp, i32, vp, vp]),
+    "fx_seq_score_bwd": (i32, [vp, C.POINTER(SeqTarget), vp, i64, i64, i32, i32, vp, i32, vp, vp, vp,
+                               C.POINTER(SeqTarget), vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

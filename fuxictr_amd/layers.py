@@ -4190,6 +4190,196 @@ class BehaviorTransformer(nn.Module):
         return self._run(x, (), (), ids, causal, pool)
 
 
+class _GRUSeqFn(torch.autograd.Function):
+    """One recurrent layer of DIEN over a padded history (DIEN.py:241-294, 373-503) as ONE autograd node: forward one
+    launch (ops.gru_seq_fwd), backward one launch through time and the fixed-order reduce of the per-workgroup
+    parameter gradients (ops.gru_seq_bwd).  -> (states [B, L, H], final [B, H]).  Kept for the backward: the
+    inputs (views, no copy), the ids, the scores and the states; the gates are recomputed.
+    `tensors`: n_parts column parts [B, L, D], then weight_ih, weight_hh, bias_ih, bias_hh."""
+
+    @staticmethod
+    def forward(ctx, mode, ids, scores, n_parts, *tensors):
+        parts = [t if t.stride(2) == 1 else t.contiguous() for t in tensors[:n_parts]]
+        w = tuple(t.contiguous() for t in tensors[n_parts:])
+        if scores is not None:
+            scores = scores.contiguous()
+        B, L, D = parts[0].shape
+        H = D * n_parts
+        dev = parts[0].device
+        states, final = _empty(B, L, H, device=dev), _empty(B, H, device=dev)
+        ops.gru_seq_fwd(parts, ids, scores, mode, *w, states, final)
+        # (through save_for_backward: autograd then notices a parameter or input changed in place before the backward)
+        ctx.save_for_backward(ids, scores, states, *(tuple(parts) + w))
+        ctx.set_materialize_grads(False)          # an unused output hands the kernel a null pointer, not zeros
+        ctx.cfg = (mode, n_parts, B, L, H)
+        return states, final
+
+    @staticmethod
+    def backward(ctx, d_states, d_final):
+        mode, n_parts, B, L, H = ctx.cfg
+        saved = ctx.saved_tensors
+        ids, scores, states = saved[:3]
+        parts, w = list(saved[3:3 + n_parts]), saved[3 + n_parts:]
+        dev = states.device
+        need = ctx.needs_input_grad          # (mode, ids, scores, n_parts, parts.., parameters..)
+        if d_states is None and d_final is None:
+            return (None,) * (8 + n_parts)
+        dparts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[4 + i] else None
+                  for i, t in enumerate(parts)]
+        d_scores = _empty(B, L, device=dev) if scores is not None else None
+        grads = torch.empty(ops.gru_grad_floats(H), dtype=torch.float32, device=dev)
+        ws = _Workspace.get(dev, ops.gru_workspace_floats(B, H), tag="gru")
+        ops.gru_seq_bwd(parts, ids, scores, mode, *w, states,
+                        None if d_states is None else d_states.contiguous(),
+                        None if d_final is None else d_final.contiguous(), dparts, d_scores, grads, ws)
+        HH = 3 * H * H
+        got = (grads[:HH].view(3 * H, H), grads[HH:2 * HH].view(3 * H, H), grads[2 * HH:2 * HH + 3 * H],
+               grads[2 * HH + 3 * H:])
+        dw = tuple(g if need[4 + n_parts + k] else None for k, g in enumerate(got))
+        return (None, None, d_scores if need[2] else None, None) + tuple(dparts) + dw
+
+
+class _SeqScoreFn(torch.autograd.Function):
+    """DIEN's attention scores (DIEN.py:342-370, bilinear and dot) as ONE autograd node: ops.seq_score_fwd /
+    ops.seq_score_bwd (+ the fixed-order reduce of dW).  Kept for the backward: the inputs and the scores.
+    `tgts`: the target's n_parts column parts [B, D]."""
+
+    @staticmethod
+    def forward(ctx, softmax, ids, interest, W, n_parts, *tgts):
+        interest = interest.contiguous()
+        tgts = tuple(t if t.stride(1) == 1 else t.contiguous() for t in tgts)
+        if W is not None:
+            W = W.contiguous()
+        B, L, H = interest.shape
+        scores = _empty(B, L, device=interest.device)
+        ops.seq_score_fwd(interest, tgts, ids, W, softmax, scores)
+        ctx.save_for_backward(ids, interest, W, scores, *tgts)
+        ctx.cfg = (softmax, n_parts)
+        return scores
+
+    @staticmethod
+    def backward(ctx, d_scores):
+        softmax, n_parts = ctx.cfg
+        saved = ctx.saved_tensors
+        ids, interest, W, scores = saved[:4]
+        tgts = saved[4:]
+        B, L, H = interest.shape
+        dev = interest.device
+        need = ctx.needs_input_grad          # (softmax, ids, interest, W, n_parts, tgts..)
+        d_interest = _empty(B, L, H, device=dev) if need[2] else None
+        dtgts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + i] else None
+                 for i, t in enumerate(tgts)]
+        dW = _empty(H, H, device=dev) if W is not None else None
+        ws = _Workspace.get(dev, ops.seq_score_workspace_floats(B, H), tag="seq_score") if W is not None else None
+        ops.seq_score_bwd(interest, tgts, ids, W, softmax, scores, d_scores.contiguous(), d_interest, dtgts, dW, ws)
+        return (None, None, d_interest, dW if W is not None and need[3] else None, None) + tuple(dtgts)
+
+
+class GRU(nn.Module):
+    """torch.nn.GRU(input_size, hidden_size, batch_first=True) as DIEN uses it (DIEN.py:116-125): one layer, one
+    direction, the same parameter names (`weight_ih_l0`, `weight_hh_l0`, `bias_ih_l0`, `bias_hh_l0`) and default
+    initialisation; the recurrence is fx_gru_seq_*.  Instead of a PackedSequence it takes the padded history and
+    the ids of the first sequence field: positions 0 .. len-1 run, len = the number of non-zero ids."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=True, dropout=0.0,
+                 bidirectional=False):
+        super(GRU, self).__init__()
+        if num_layers != 1 or not bias or not batch_first or dropout or bidirectional:
+            raise NotImplementedError("GRU: one biased, batch-first, unidirectional layer without dropout is what "
+                                      "the fused kernel runs")
+        if input_size != hidden_size:
+            raise NotImplementedError("GRU: input_size={} != hidden_size={}, the fused kernel keeps one "
+                                      "width".format(input_size, hidden_size))
+        ops.gru_check(hidden_size, who="GRU")
+        dev = _alloc_device()
+        self.input_size, self.hidden_size = input_size, hidden_size
+        H = hidden_size
+        self.weight_ih_l0 = nn.Parameter(torch.empty(3 * H, H, device=dev))
+        self.weight_hh_l0 = nn.Parameter(torch.empty(3 * H, H, device=dev))
+        self.bias_ih_l0 = nn.Parameter(torch.empty(3 * H, device=dev))
+        self.bias_hh_l0 = nn.Parameter(torch.empty(3 * H, device=dev))
+        for p in self.parameters():
+            nn.init.uniform_(p, -1.0 / math.sqrt(H), 1.0 / math.sqrt(H))
+
+    def _weights(self):
+        return (self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0)
+
+    def forward_parts(self, parts, ids):
+        """parts[i] [B, L, D]: the input's column parts (views are read in place), ids int32 [B, L]
+        -> (states [B, L, H], 0 past len; final [B, H])."""
+        _check_seq_parts(parts, self.hidden_size, "GRU")
+        return _GRUSeqFn.apply("GRU", ids, None, len(parts), *(tuple(parts) + self._weights()))
+
+    def forward(self, x, ids):
+        return self.forward_parts([x], ids)
+
+
+def _check_seq_parts(parts, H, who):
+    n = len(parts)
+    if not 1 <= n <= ops.GRU_MAX_PARTS or any(t.dim() != 3 or t.shape[-1] * n != H for t in parts):
+        raise NotImplementedError("{}: {} parts of {}, the fused kernel takes 1 or {} parts of one width that make "
+                                  "up H={}".format(who, n, [tuple(t.shape) for t in parts], ops.GRU_MAX_PARTS, H))
+    ops.gru_check(H, parts[0].shape[1], who=who)
+
+
+class DynamicGRU(nn.Module):
+    """DIEN's DynamicGRU over AGRUCell / AUGRUCell (DIEN.py:373-503): same constructor, keys
+    `gru_cell.x2h.weight|bias`, `gru_cell.h2h.weight|bias` (Linear modules that hold the parameters, so that
+    BaseModel.reset_parameters gives them Xavier as in the reference; they are never called).  One launch over the
+    padded history instead of a Python loop of cell calls over a PackedSequence."""
+
+    def __init__(self, input_size, hidden_size, bias=True, gru_type="AUGRU"):
+        super(DynamicGRU, self).__init__()
+        if gru_type not in ("AGRU", "AUGRU"):
+            raise NotImplementedError("DynamicGRU: gru_type={}, AGRU and AUGRU are what DIEN.py:466-469 "
+                                      "builds".format(gru_type))
+        if not bias or input_size != hidden_size:
+            raise NotImplementedError("DynamicGRU: the fused kernel runs biased cells of one width (input_size={}, "
+                                      "hidden_size={})".format(input_size, hidden_size))
+        ops.gru_check(hidden_size, who="DynamicGRU")
+        dev = _alloc_device()
+        self.hidden_size, self.gru_type = hidden_size, gru_type
+        self.gru_cell = _Params()
+        self.gru_cell.x2h = nn.Linear(input_size, 3 * hidden_size, device=dev)
+        self.gru_cell.h2h = nn.Linear(hidden_size, 3 * hidden_size, device=dev)
+
+    def forward(self, x, attn_score, ids):
+        """x [B, L, H] the interests, attn_score [B, L], ids int32 [B, L] -> (states, final)."""
+        _check_seq_parts([x], self.hidden_size, "DynamicGRU")
+        cell = self.gru_cell
+        return _GRUSeqFn.apply(self.gru_type, ids, attn_score, 1, x, cell.x2h.weight, cell.h2h.weight, cell.x2h.bias,
+                               cell.h2h.bias)
+
+
+class AttentionLayer(nn.Module):
+    """DIEN's AttentionLayer (DIEN.py:313-370) for `bilinear_attention` (key `W_kernel`, the identity at first) and
+    `dot_attention`, on fx_seq_score_*.  `din_attention` takes its Dice statistics over the compacted (non-empty)
+    rows only, which ties it to the compaction the native layer does without: it is refused."""
+
+    def __init__(self, model_dim, attention_type="bilinear_attention", attention_hidden_units=[80, 40],
+                 attention_activation="Dice", use_attention_softmax=True, attention_dropout=0.0):
+        super(AttentionLayer, self).__init__()
+        assert attention_type in ["bilinear_attention", "dot_attention", "din_attention"], \
+            "attention_type={} is not supported.".format(attention_type)
+        if attention_type == "din_attention":
+            raise NotImplementedError("AttentionLayer: attention_type=din_attention (DIEN.py:358-362) takes its Dice "
+                                      "statistics over the compacted rows; bilinear_attention and dot_attention "
+                                      "are native")
+        ops.gru_check(model_dim, who="AttentionLayer")
+        self.attention_type = attention_type
+        self.use_attention_softmax = bool(use_attention_softmax)
+        if attention_type == "bilinear_attention":
+            self.W_kernel = nn.Parameter(torch.eye(model_dim, device=_alloc_device()))
+
+    def forward_parts(self, sequence_emb, tgts, ids):
+        """sequence_emb [B, L, H], tgts[i] [B, D] the target's column parts, ids int32 [B, L] (0 = padding)."""
+        W = self.W_kernel if self.attention_type == "bilinear_attention" else None
+        return _SeqScoreFn.apply(self.use_attention_softmax, ids, sequence_emb, W, len(tgts), *tgts)
+
+    def forward(self, sequence_emb, target_emb, ids):
+        return self.forward_parts(sequence_emb, [target_emb], ids)
+
+
 class _SideBySideFn(torch.autograd.Function):
     """`buf` [B, Da + Db] already holds a in its first Da columns and b in the rest (both were written in place):
     hand it on as the concatenation of the two, with the gradient's two column slices (row-strided views, read in

@@ -1746,6 +1746,187 @@ def bst_block_bwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool
     return grads
 
 
+# ---- DIEN: GRU / AGRU / AUGRU over a padded history in one launch, and the attention scores ---------
+GRU_MAX_H = 64       # hidden (= input) width of fx_gru_seq_*, a multiple of 4
+GRU_MAX_L = 256
+GRU_MAX_PARTS = 2
+GRU_MODES = {"GRU": 0, "AGRU": 1, "AUGRU": 2}
+
+
+def gru_check(H, L=None, who="gru"):
+    """The limits of fx_gru_seq_* / fx_seq_score_*, raised here before anything is launched."""
+    if H % 4 or not 4 <= H <= GRU_MAX_H:
+        raise NotImplementedError("{}: H={}, the kernel's limit is 4 <= H <= {} and H % 4 == 0"
+                                  .format(who, H, GRU_MAX_H))
+    if L is not None and not 1 <= L <= GRU_MAX_L:
+        raise NotImplementedError("{}: L={}, the kernel's limit is 1 <= L <= {}".format(who, L, GRU_MAX_L))
+
+
+def gru_limits():
+    """(most H, most L, forward grid, backward grid) of fx_gru_seq_*."""
+    lim = (C.c_int32 * 4)()
+    _lib.load().fx_gru_limits(lim)
+    return tuple(int(v) for v in lim)
+
+
+def gru_tile_rows(H):
+    """Samples one workgroup of fx_gru_seq_* keeps on chip."""
+    return int(_lib.load().fx_gru_tile_rows(H))
+
+
+def gru_grad_floats(H):
+    """grads of gru_seq_bwd: [d w_ih (3 H H) | d w_hh (3 H H) | d b_ih (3 H) | d b_hh (3 H)]."""
+    return 6 * H * H + 6 * H
+
+
+def gru_workspace_floats(B, H):
+    return int(_lib.load().fx_gru_workspace_floats(B, H))
+
+
+def seq_score_workspace_floats(B, H):
+    return int(_lib.load().fx_seq_score_workspace_floats(B, H))
+
+
+def _gru_input(parts, who, D=None):
+    n = len(parts)
+    assert 1 <= n <= GRU_MAX_PARTS, who
+    d = _lib.GruInput()
+    D = D or next(t.shape[-1] for t in parts if t is not None)
+    for i, s in enumerate(parts):
+        if s is not None:
+            assert s.dim() == 3 and s.shape[2] == D and s.stride(2) == 1 and s.dtype == torch.float32, who
+            d.seq[i] = s.data_ptr()
+            d.seq_row_ld[i] = s.stride(1) if s.shape[1] > 1 else D
+            d.seq_ld[i] = s.stride(0) if s.shape[0] > 1 else s.shape[1] * d.seq_row_ld[i]
+    d.n_parts, d.D = n, D
+    return d
+
+
+def _seq_target(parts, who, D=None):
+    n = len(parts)
+    assert 1 <= n <= GRU_MAX_PARTS, who
+    d = _lib.SeqTarget()
+    D = D or next(t.shape[-1] for t in parts if t is not None)
+    for i, t in enumerate(parts):
+        if t is not None:
+            assert t.dim() == 2 and t.shape[1] == D and t.stride(1) == 1 and t.dtype == torch.float32, who
+            d.tgt[i], d.tgt_ld[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else D)
+    d.n_parts, d.D = n, D
+    return d
+
+
+def _seq_ids(ids, B, L):
+    assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L) and (L == 1 or ids.stride(1) == 1)
+    return ptr(ids), (ids.stride(0) if B > 1 else L)
+
+
+def _gru_shape(parts):
+    B, L, D = parts[0].shape
+    return B, L, D * len(parts)
+
+
+def _gru_bytes_fwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, final):
+    B, L, H = _gru_shape(parts)
+    return 4.0 * (2 * B * L * H + B * L * (2 if scores is not None else 1) + B * H + 6 * H * H + 6 * H)
+
+
+def _gru_bytes_bwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, d_states, d_final, *a, **kw):
+    B, L, H = _gru_shape(parts)
+    G = min(-(-B // gru_tile_rows(H)), gru_limits()[3])
+    return 4.0 * (B * L * H * (3 + (d_states is not None)) + 3 * B * L + B * H + 6 * H * H + 6 * H
+                  + 2 * G * gru_grad_floats(H))
+
+
+@_timed("gru_seq_fwd", "gru", _gru_bytes_fwd)
+def gru_seq_fwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, final):
+    """One recurrent layer over the history.  parts[i] [B, L, D]: column part i of the input (views with unit stride
+    over D are read in place), ids: int32 [B, L] of the first sequence field (len = its non-zero count; positions
+    0 .. len-1 run), scores: [B, L] a_t or None ("GRU"), mode: a key of GRU_MODES, w_ih / w_hh [3H, H], b_ih / b_hh
+    [3H].  states [B, L, H] (0 past len) and final [B, H], contiguous."""
+    _need_cuda(states, "states")
+    B, L, H = _gru_shape(parts)
+    gru_check(H, L)
+    assert states.is_contiguous() and tuple(states.shape) == (B, L, H) and final.is_contiguous() \
+        and tuple(final.shape) == (B, H)
+    for t in (w_ih, w_hh, b_ih, b_hh):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert tuple(w_ih.shape) == (3 * H, H) and tuple(w_hh.shape) == (3 * H, H)
+    assert scores is None or (scores.is_contiguous() and tuple(scores.shape) == (B, L))
+    ip, iw = _seq_ids(ids, B, L)
+    check(_lib.load().fx_gru_seq_fwd(C.byref(_gru_input(parts, "gru_seq_fwd")), ip, iw, ptr(scores), B, L, H,
+                                     GRU_MODES[mode], ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(states),
+                                     ptr(final), stream_ptr(states.device)), "fx_gru_seq_fwd")
+    return states, final
+
+
+@_timed("gru_seq_bwd", "gru", _gru_bytes_bwd)
+def gru_seq_bwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, d_states, d_final, dparts, d_scores, grads,
+                workspace):
+    """Back-propagation through time from d_states [B, L, H] and / or d_final [B, H] (None: no such gradient):
+    the parts' gradients into dparts[i] (own strides; None: not wanted), d_scores [B, L] (not "GRU") and grads
+    [gru_grad_floats(H)].  workspace: gru_workspace_floats(B, H) floats."""
+    _need_cuda(grads, "grads")
+    B, L, H = _gru_shape(parts)
+    gru_check(H, L)
+    assert states.is_contiguous() and tuple(states.shape) == (B, L, H)
+    assert d_states is None or (d_states.is_contiguous() and tuple(d_states.shape) == (B, L, H))
+    assert d_final is None or (d_final.is_contiguous() and tuple(d_final.shape) == (B, H))
+    assert scores is None or (scores.is_contiguous() and d_scores.is_contiguous()
+                              and tuple(d_scores.shape) == (B, L))
+    assert grads.is_contiguous() and grads.numel() == gru_grad_floats(H)
+    assert workspace.is_contiguous() and workspace.numel() >= gru_workspace_floats(B, H)
+    ip, iw = _seq_ids(ids, B, L)
+    check(_lib.load().fx_gru_seq_bwd(C.byref(_gru_input(parts, "gru_seq_bwd")), ip, iw, ptr(scores), B, L, H,
+                                     GRU_MODES[mode], ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(states),
+                                     ptr(d_states), ptr(d_final), C.byref(_gru_input(dparts, "gru_seq_bwd", H // len(parts))),
+                                     ptr(d_scores), ptr(grads), ptr(workspace), stream_ptr(grads.device)),
+          "fx_gru_seq_bwd")
+    return grads
+
+
+def _score_bytes(interest, tgts, ids, W, softmax, *a, **kw):
+    B, L, H = interest.shape
+    return 4.0 * (B * L * H + 2 * B * L + B * H + (H * H if W is not None else 0))
+
+
+@_timed("seq_score_fwd", "gru", _score_bytes)
+def seq_score_fwd(interest, tgts, ids, W, softmax, scores):
+    """scores[b, t] = (interest[b, t] W) . target[b] (W None: the plain dot), times (ids != 0); with softmax then
+    + -1e9 where ids == 0 and a soft-max over the L positions (a row without an open position: zeros).
+    interest [B, L, H] contiguous, tgts[i] [B, D] the target's column parts, ids int32 [B, L]."""
+    _need_cuda(scores, "scores")
+    B, L, H = interest.shape
+    gru_check(H, L, who="seq_score")
+    assert interest.is_contiguous() and interest.dtype == torch.float32
+    assert scores.is_contiguous() and tuple(scores.shape) == (B, L)
+    assert W is None or (W.is_contiguous() and tuple(W.shape) == (H, H) and W.dtype == torch.float32)
+    ip, iw = _seq_ids(ids, B, L)
+    check(_lib.load().fx_seq_score_fwd(ptr(interest), C.byref(_seq_target(tgts, "seq_score_fwd")), ip, iw, B, L, H,
+                                       ptr(W), 1 if softmax else 0, ptr(scores), stream_ptr(scores.device)),
+          "fx_seq_score_fwd")
+    return scores
+
+
+@_timed("seq_score_bwd", "gru", _score_bytes)
+def seq_score_bwd(interest, tgts, ids, W, softmax, scores, d_scores, d_interest, dtgts, dW, workspace):
+    """From d_scores and the forward's scores: d_interest [B, L, H] (None: not wanted), the target parts' gradients
+    into dtgts[i] (None: not wanted), dW [H, H] (with W).  workspace: seq_score_workspace_floats(B, H) floats."""
+    _need_cuda(d_scores, "d_scores")
+    B, L, H = interest.shape
+    gru_check(H, L, who="seq_score")
+    assert interest.is_contiguous() and scores.is_contiguous() and d_scores.is_contiguous()
+    assert tuple(scores.shape) == (B, L) and tuple(d_scores.shape) == (B, L)
+    assert d_interest is None or (d_interest.is_contiguous() and tuple(d_interest.shape) == (B, L, H))
+    assert W is None or (dW.is_contiguous() and dW.numel() == H * H
+                         and workspace.numel() >= seq_score_workspace_floats(B, H))
+    ip, iw = _seq_ids(ids, B, L)
+    check(_lib.load().fx_seq_score_bwd(ptr(interest), C.byref(_seq_target(tgts, "seq_score_bwd")), ip, iw, B, L, H,
+                                       ptr(W), 1 if softmax else 0, ptr(scores), ptr(d_scores), ptr(d_interest),
+                                       C.byref(_seq_target(dtgts, "seq_score_bwd", H // len(tgts))), ptr(dW), ptr(workspace),
+                                       stream_ptr(d_scores.device)), "fx_seq_score_bwd")
+    return dW
+
+
 # ---- evaluation metrics ---------------------------------------------------------------------------
 def binary_metrics(y_pred, y_true):
     """(logloss, AUC) of float32 device vectors, as sklearn's log_loss / roc_auc_score on float64.

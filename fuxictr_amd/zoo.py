@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM and BST, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST and DIEN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -9,7 +9,8 @@ model_zoo/FinalMLP/src/FinalMLP.py:49-127, model_zoo/FinalMLP/src/DualMLP.py:44-
 model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96,
 model_zoo/DCN/DCN_torch/src/DCN.py:24-101, model_zoo/FwFM/src/FwFM.py:24-91,
 model_zoo/FmFM/src/FmFM.py:25-94,
-model_zoo/BST/src/BST.py:33-366), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/BST/src/BST.py:33-366,
+model_zoo/DIEN/src/DIEN.py:27-503), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -19,7 +20,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (BehaviorTransformer, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (AttentionLayer, BehaviorTransformer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -812,3 +813,151 @@ class BST(_ZooModel):
         # so the dict's order is nothing to build the DNN's input on)
         rest = [emb[f] for f in self.feature_map.features if f in emb and f not in dropped]
         return {"y_pred": self.dnn(torch.cat(rest + pooled, dim=-1))}
+
+
+def _flat_len(fields):
+    """len(list(pandas.core.common.flatten([fields]))): the names in a str / tuple / list of them."""
+    if isinstance(fields, (list, tuple)):
+        return sum(_flat_len(f) for f in fields)
+    return 1
+
+
+class DIEN(_ZooModel):
+    """Deep Interest Evolution Network (DIEN.py:27-310): per (target, sequence) pair a GRU over the history
+    (interest extraction), attention scores of its states against the target, and an attention-gated GRU towards
+    the target (interest evolution), next to the other fields' embeddings in front of the DNN.  Three launches per
+    pair and direction (layers.GRU, layers.AttentionLayer, layers.DynamicGRU); the lengths stay on the device:
+    no host read, no compaction of the batch, no packing, so the step captures into a hipGraph.
+    Not native, each for the reason its message gives: aux_loss_alpha > 0, gru_type="AIGRU" (both raise in the
+    reference as well) and attention_type="din_attention"."""
+
+    def __init__(self, feature_map, model_id="DIEN", gpu=-1, dnn_hidden_units=[200, 80], dnn_activations="ReLU",
+                 learning_rate=1e-3, embedding_dim=16, net_dropout=0, batch_norm=True,
+                 dien_target_field=[("item_id", "cate_id")], dien_sequence_field=[("click_history", "cate_history")],
+                 dien_neg_seq_field=[("neg_click_history", "neg_cate_history")], gru_type="AUGRU",
+                 enable_sum_pooling=False, attention_dropout=0, attention_type="bilinear_attention",
+                 attention_hidden_units=[80, 40], attention_activation="Dice", use_attention_softmax=True,
+                 aux_hidden_units=[100, 50], aux_activation="ReLU", aux_loss_alpha=0, embedding_regularizer=None,
+                 net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        as_list = lambda f: f if isinstance(f, list) else [f]                  # noqa: E731
+        as_field = lambda f: tuple(f) if isinstance(f, list) else f            # noqa: E731
+        self.dien_target_field = [as_field(f) for f in as_list(dien_target_field)]
+        self.dien_sequence_field = [as_field(f) for f in as_list(dien_sequence_field)]
+        assert len(self.dien_target_field) == len(self.dien_sequence_field), \
+            "dien_sequence_field or dien_target_field not supported."
+        self.dien_neg_seq_field = [as_field(f) for f in as_list(dien_neg_seq_field)]
+        if aux_loss_alpha > 0:
+            raise NotImplementedError("DIEN: aux_loss_alpha > 0 is not native; the reference's own auxiliary loss "
+                                      "raises at DIEN.py:228 (the .view of a non-contiguous cat; the mask and loss "
+                                      "shapes of DIEN.py:235-237 do not broadcast either)")
+        if gru_type == "AIGRU":
+            raise NotImplementedError("DIEN: gru_type=AIGRU is not native; the reference raises at DIEN.py:283 "
+                                      "([B, L, H] * [B, L] does not broadcast)")
+        if gru_type not in ("GRU", "AGRU", "AUGRU"):
+            raise ValueError("gru_type={} not supported.".format(gru_type))
+        if attention_dropout:
+            raise NotImplementedError("DIEN: attention_dropout > 0 only acts inside din_attention, which is not "
+                                      "native")
+        self.aux_loss_alpha = aux_loss_alpha
+        self.feature_map = feature_map
+        self.embedding_dim = embedding_dim
+        self.embedding_layer = FeatureEmbeddingDict(feature_map, embedding_dim)
+        self.sum_pooling = MaskedSumPooling()
+        self.gru_type = gru_type
+        self.extraction_modules = nn.ModuleList()
+        self.evolving_modules = nn.ModuleList()
+        self.attention_modules = nn.ModuleList()
+        feature_dim = 0
+        for target_field, sequence_field in zip(self.dien_target_field, self.dien_sequence_field):
+            model_dim = embedding_dim * _flat_len(target_field)
+            if len(_fields(sequence_field)) != len(_fields(target_field)):
+                raise ValueError("DIEN: target {} and sequence {} differ in their number of fields"
+                                 .format(target_field, sequence_field))
+            seq_len = feature_map.features[_fields(sequence_field)[0]]["max_len"]
+            ops.gru_check(model_dim, seq_len, who="DIEN")
+            if len(_fields(target_field)) > ops.GRU_MAX_PARTS:
+                raise NotImplementedError("DIEN: {} grouped fields, the fused kernels take 1 or {}"
+                                          .format(len(_fields(target_field)), ops.GRU_MAX_PARTS))
+            feature_dim += model_dim * 2
+            self.extraction_modules.append(GRU(input_size=model_dim, hidden_size=model_dim, batch_first=True))
+            if gru_type in ["AGRU", "AUGRU"]:
+                self.evolving_modules.append(DynamicGRU(model_dim, model_dim, gru_type=gru_type))
+                self.attention_modules.append(
+                    AttentionLayer(model_dim, attention_type=attention_type,
+                                   attention_hidden_units=attention_hidden_units,
+                                   attention_activation=attention_activation,
+                                   use_attention_softmax=use_attention_softmax, attention_dropout=attention_dropout))
+            else:
+                self.evolving_modules.append(GRU(input_size=model_dim, hidden_size=model_dim, batch_first=True))
+        # the reference's own width (DIEN.py:134-138): it subtracts the neg-sequence fields whether or not the
+        # feature map has them
+        feature_dim = feature_dim + feature_map.sum_emb_out_dim() - embedding_dim * _flat_len(self.dien_neg_seq_field)
+        self.enable_sum_pooling = enable_sum_pooling
+        if not self.enable_sum_pooling:
+            feature_dim -= embedding_dim * _flat_len(self.dien_target_field) * 2
+        built = self._dnn_input_width()
+        if built != feature_dim:        # the reference's shape error at the DNN's first matmul, raised here
+            raise RuntimeError("DIEN: mat1 and mat2 shapes cannot be multiplied (Bx{} and {}x{}): DIEN.py:134-135 "
+                               "subtracts dien_neg_seq_field={} from the DNN's width, the forward assembles {} "
+                               "columns; pass dien_neg_seq_field=[] when the feature map has no such features"
+                               .format(built, feature_dim, dnn_hidden_units[0] if dnn_hidden_units else 1,
+                                       self.dien_neg_seq_field, built))
+        self.dnn = self._tower(feature_dim, dnn_hidden_units, dnn_activations, net_dropout, batch_norm,
+                               output_activation=self.output_activation)
+        self._ready(kwargs, learning_rate)
+
+    def _neg_names(self):
+        names = set()
+        for f in self.dien_neg_seq_field:
+            names.update(_fields(f))
+        return names
+
+    def _dnn_input_width(self):
+        """What forward() concatenates in front of the DNN."""
+        D = self.embedding_dim
+        width = 0
+        for target_field in self.dien_target_field:
+            width += D * _flat_len(target_field) * (3 if self.enable_sum_pooling else 1)
+        neg = self._neg_names()
+        for name, spec in self.feature_map.features.items():
+            if spec["type"] == "meta" or name in neg:
+                continue
+            if spec["type"] == "sequence" and not spec.get("feature_encoder"):
+                continue                                        # [B, L, D]: not a 2-D embedding
+            width += spec.get("emb_output_dim", spec.get("embedding_dim", D))
+        return width
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # name -> [B, D] | [B, L, D]
+        concat_emb = []
+        interest_emb = pad_mask = sequence_emb = None
+        for idx, (target_field, sequence_field) in enumerate(zip(self.dien_target_field, self.dien_sequence_field)):
+            seq_names = _fields(sequence_field)
+            tgts = [emb[f] for f in _fields(target_field)]
+            seqs = [emb[f] for f in seq_names]
+            # padding_idx 0 (DIEN.py:177 on the FIRST sequence field): the packed int32 id columns are the lengths
+            # and the mask; they never leave the device
+            ids = self.embedding_layer.packed_ids(X, seq_names[0])
+            if ids is None:
+                ids = X[seq_names[0]].to(torch.int32).contiguous()
+            interest_emb, final = self.extraction_modules[idx].forward_parts(seqs, ids)
+            if self.gru_type == "GRU":
+                _, final = self.evolving_modules[idx].forward_parts([interest_emb], ids)
+            else:
+                scores = self.attention_modules[idx].forward_parts(interest_emb, tgts, ids)
+                _, final = self.evolving_modules[idx](interest_emb, scores, ids)
+            concat_emb.append(final)
+            sequence_emb = seqs[0] if len(seqs) == 1 else torch.cat(seqs, dim=-1)
+            pad_mask = ids != 0
+            if self.enable_sum_pooling:
+                sum_pool = [self.sum_pooling(s) for s in seqs]
+                concat_emb += sum_pool + [t * s for t, s in zip(tgts, sum_pool)]
+        # the other fields in the feature map's order (DIEN.py:189 follows the batch dict's own order, which is the
+        # loaders' = the feature map's; a captured step's static batch is ordered by packed matrix)
+        neg = self._neg_names()
+        concat_emb += [emb[f] for f in self.feature_map.features if f in emb and emb[f].dim() == 2 and f not in neg]
+        y_pred = self.dnn(torch.cat(concat_emb, dim=-1))
+        return {"y_pred": y_pred, "interest_emb": interest_emb, "neg_emb": None, "pad_mask": pad_mask,
+                "pos_emb": sequence_emb}

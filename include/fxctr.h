@@ -1018,6 +1018,74 @@ int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld,
                      float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DIEN (csrc/fx_gru.hip): the recurrent layers and the attention scores of the Deep Interest Evolution Network
+ * (model_zoo/DIEN/src/DIEN.py:241-262 interest_extraction, DIEN.py:264-294 interest_evolution, DIEN.py:342-370
+ * AttentionLayer, DIEN.py:388-408 AGRUCell, DIEN.py:426-448 AUGRUCell, DIEN.py:471-503 DynamicGRU; torch.nn.GRU's
+ * weight_ih_l0 / weight_hh_l0), without the host read of the lengths, the compaction and the packing:
+ *     len[b] = the number of non-zero ids[b, :] (the FIRST sequence field); the recurrence runs over the positions
+ *     0 .. len-1 whatever the padding layout (what pack_padded_sequence keeps), from h = 0:
+ *         gx = w_ih x_t + b_ih,  gh = w_hh h + b_hh        w_ih, w_hh [3H, H], three chunks of H rows
+ *         r = sigmoid(gx_r + gh_r),  n = tanh(gx_n + r * gh_n),  h' = h + g * (n - h)
+ *         mode 0 GRU   chunks (r, z, n): g = 1 - sigmoid(gx_z + gh_z)
+ *         mode 1 AGRU  chunks (u, r, n): g = scores[b, t]                      (the u chunk is unused)
+ *         mode 2 AUGRU chunks (u, r, n): g = sigmoid(gx_u + gh_u) * scores[b, t]
+ *     states [B, L, H] = h' per position, 0 past len;  final_state [B, H] = h after position len-1, 0 for len = 0.
+ *   fx_gru_input: X [B, L, H] as n_parts (1 or 2) column parts of D = H / n_parts floats: part i of position t is
+ *   seq[i] + b * seq_ld[i] + t * seq_row_ld[i] (views into the gather record are read in place).
+ *   fx_gru_seq_fwd : one launch; a workgroup keeps a tile of fx_gru_tile_rows(H) samples' hidden states and both
+ *                    weight matrices in LDS for the whole sequence.
+ *   fx_gru_seq_bwd : back-propagation through time in one launch from d_states [B, L, H] and / or d_final [B, H]
+ *                    (either may be NULL), re-reading `states` and recomputing the gates: dX through `dx` (the same
+ *                    description; a NULL part: not wanted), d_scores [B, L] (modes 1, 2; 0 past len), the
+ *                    per-workgroup rows of the parameter gradients into `workspace`, then a fixed-order sum:
+ *                    grads = [d w_ih (3 H H) | d w_hh (3 H H) | d b_ih (3H) | d b_hh (3H)] (fx_gru_grad_floats).
+ *                    In mode 1 the u rows of all four are exact zeros.
+ *   fx_seq_score_fwd : scores[b, t] = (interest[b, t] W) . target[b]  (W [H, H]; NULL: the plain dot), times
+ *                    mask[b, t] = (ids[b, t] != 0); with `softmax` then + -1e9 (1 - mask) and a soft-max over all L
+ *                    positions.  A row without any open position gives zeros (the reference never sees one).
+ *                    interest [B, L, H] contiguous, 16-byte aligned; fx_seq_target: the target's column parts.
+ *   fx_seq_score_bwd : from d_scores and the forward's `scores`: d_interest [B, L, H] (nullable), the target's
+ *                    gradient through `d_tgt` (a NULL part: not wanted), dW [H, H] (with W) by per-workgroup rows
+ *                    in `workspace` and a fixed-order sum.
+ *   No atomics: two runs give the same bits.  fp32.
+ *   Limits: H % 4 == 0, 4 <= H <= 64, 1 <= L <= 256.
+ *   fx_gru_limits : limits[4] = {most H, most L, forward grid, backward grid} (housekeeping).
+ *   fx_gru_tile_rows : samples per workgroup tile (housekeeping).
+ *   fx_gru_workspace_floats, fx_seq_score_workspace_floats : floats of the backward workspaces (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fx_gru_input {
+    const float* seq[2];
+    int64_t seq_ld[2];
+    int64_t seq_row_ld[2];
+    int32_t n_parts;
+    int32_t D;
+} fx_gru_input;
+typedef struct fx_seq_target {
+    const float* tgt[2];
+    int64_t tgt_ld[2];
+    int32_t n_parts;
+    int32_t D;
+} fx_seq_target;
+void fx_gru_limits(int32_t* limits);
+int32_t fx_gru_tile_rows(int32_t H);
+int64_t fx_gru_grad_floats(int32_t H);
+int64_t fx_gru_workspace_floats(int64_t B, int32_t H);
+int fx_gru_seq_fwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
+                   int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh, const float* b_ih,
+                   const float* b_hh, float* states, float* final_state, fx_stream_t stream);
+int fx_gru_seq_bwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
+                   int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh, const float* b_ih,
+                   const float* b_hh, const float* states, const float* d_states, const float* d_final,
+                   const fx_gru_input* dx, float* d_scores, float* grads, float* workspace, fx_stream_t stream);
+int64_t fx_seq_score_workspace_floats(int64_t B, int32_t H);
+int fx_seq_score_fwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
+                     int32_t L, int32_t H, const float* W, int32_t softmax, float* scores, fx_stream_t stream);
+int fx_seq_score_bwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
+                     int32_t L, int32_t H, const float* W, int32_t softmax, const float* scores,
+                     const float* d_scores, float* d_interest, const fx_seq_target* d_tgt, float* dW,
+                     float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
