@@ -63,29 +63,19 @@ class GemmStrategyRecord(C.Structure):
                 ("tr", i32 * 4), ("plain_vec", i32 * 4)]
 
 
-# name -> (restype, argtypes).  This table is also what tests/test_abi.py checks against the header.
-class BstInput(C.Structure):
-    """struct fx_bst_input"""
-    _fields_ = [("seq", vp * 3), ("tgt", vp * 3), ("seq_ld", i64 * 3), ("seq_row_ld", i64 * 3), ("tgt_ld", i64 * 3),
-                ("pos", vp), ("n_parts", i32), ("D", i32)]
+class SeqParts(C.Structure):
+    """struct fx_seq_parts"""
+    _fields_ = [("seq", vp * 3), ("seq_ld", i64 * 3), ("seq_row_ld", i64 * 3), ("tgt", vp * 3), ("tgt_ld", i64 * 3),
+                ("n_parts", i32), ("D", i32)]
 
 
 class BstWeights(C.Structure):
     """struct fx_bst_weights"""
     _fields_ = [(n, vp) for n in ("in_w", "in_b", "out_w", "out_b", "w1", "b1", "w2", "b2", "ln1_w", "ln1_b",
-                                  "ln2_w", "ln2_b")]
+                                  "ln2_w", "ln2_b", "pos")]
 
 
-class GruInput(C.Structure):
-    """struct fx_gru_input"""
-    _fields_ = [("seq", vp * 2), ("seq_ld", i64 * 2), ("seq_row_ld", i64 * 2), ("n_parts", i32), ("D", i32)]
-
-
-class SeqTarget(C.Structure):
-    """struct fx_seq_target"""
-    _fields_ = [("tgt", vp * 2), ("tgt_ld", i64 * 2), ("n_parts", i32), ("D", i32)]
-
-
+# name -> (restype, argtypes).  This table is also what tests/test_abi.py checks against the header.
 SIGNATURES = {
     "fx_abi_version": (i32, []),
     "fx_last_error": (C.c_char_p, []),
@@ -201,21 +191,21 @@ SIGNATURES = {
     "fx_bst_limits": (None, [vp]),
     "fx_bst_grad_floats": (i64, [i32, i32, i32]),
     "fx_bst_workspace_floats": (i64, [i64, i32, i32, i32]),
-    "fx_bst_block_fwd": (i32, [C.POINTER(BstInput), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
+    "fx_bst_block_fwd": (i32, [C.POINTER(SeqParts), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
                                i32, i32, vp, vp]),
-    "fx_bst_block_bwd": (i32, [C.POINTER(BstInput), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
-                               i32, i32, vp, C.POINTER(BstInput), i32, vp, vp, vp]),
+    "fx_bst_block_bwd": (i32, [C.POINTER(SeqParts), vp, i64, i64, i32, i32, i32, C.POINTER(BstWeights), i32, i32,
+                               i32, i32, vp, C.POINTER(SeqParts), i32, vp, vp, vp]),
     "fx_gru_limits": (None, [vp]),
     "fx_gru_tile_rows": (i32, [i32]),
     "fx_gru_grad_floats": (i64, [i32]),
     "fx_gru_workspace_floats": (i64, [i64, i32]),
-    "fx_gru_seq_fwd": (i32, [C.POINTER(GruInput), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "fx_gru_seq_bwd": (i32, [C.POINTER(GruInput), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
-                             C.POINTER(GruInput), vp, vp, vp, vp]),
+    "fx_gru_seq_fwd": (i32, [C.POINTER(SeqParts), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "fx_gru_seq_bwd": (i32, [C.POINTER(SeqParts), vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                             C.POINTER(SeqParts), vp, vp, vp, vp]),
     "fx_seq_score_workspace_floats": (i64, [i64, i32]),
-    "fx_seq_score_fwd": (i32, [vp, C.POINTER(SeqTarget), vp, i64, i64, i32, i32, vp, i32, vp, vp]),
-    "fx_seq_score_bwd": (i32, [vp, C.POINTER(SeqTarget), vp, i64, i64, i32, i32, vp, i32, vp, vp, vp,
-                               C.POINTER(SeqTarget), vp, vp, vp]),
+    "fx_seq_score_fwd": (i32, [vp, C.POINTER(SeqParts), vp, i64, i64, i32, i32, vp, i32, vp, vp]),
+    "fx_seq_score_bwd": (i32, [vp, C.POINTER(SeqParts), vp, i64, i64, i32, i32, vp, i32, vp, vp, vp,
+                               C.POINTER(SeqParts), vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

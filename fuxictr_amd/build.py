@@ -19,6 +19,7 @@ SOURCES = ["fx_api.cpp", "fx_embed.hip", "fx_sparse.hip", "fx_gemm.hip", "fx_gem
            "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip", "fx_gru.hip"]
 HEADERS = [os.path.join(CSRC, "fx_common.h"), os.path.join(CSRC, "fx_cin.h"), os.path.join(CSRC, "fx_gemm_int.h"),
            os.path.join(CSRC, "fx_dice_int.h"), os.path.join(CSRC, "fx_rowsum.h"), os.path.join(CSRC, "fx_attn_lds.h"),
+           os.path.join(CSRC, "fx_seq_parts.h"),
            os.path.join(HERE, "..", "include", "fxctr.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -27,6 +27,7 @@
 //   sp  P -> out before LN2 -> xhat2 -> dz1 -> P        sd  g -> d out -> ds -> d s -> dP / dS
 //   + rstd1, rstd2, pad (64 each), the bias gradients (10 dm), d position_emb (L1 * D), the weights when they fit.
 #include "fx_attn_lds.h"
+#include "fx_seq_parts.h"
 
 #define BT_T FX_ATTN_T
 #define BT_MAX FX_ATTN_MAX
@@ -38,8 +39,9 @@
 enum { BT_POOL_NONE = 0, BT_POOL_MEAN = 1, BT_POOL_SUM = 2, BT_POOL_TARGET = 3 };
 
 struct BstArgs {
-    fx_bst_input in;         // the sample's parts
-    fx_bst_input din;        // where their gradients go (backward)
+    fx_seq_parts in;         // the sample's parts
+    const float* pos;        // position_emb [L1, D] or null
+    fx_seq_parts din;        // where the parts' gradients go (backward)
     const int32_t* ids;      // [B, L] ids of the first sequence field, row stride ids_ld; null: nothing is padded
     int64_t ids_ld;
     int64_t B;
@@ -66,10 +68,10 @@ __device__ __forceinline__ void bt_load_x(const BstArgs& p, int64_t b, float* sX
         const int f = idx / dm, c = idx - f * dm, part = c / D, cc = c - part * D;
         float v;
         if (part < p.np) {
-            v = f == L ? p.in.tgt[part][b * p.in.tgt_ld[part] + cc]
-                       : p.in.seq[part][b * p.in.seq_ld[part] + f * p.in.seq_row_ld[part] + cc];
+            v = f == L ? p.in.tgt[part][fx_parts_tgt_off(p.in, part, b, cc)]
+                       : p.in.seq[part][fx_parts_seq_off(p.in, part, b, f, cc)];
         } else {
-            v = p.in.pos[f * D + cc];
+            v = p.pos[f * D + cc];
         }
         sX[f * DS + c] = v;
     }
@@ -226,12 +228,9 @@ __device__ __forceinline__ void bt_put_dx(const BstArgs& p, int64_t b, int f, in
                                           float* sDpos) {
     const int D = p.D, part = c / D, cc = c - part * D;
     if (part < p.np) {
-        float* dst = f == p.L1 - 1 ? const_cast<float*>(p.din.tgt[part])
-                                   : const_cast<float*>(p.din.seq[part]);
-        if (dst == nullptr) return;
-        dst += f == p.L1 - 1 ? b * p.din.tgt_ld[part] + cc
-                             : b * p.din.seq_ld[part] + f * p.din.seq_row_ld[part] + cc;
-        *dst = acc ? *dst + v : v;
+        const bool tgt = f == p.L1 - 1;
+        fx_parts_put(tgt ? p.din.tgt[part] : p.din.seq[part],
+                     tgt ? fx_parts_tgt_off(p.din, part, b, cc) : fx_parts_seq_off(p.din, part, b, f, cc), v, acc);
     } else {
         sDpos[f * D + cc] += v;
     }
@@ -320,7 +319,7 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
     int* sPad = reinterpret_cast<int*>(sR2 + BT_MAX);
     float* sDB = reinterpret_cast<float*>(sPad + BT_MAX);     // in_b 3dm | out_b | b1 | b2 | ln1 w, b | ln2 w, b
     float* sDpos = sDB + 10 * dm;
-    const int n_pos = p.in.pos != nullptr ? L1 * p.D : 0;
+    const int n_pos = p.pos != nullptr ? L1 * p.D : 0;
     float* sW = sDpos + n_pos;
     const FxAttnW<6, WLDS> w = fx_attn_weights<6, WLDS>(p.W, 6, dm, dm, sW);
     for (int i = threadIdx.x; i < 10 * dm + n_pos; i += BT_T) sDB[i] = 0.f;
@@ -451,9 +450,8 @@ __global__ __launch_bounds__(BT_T) void k_bst_bwd(BstArgs p) {
 static inline int64_t bt_n_grad(int L1, int dm, int pos_D) {
     return 6 * (int64_t)dm * dm + 10 * (int64_t)dm + (int64_t)L1 * pos_D;
 }
-static inline int64_t bt_al4(int64_t n) { return (n + 3) / 4 * 4; }
 
-static int bt_check(const char* who, const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
+static int bt_check(const char* who, const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
                     int32_t dm, int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t pool) {
     FX_CHECK_ARG(in && w, "%s: null input / weights description", who);
     FX_CHECK_ARG(L1 >= 1 && L1 <= BT_MAX, "%s: L1=%d, limit 1 <= L1 <= 64", who, L1);
@@ -462,17 +460,15 @@ static int bt_check(const char* who, const fx_bst_input* in, const int32_t* ids,
     FX_CHECK_ARG(in->n_parts >= 1 && in->n_parts <= 3, "%s: n_parts=%d, limit 1 <= n_parts <= 3", who, in->n_parts);
     FX_CHECK_ARG(in->D >= 1 && dm % in->D == 0 && dm / in->D <= 4, "%s: D=%d must divide dm=%d at most 4 times", who,
                  in->D, dm);
-    FX_CHECK_ARG(dm / in->D == in->n_parts + (in->pos ? 1 : 0), "%s: dm=%d is not (n_parts=%d%s) * D=%d", who, dm,
-                 in->n_parts, in->pos ? " + position_emb" : "", in->D);
+    FX_CHECK_ARG(dm / in->D == in->n_parts + (w->pos ? 1 : 0), "%s: dm=%d is not (n_parts=%d%s) * D=%d", who, dm,
+                 in->n_parts, w->pos ? " + position_emb" : "", in->D);
     FX_CHECK_ARG(pool >= BT_POOL_NONE && pool <= BT_POOL_TARGET, "%s: pool=%d", who, pool);
     FX_CHECK_ARG(B >= 0, "%s: B=%lld", who, (long long)B);
     if (B == 0) return FX_OK;
     for (int i = 0; i < in->n_parts; ++i) {
-        FX_CHECK_ARG(in->tgt[i] && (L1 == 1 || in->seq[i]), "%s: null part %d", who, i);
-        FX_CHECK_ARG(L1 == 1 || (in->seq_row_ld[i] >= in->D && in->seq_ld[i] >= (L1 - 1) * in->seq_row_ld[i]),
-                     "%s: part %d: strides %lld / %lld below D / (L1 - 1) rows", who, i, (long long)in->seq_row_ld[i],
-                     (long long)in->seq_ld[i]);
-        FX_CHECK_ARG(in->tgt_ld[i] >= in->D, "%s: part %d: target stride %lld < D", who, i, (long long)in->tgt_ld[i]);
+        if (int st = fx_parts_check_tgt(who, "part", in, i, in->D, false)) return st;
+        if (L1 == 1) continue;
+        if (int st = fx_parts_check_seq(who, "part", in, i, in->D, L1 - 1, false)) return st;
     }
     FX_CHECK_ARG(!ids || ids_ld >= L1 - 1, "%s: ids stride %lld < L", who, (long long)ids_ld);
     FX_CHECK_ARG(w->in_w && w->in_b && w->out_w && w->out_b && w->w1 && w->b1 && w->w2 && w->b2,
@@ -481,12 +477,13 @@ static int bt_check(const char* who, const fx_bst_input* in, const int32_t* ids,
     return FX_OK;
 }
 
-static BstArgs bt_args(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
+static BstArgs bt_args(const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
                        int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual, int32_t causal,
                        int32_t pool) {
     BstArgs p;
     memset(&p, 0, sizeof(p));
     p.in = *in;
+    p.pos = w->pos;
     p.ids = ids; p.ids_ld = ids_ld; p.B = B;
     p.L1 = L1; p.dm = dm; p.H = H; p.hd = dm / H; p.D = in->D; p.np = in->n_parts;
     p.HG = fx_attn_heads_per_pass(L1, H);
@@ -520,11 +517,11 @@ extern "C" int64_t fx_bst_grad_floats(int32_t L1, int32_t dm, int32_t pos_D) { r
 
 extern "C" int64_t fx_bst_workspace_floats(int64_t B, int32_t L1, int32_t dm, int32_t pos_D) {
     const int64_t G = B < BT_BWD_GRID ? (B > 0 ? B : 1) : BT_BWD_GRID;
-    const int64_t n4 = bt_al4(bt_n_grad(L1, dm, pos_D));
+    const int64_t n4 = fx_al4(bt_n_grad(L1, dm, pos_D));
     return G * n4 + FX_COLSUM_CHUNKS * n4;
 }
 
-extern "C" int fx_bst_block_fwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
+extern "C" int fx_bst_block_fwd(const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
                                 int32_t dm, int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual,
                                 int32_t causal, int32_t pool, float* Y, fx_stream_t stream) {
     if (int st = bt_check("fx_bst_block_fwd", in, ids, ids_ld, B, L1, dm, H, w, layer_norm, pool)) return st;
@@ -548,28 +545,25 @@ static int bt_launch_bwd(const BstArgs& p, unsigned grid, size_t lds, hipStream_
     return fx_attn_launch<k_bst_bwd<WLDS, 16>>(p, grid, lds, s);
 }
 
-extern "C" int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
+extern "C" int fx_bst_block_bwd(const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1,
                                 int32_t dm, int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual,
-                                int32_t causal, int32_t pool, const float* dY, const fx_bst_input* din,
+                                int32_t causal, int32_t pool, const float* dY, const fx_seq_parts* din,
                                 int32_t dx_accumulate, float* grads, float* workspace, fx_stream_t stream) {
     if (int st = bt_check("fx_bst_block_bwd", in, ids, ids_ld, B, L1, dm, H, w, layer_norm, pool)) return st;
     FX_CHECK_ARG(B > 0, "fx_bst_block_bwd: B=%lld", (long long)B);
     FX_CHECK_ARG(dY && din && grads && workspace, "fx_bst_block_bwd: null dY / gradient description / grads / workspace");
     FX_CHECK_ARG(fx_al16(workspace), "fx_bst_block_bwd: the workspace is not 16-byte aligned");
     for (int i = 0; i < in->n_parts; ++i) {
-        FX_CHECK_ARG(!din->seq[i] || L1 == 1 ||
-                         (din->seq_row_ld[i] >= in->D && din->seq_ld[i] >= (L1 - 1) * din->seq_row_ld[i]),
-                     "fx_bst_block_bwd: gradient of part %d: strides %lld / %lld below D / (L1 - 1) rows", i,
-                     (long long)din->seq_row_ld[i], (long long)din->seq_ld[i]);
-        FX_CHECK_ARG(!din->tgt[i] || din->tgt_ld[i] >= in->D, "fx_bst_block_bwd: gradient of part %d: target stride "
-                     "%lld < D", i, (long long)din->tgt_ld[i]);
+        if (int st = fx_parts_check_tgt("fx_bst_block_bwd", "gradient of part", din, i, in->D, true)) return st;
+        if (L1 == 1) continue;
+        if (int st = fx_parts_check_seq("fx_bst_block_bwd", "gradient of part", din, i, in->D, L1 - 1, true)) return st;
     }
     BstArgs p = bt_args(in, ids, ids_ld, B, L1, dm, H, w, layer_norm, residual, causal, pool);
     p.din = *din;
     p.dY = dY;
     p.dx_acc = dx_accumulate ? 1 : 0;
-    const int pos_D = in->pos ? in->D : 0;
-    const int64_t n = bt_n_grad(L1, dm, pos_D), n4 = bt_al4(n);
+    const int pos_D = w->pos ? in->D : 0;
+    const int64_t n = bt_n_grad(L1, dm, pos_D), n4 = fx_al4(n);
     p.partial = workspace;
     p.n_grad = n4;
     const size_t small = 3 * BT_MAX + 10 * (size_t)dm + (size_t)L1 * pos_D;

@@ -20,6 +20,7 @@
 // two weight-gradient matrices in registers over the workgroup's tiles and steps (entry e belongs to thread
 // e % 256); one row of partial sums per workgroup, added in fixed order by fx_rowsum.
 #include "fx_rowsum.h"
+#include "fx_seq_parts.h"
 
 #define GR_T 256
 #define GR_S 2               // samples per thread
@@ -35,8 +36,8 @@
 enum { GR_GRU = 0, GR_AGRU = 1, GR_AUGRU = 2 };
 
 struct GruArgs {
-    fx_gru_input x;          // the layer's input
-    fx_gru_input dx;         // where its gradient goes (backward; a null part is skipped)
+    fx_seq_parts x;          // the layer's input: the sequence side
+    fx_seq_parts dx;         // where its gradient goes (backward; a null part is skipped)
     const int32_t* ids;      // [B, L] ids of the first sequence field, row stride ids_ld
     int64_t ids_ld;
     const float* scores;     // [B, L] a_t (AGRU, AUGRU)
@@ -57,12 +58,6 @@ struct GruArgs {
 };
 
 __device__ __forceinline__ float gr_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-// element (b, t, c) of X through its parts
-__device__ __forceinline__ int64_t gr_x_off(const fx_gru_input& x, int D, int64_t b, int t, int c, int& part) {
-    part = c / D;
-    return b * x.seq_ld[part] + (int64_t)t * x.seq_row_ld[part] + (c - part * D);
-}
 
 struct GruLds {
     float* sWi;      // [H][3H + 1]: W_ih transposed
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(GR_T) void k_gru_fwd(GruArgs p) {
             h[i] = 0.f;
             if (live) {
                 int part;
-                const int64_t off = gr_x_off(p.x, p.D, b0 + s0 + i, 0, j, part);
+                const int64_t off = fx_parts_seq_off(p.x, p.D, b0 + s0 + i, 0, j, part);
                 l.sX[(s0 + i) * HS + j] = len[i] > 0 ? p.x.seq[part][off] : 0.f;
                 l.sH[(s0 + i) * HS + j] = 0.f;
             }
@@ -186,7 +181,7 @@ __global__ __launch_bounds__(GR_T) void k_gru_fwd(GruArgs p) {
                     at[i] = 0.f;
                     if (t + 1 < len[i]) {
                         int part;
-                        const int64_t off = gr_x_off(p.x, p.D, b, t + 1, j, part);
+                        const int64_t off = fx_parts_seq_off(p.x, p.D, b, t + 1, j, part);
                         xn[i] = p.x.seq[part][off];
                     }
                     if (t < len[i] && p.mode != GR_GRU) at[i] = p.scores[b * L + t];
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(GR_T) void k_gru_bwd(GruArgs p) {
                 float xv = 0.f, hv = 0.f;
                 if (t >= 0 && t < len[i]) {
                     int part;
-                    const int64_t off = gr_x_off(p.x, p.D, b, t, j, part);
+                    const int64_t off = fx_parts_seq_off(p.x, p.D, b, t, j, part);
                     xv = p.x.seq[part][off];
                     if (t > 0) hv = p.hs[(b * L + t - 1) * H + j];
                 }
@@ -286,7 +281,7 @@ __global__ __launch_bounds__(GR_T) void k_gru_bwd(GruArgs p) {
                     dh[i] = sDh[(s0 + i) * HS + j];
                     if (t - 1 >= 0 && t - 1 < len[i]) {
                         int part;
-                        const int64_t off = gr_x_off(p.x, p.D, b, t - 1, j, part);
+                        const int64_t off = fx_parts_seq_off(p.x, p.D, b, t - 1, j, part);
                         xn[i] = p.x.seq[part][off];
                         if (t - 1 > 0) hn[i] = p.hs[(b * L + t - 2) * H + j];
                     }
@@ -352,9 +347,8 @@ __global__ __launch_bounds__(GR_T) void k_gru_bwd(GruArgs p) {
                     const int64_t b = b0 + s0 + i;
                     if (b < p.B) {
                         int part;
-                        const int64_t off = gr_x_off(p.dx, p.D, b, t, j, part);
-                        float* dst = const_cast<float*>(p.dx.seq[part]);
-                        if (dst != nullptr) dst[off] = dxv;
+                        const int64_t off = fx_parts_seq_off(p.dx, p.D, b, t, j, part);
+                        fx_parts_put(p.dx.seq[part], off, dxv, false);
                     }
                     sDh[(s0 + i) * HS + j] = dhv;
                     sXn[(s0 + i) * HS + j] = xn[i];
@@ -406,32 +400,30 @@ __global__ __launch_bounds__(GR_T) void k_gru_bwd(GruArgs p) {
                 if (b >= p.B) continue;
                 for (int t = maxlen; t < L; ++t) {
                     int part;
-                    const int64_t off = gr_x_off(p.dx, p.D, b, t, j, part);
-                    float* dst = const_cast<float*>(p.dx.seq[part]);
-                    if (dst != nullptr) dst[off] = 0.f;
+                    const int64_t off = fx_parts_seq_off(p.dx, p.D, b, t, j, part);
+                    fx_parts_put(p.dx.seq[part], off, 0.f, false);
                     if (j == 0 && p.d_scores != nullptr) p.d_scores[b * L + t] = 0.f;
                 }
             }
         }
     }
-    float* part = p.partial + (int64_t)blockIdx.x * p.n_grad;
+    float* row = p.partial + (int64_t)blockIdx.x * p.n_grad;
     {
         int e = threadIdx.x;
 #pragma unroll
         for (int r = 0; r < R; ++r, e += GR_T) {
             if (e < H3 * H) {
-                part[e] = accI[r];
-                part[H3 * H + e] = accH[r];
+                row[e] = accI[r];
+                row[H3 * H + e] = accH[r];
             }
         }
     }
     if ((int)threadIdx.x < H3) {
-        part[2 * H3 * H + threadIdx.x] = dbi;
-        part[2 * H3 * H + H3 + threadIdx.x] = dbh;
+        row[2 * H3 * H + threadIdx.x] = dbi;
+        row[2 * H3 * H + H3 + threadIdx.x] = dbh;
     }
 }
 
-static inline int64_t gr_al4(int64_t n) { return (n + 3) / 4 * 4; }
 static inline int64_t gr_n_grad(int H) { return 6 * (int64_t)H * H + 6 * (int64_t)H; }
 static inline int gr_tile(int H) { return GR_S * (GR_T / H); }
 static inline int64_t gr_tiles(int64_t B, int H) { return (B + gr_tile(H) - 1) / gr_tile(H); }
@@ -443,7 +435,7 @@ static inline size_t gr_lds_floats(int H, bool backward) {
     return n;
 }
 
-static int gr_check(const char* who, const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores,
+static int gr_check(const char* who, const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores,
                     int64_t B, int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh,
                     const float* b_ih, const float* b_hh) {
     FX_CHECK_ARG(x, "%s: null input description", who);
@@ -454,19 +446,15 @@ static int gr_check(const char* who, const fx_gru_input* x, const int32_t* ids, 
                  "%s: H=%d is not n_parts=%d (1 or 2) * D=%d", who, H, x->n_parts, x->D);
     FX_CHECK_ARG(B >= 0, "%s: B=%lld", who, (long long)B);
     if (B == 0) return FX_OK;
-    for (int i = 0; i < x->n_parts; ++i) {
-        FX_CHECK_ARG(x->seq[i], "%s: null part %d", who, i);
-        FX_CHECK_ARG(x->seq_row_ld[i] >= x->D && x->seq_ld[i] >= (int64_t)L * x->seq_row_ld[i],
-                     "%s: part %d: strides %lld / %lld below D / L rows", who, i, (long long)x->seq_row_ld[i],
-                     (long long)x->seq_ld[i]);
-    }
+    for (int i = 0; i < x->n_parts; ++i)
+        if (int st = fx_parts_check_seq(who, "part", x, i, x->D, L, false)) return st;
     FX_CHECK_ARG(ids && ids_ld >= L, "%s: null ids or ids stride %lld < L", who, (long long)ids_ld);
     FX_CHECK_ARG(mode == GR_GRU || scores, "%s: null scores", who);
     FX_CHECK_ARG(w_ih && w_hh && b_ih && b_hh, "%s: null weight or bias", who);
     return FX_OK;
 }
 
-static GruArgs gr_args(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
+static GruArgs gr_args(const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
                        int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh, const float* b_ih,
                        const float* b_hh) {
     GruArgs p;
@@ -502,10 +490,10 @@ extern "C" int64_t fx_gru_grad_floats(int32_t H) { return gr_n_grad(H); }
 extern "C" int64_t fx_gru_workspace_floats(int64_t B, int32_t H) {
     if (H < 4 || H > GR_MAX_H) return 0;
     const int64_t tiles = gr_tiles(B > 0 ? B : 1, H);
-    return (tiles < GR_BWD_GRID ? tiles : GR_BWD_GRID) * gr_al4(gr_n_grad(H));
+    return (tiles < GR_BWD_GRID ? tiles : GR_BWD_GRID) * fx_al4(gr_n_grad(H));
 }
 
-extern "C" int fx_gru_seq_fwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores,
+extern "C" int fx_gru_seq_fwd(const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores,
                               int64_t B, int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh,
                               const float* b_ih, const float* b_hh, float* states, float* final_state,
                               fx_stream_t stream) {
@@ -530,10 +518,10 @@ static int gr_launch_bwd(const GruArgs& p, unsigned grid, size_t lds, hipStream_
     return gr_launch<k_gru_bwd<48>>(p, grid, lds, s);
 }
 
-extern "C" int fx_gru_seq_bwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores,
+extern "C" int fx_gru_seq_bwd(const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores,
                               int64_t B, int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh,
                               const float* b_ih, const float* b_hh, const float* states, const float* d_states,
-                              const float* d_final, const fx_gru_input* dx, float* d_scores, float* grads,
+                              const float* d_final, const fx_seq_parts* dx, float* d_scores, float* grads,
                               float* workspace, fx_stream_t stream) {
     if (int st = gr_check("fx_gru_seq_bwd", x, ids, ids_ld, scores, B, L, H, mode, w_ih, w_hh, b_ih, b_hh)) return st;
     FX_CHECK_ARG(B > 0, "fx_gru_seq_bwd: B=%lld", (long long)B);
@@ -544,16 +532,14 @@ extern "C" int fx_gru_seq_bwd(const fx_gru_input* x, const int32_t* ids, int64_t
     FX_CHECK_ARG(dx->n_parts == x->n_parts && dx->D == x->D, "fx_gru_seq_bwd: the gradient's parts differ from the "
                  "input's");
     for (int i = 0; i < x->n_parts; ++i)
-        FX_CHECK_ARG(!dx->seq[i] || (dx->seq_row_ld[i] >= x->D && dx->seq_ld[i] >= (int64_t)L * dx->seq_row_ld[i]),
-                     "fx_gru_seq_bwd: gradient of part %d: strides %lld / %lld below D / L rows", i,
-                     (long long)dx->seq_row_ld[i], (long long)dx->seq_ld[i]);
+        if (int st = fx_parts_check_seq("fx_gru_seq_bwd", "gradient of part", dx, i, x->D, L, true)) return st;
     GruArgs p = gr_args(x, ids, ids_ld, scores, B, L, H, mode, w_ih, w_hh, b_ih, b_hh);
     p.dx = *dx;
     p.hs = states;
     p.d_states = d_states;
     p.d_final = d_final;
     p.d_scores = mode == GR_GRU ? nullptr : d_scores;
-    const int64_t n = gr_n_grad(H), n4 = gr_al4(n);
+    const int64_t n = gr_n_grad(H), n4 = fx_al4(n);
     p.partial = workspace;
     p.n_grad = n4;
     const int64_t tiles = gr_tiles(B, H);
@@ -568,8 +554,8 @@ extern "C" int fx_gru_seq_bwd(const fx_gru_input* x, const int32_t* ids, int64_t
 // ---- the attention scores ---------------------------------------------------------------------------------
 struct ScoreArgs {
     const float* I;          // interest [B, L, H], contiguous
-    fx_seq_target tgt;
-    fx_seq_target dtgt;      // backward; a null part is skipped
+    fx_seq_parts tgt;
+    fx_seq_parts dtgt;      // backward; a null part is skipped
     const int32_t* ids;
     int64_t ids_ld;
     int64_t B;
@@ -604,7 +590,7 @@ __device__ __forceinline__ void sc_target(const ScoreArgs& p, const ScoreLds& l,
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, H = p.H, HS = H | 1;
     if (lane < H) {
         const int part = lane / p.D;
-        l.sT[w * GR_MAX_H + lane] = valid ? p.tgt.tgt[part][b * p.tgt.tgt_ld[part] + lane - part * p.D] : 0.f;
+        l.sT[w * GR_MAX_H + lane] = valid ? p.tgt.tgt[part][fx_parts_tgt_off(p.tgt, part, b, lane - part * p.D)] : 0.f;
     }
     __syncthreads();
     if (lane < H) {
@@ -756,8 +742,7 @@ __global__ __launch_bounds__(GR_T) void k_seq_score_bwd(ScoreArgs p) {
                 for (int c = 0; c < H; ++c) dt = fmaf(l.sW[c * HS + lane], l.sV[w * GR_MAX_H + c], dt);
             }
             const int part = lane / p.D;
-            float* dst = const_cast<float*>(p.dtgt.tgt[part]);
-            if (dst != nullptr) dst[b * p.dtgt.tgt_ld[part] + lane - part * p.D] = dt;
+            fx_parts_put(p.dtgt.tgt[part], fx_parts_tgt_off(p.dtgt, part, b, lane - part * p.D), dt, false);
         }
         if (p.W != nullptr) {                                        // dW[k][c] += d(W target)[k] * target[c]
             int e = threadIdx.x;
@@ -784,7 +769,7 @@ __global__ __launch_bounds__(GR_T) void k_seq_score_bwd(ScoreArgs p) {
     }
 }
 
-static int sc_check(const char* who, const float* interest, const fx_seq_target* tgt, const int32_t* ids,
+static int sc_check(const char* who, const float* interest, const fx_seq_parts* tgt, const int32_t* ids,
                     int64_t ids_ld, int64_t B, int32_t L, int32_t H) {
     FX_CHECK_ARG(tgt, "%s: null target description", who);
     FX_CHECK_ARG(H >= 4 && H <= GR_MAX_H && H % 4 == 0, "%s: H=%d, limit 4 <= H <= 64 and H %% 4 == 0", who, H);
@@ -795,13 +780,12 @@ static int sc_check(const char* who, const float* interest, const fx_seq_target*
     if (B == 0) return FX_OK;
     FX_CHECK_ARG(interest && fx_al16(interest), "%s: interest is null or not 16-byte aligned", who);
     for (int i = 0; i < tgt->n_parts; ++i)
-        FX_CHECK_ARG(tgt->tgt[i] && tgt->tgt_ld[i] >= tgt->D, "%s: target part %d is null or its stride %lld < D", who,
-                     i, (long long)tgt->tgt_ld[i]);
+        if (int st = fx_parts_check_tgt(who, "part", tgt, i, tgt->D, false)) return st;
     FX_CHECK_ARG(ids && ids_ld >= L, "%s: null ids or ids stride %lld < L", who, (long long)ids_ld);
     return FX_OK;
 }
 
-static ScoreArgs sc_args(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld,
+static ScoreArgs sc_args(const float* interest, const fx_seq_parts* tgt, const int32_t* ids, int64_t ids_ld,
                          int64_t B, int32_t L, int32_t H, const float* W, int32_t softmax) {
     ScoreArgs p;
     memset(&p, 0, sizeof(p));
@@ -819,10 +803,10 @@ static inline unsigned sc_grid(int64_t B) {
 }
 
 extern "C" int64_t fx_seq_score_workspace_floats(int64_t B, int32_t H) {
-    return (int64_t)sc_grid(B > 0 ? B : 1) * gr_al4((int64_t)H * H);
+    return (int64_t)sc_grid(B > 0 ? B : 1) * fx_al4((int64_t)H * H);
 }
 
-extern "C" int fx_seq_score_fwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld,
+extern "C" int fx_seq_score_fwd(const float* interest, const fx_seq_parts* tgt, const int32_t* ids, int64_t ids_ld,
                                 int64_t B, int32_t L, int32_t H, const float* W, int32_t softmax, float* scores,
                                 fx_stream_t stream) {
     if (int st = sc_check("fx_seq_score_fwd", interest, tgt, ids, ids_ld, B, L, H)) return st;
@@ -835,9 +819,9 @@ extern "C" int fx_seq_score_fwd(const float* interest, const fx_seq_target* tgt,
     return FX_OK;
 }
 
-extern "C" int fx_seq_score_bwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld,
+extern "C" int fx_seq_score_bwd(const float* interest, const fx_seq_parts* tgt, const int32_t* ids, int64_t ids_ld,
                                 int64_t B, int32_t L, int32_t H, const float* W, int32_t softmax, const float* scores,
-                                const float* d_scores, float* d_interest, const fx_seq_target* d_tgt, float* dW,
+                                const float* d_scores, float* d_interest, const fx_seq_parts* d_tgt, float* dW,
                                 float* workspace, fx_stream_t stream) {
     if (int st = sc_check("fx_seq_score_bwd", interest, tgt, ids, ids_ld, B, L, H)) return st;
     FX_CHECK_ARG(B > 0, "fx_seq_score_bwd: B=%lld", (long long)B);
@@ -846,15 +830,14 @@ extern "C" int fx_seq_score_bwd(const float* interest, const fx_seq_target* tgt,
     FX_CHECK_ARG(!W || (dW && workspace && fx_al16(workspace)), "fx_seq_score_bwd: null dW / workspace, or the "
                  "workspace is not 16-byte aligned");
     for (int i = 0; i < tgt->n_parts; ++i)
-        FX_CHECK_ARG(!d_tgt->tgt[i] || d_tgt->tgt_ld[i] >= tgt->D, "fx_seq_score_bwd: gradient of target part %d: "
-                     "stride %lld < D", i, (long long)d_tgt->tgt_ld[i]);
+        if (int st = fx_parts_check_tgt("fx_seq_score_bwd", "gradient of part", d_tgt, i, tgt->D, true)) return st;
     ScoreArgs p = sc_args(interest, tgt, ids, ids_ld, B, L, H, W, softmax);
     p.dtgt = *d_tgt;
     p.P = scores;
     p.dS = d_scores;
     p.dI = d_interest;
     p.partial = workspace;
-    p.n_grad = gr_al4((int64_t)H * H);
+    p.n_grad = fx_al4((int64_t)H * H);
     const unsigned grid = sc_grid(B);
     hipStream_t s = fx_hip_stream(stream);
     const size_t lds = sc_lds_bytes(H);
@@ -865,5 +848,5 @@ extern "C" int fx_seq_score_bwd(const float* interest, const fx_seq_target* tgt,
     else hipLaunchKernelGGL(k_seq_score_bwd<16>, dim3(grid), dim3(GR_T), lds, s, p);
     FX_CHECK_LAUNCH();
     if (!W) return FX_OK;
-    return fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, (int)grid, gr_al4(HH), fx_rowsum_out(dW, HH));
+    return fx_rowsum<double, FX_ROWS_SLICES>(s, workspace, (int)grid, fx_al4(HH), fx_rowsum_out(dW, HH));
 }

@@ -123,6 +123,21 @@ def _empty(*shape, device):
     return torch.empty(*shape, dtype=torch.float32, device=device)
 
 
+def _grad_dests(tensors, need):
+    """Where a kernel writes the gradients of `tensors`: an empty tensor per wanted one, None (a null destination:
+    nothing of it is written) for the others."""
+    return [_empty(t.shape, device=t.device) if n else None for t, n in zip(tensors, need)]
+
+
+def _split(seq, *counts):
+    """`seq` cut into lists of the given lengths, and the rest."""
+    out, at = [], 0
+    for n in counts:
+        out.append(list(seq[at:at + n]))
+        at += n
+    return out + [tuple(seq[at:])]
+
+
 class _BatchState(object):
     """What the embedding path has already done for ONE batch: its packed input matrices (a captured
     step keeps them as its static buffers) and the results of the current step's launches."""
@@ -3993,9 +4008,9 @@ class _BSTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, ids, pos, x, n_parts, *tensors):
         H, layer_norm, residual, causal, pool = cfg
-        seqs = [t if t.stride(2) == 1 else t.contiguous() for t in tensors[:n_parts]]
-        tgts = [t if t.stride(1) == 1 else t.contiguous() for t in tensors[n_parts:2 * n_parts]]
-        w = tuple(None if t is None else t.contiguous() for t in tensors[2 * n_parts:])
+        seqs, tgts, w = _split(tensors, n_parts, n_parts)
+        seqs, tgts = [_unit_cols(t) for t in seqs], [_unit_cols(t) for t in tgts]
+        w = tuple(None if t is None else t.contiguous() for t in w)
         if x is not None:
             x = x.contiguous()
             D = pos.shape[1] if pos is not None else x.shape[2]
@@ -4016,9 +4031,7 @@ class _BSTBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         B, L1, dm, D, n_parts = ctx.shape
-        saved = ctx.saved_tensors
-        x, pos, ids = saved[:3]
-        seqs, tgts, w = list(saved[3:3 + n_parts]), list(saved[3 + n_parts:3 + 2 * n_parts]), saved[3 + 2 * n_parts:]
+        (x, pos, ids), seqs, tgts, w = _split(ctx.saved_tensors, 3, n_parts, n_parts)
         H, layer_norm, residual, causal, pool = ctx.cfg
         dev = dy.device
         need = ctx.needs_input_grad          # (cfg, ids, pos, x, n_parts, parts.., parameters..)
@@ -4029,10 +4042,7 @@ class _BSTBlockFn(torch.autograd.Function):
             dparts = ()
         else:                                # a part nobody differentiates is not written (a null destination)
             dx = None
-            dseqs = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + i] else None
-                     for i, t in enumerate(seqs)]
-            dtgts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + n_parts + i] else None
-                     for i, t in enumerate(tgts)]
+            dseqs, dtgts = _grad_dests(seqs, need[5:]), _grad_dests(tgts, need[5 + n_parts:])
             dparts = tuple(dseqs) + tuple(dtgts)
         pos_D = D if pos is not None else 0
         grads = torch.empty(ops.bst_grad_floats(L1, dm, pos_D), dtype=torch.float32, device=dev)
@@ -4199,8 +4209,8 @@ class _GRUSeqFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, ids, scores, n_parts, *tensors):
-        parts = [t if t.stride(2) == 1 else t.contiguous() for t in tensors[:n_parts]]
-        w = tuple(t.contiguous() for t in tensors[n_parts:])
+        parts, w = _split(tensors, n_parts)
+        parts, w = [_unit_cols(t) for t in parts], tuple(t.contiguous() for t in w)
         if scores is not None:
             scores = scores.contiguous()
         B, L, D = parts[0].shape
@@ -4217,15 +4227,12 @@ class _GRUSeqFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_states, d_final):
         mode, n_parts, B, L, H = ctx.cfg
-        saved = ctx.saved_tensors
-        ids, scores, states = saved[:3]
-        parts, w = list(saved[3:3 + n_parts]), saved[3 + n_parts:]
+        (ids, scores, states), parts, w = _split(ctx.saved_tensors, 3, n_parts)
         dev = states.device
         need = ctx.needs_input_grad          # (mode, ids, scores, n_parts, parts.., parameters..)
         if d_states is None and d_final is None:
             return (None,) * (8 + n_parts)
-        dparts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[4 + i] else None
-                  for i, t in enumerate(parts)]
+        dparts = _grad_dests(parts, need[4:])
         d_scores = _empty(B, L, device=dev) if scores is not None else None
         grads = torch.empty(ops.gru_grad_floats(H), dtype=torch.float32, device=dev)
         ws = _Workspace.get(dev, ops.gru_workspace_floats(B, H), tag="gru")
@@ -4247,7 +4254,7 @@ class _SeqScoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, softmax, ids, interest, W, n_parts, *tgts):
         interest = interest.contiguous()
-        tgts = tuple(t if t.stride(1) == 1 else t.contiguous() for t in tgts)
+        tgts = tuple(_unit_cols(t) for t in tgts)
         if W is not None:
             W = W.contiguous()
         B, L, H = interest.shape
@@ -4260,15 +4267,12 @@ class _SeqScoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_scores):
         softmax, n_parts = ctx.cfg
-        saved = ctx.saved_tensors
-        ids, interest, W, scores = saved[:4]
-        tgts = saved[4:]
+        (ids, interest, W, scores), tgts = _split(ctx.saved_tensors, 4)
         B, L, H = interest.shape
         dev = interest.device
         need = ctx.needs_input_grad          # (softmax, ids, interest, W, n_parts, tgts..)
         d_interest = _empty(B, L, H, device=dev) if need[2] else None
-        dtgts = [torch.empty(t.shape, dtype=torch.float32, device=dev) if need[5 + i] else None
-                 for i, t in enumerate(tgts)]
+        dtgts = _grad_dests(tgts, need[5:])
         dW = _empty(H, H, device=dev) if W is not None else None
         ws = _Workspace.get(dev, ops.seq_score_workspace_floats(B, H), tag="seq_score") if W is not None else None
         ops.seq_score_bwd(interest, tgts, ids, W, softmax, scores, d_scores.contiguous(), d_interest, dtgts, dW, ws)

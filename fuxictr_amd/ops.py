@@ -1647,33 +1647,51 @@ def bst_flops(B, L1, dm, backward=False):
     return B * (fwd + 2.0 * L1 * dm * (15 * dm + 5 * L1) if backward else fwd)
 
 
-def _bst_input(seqs, tgts, pos, who):
-    n = len(tgts)
-    assert 1 <= n <= BST_MAX_PARTS and len(seqs) == n, who
-    d = _lib.BstInput()
-    D = next((t.shape[-1] for t in list(tgts) + list(seqs) if t is not None), 1)
-    for i, (s, t) in enumerate(zip(seqs, tgts)):
+SEQ_MAX_PARTS = 3    # room in struct fx_seq_parts; the entry points keep their own limits (BST 3, DIEN 2)
+
+
+def _seq_parts(seqs, tgts, who, D=None):
+    """struct fx_seq_parts of the sequence parts seqs[i] [B, L, D] and / or the target parts tgts[i] [B, D].  A side
+    that is None stays null, and so does a part that is None (a gradient nobody wants; D then comes from the
+    caller).  Unit stride over D, every other stride the tensor's own; an axis of extent 1, whose stride torch
+    leaves arbitrary, gets the dense one."""
+    sides = [list(p) for p in (tgts, seqs) if p is not None]
+    n = len(sides[0])
+    assert 1 <= n <= SEQ_MAX_PARTS and all(len(p) == n for p in sides), who
+    d = _lib.SeqParts()
+    D = D or next((t.shape[-1] for p in sides for t in p if t is not None), 1)
+    for i, t in enumerate(tgts or ()):
         if t is not None:
             assert t.dim() == 2 and t.shape[1] == D and t.stride(1) == 1 and t.dtype == torch.float32, who
             d.tgt[i], d.tgt_ld[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else D)
+    for i, s in enumerate(seqs or ()):
         if s is not None and s.shape[1] > 0:
             assert s.dim() == 3 and s.shape[2] == D and s.stride(2) == 1 and s.dtype == torch.float32, who
             d.seq[i] = s.data_ptr()
             d.seq_row_ld[i] = s.stride(1) if s.shape[1] > 1 else D
             d.seq_ld[i] = s.stride(0) if s.shape[0] > 1 else s.shape[1] * d.seq_row_ld[i]
-    if pos is not None:
-        assert pos.is_contiguous() and pos.shape[1] == D and pos.dtype == torch.float32, who
-        d.pos = pos.data_ptr()
     d.n_parts, d.D = n, D
     return d
 
 
-def _bst_weights(w):
+def _seq_ids(ids, B, L, nullable=False):
+    """(pointer, row stride) of the int32 ids [B, L] of the first sequence field; None (nothing is padded) only
+    where nullable."""
+    if ids is None and nullable:
+        return vp(0), 0
+    assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L) and (L <= 1 or ids.stride(1) == 1)
+    return ptr(ids), (ids.stride(0) if B > 1 else L)
+
+
+def _bst_weights(w, pos, D):
     s = _lib.BstWeights()
     for name, t in zip(BST_WEIGHTS, w):
         if t is not None:
             assert t.is_contiguous() and t.dtype == torch.float32, name
             setattr(s, name, t.data_ptr())
+    if pos is not None:
+        assert pos.is_contiguous() and pos.shape[1] == D and pos.dtype == torch.float32, "position_emb"
+        s.pos = pos.data_ptr()
     return s
 
 
@@ -1681,13 +1699,6 @@ def _bst_shape(seqs, tgts, pos):
     B, D = tgts[0].shape
     L1 = (seqs[0].shape[1] if seqs[0] is not None else 0) + 1
     return B, L1, D * (len(tgts) + (1 if pos is not None else 0)), D
-
-
-def _bst_ids(ids, B, L1):
-    if ids is None:
-        return vp(0), 0
-    assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L1 - 1) and (L1 == 1 or ids.stride(1) == 1)
-    return ptr(ids), (ids.stride(0) if B > 1 else L1 - 1)
 
 
 def _bst_bytes_fwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool, Y):
@@ -1715,9 +1726,9 @@ def bst_block_fwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool
     B, L1, dm, D = _bst_shape(seqs, tgts, pos)
     bst_check(L1, dm, H, D)
     assert Y.is_contiguous() and Y.numel() == (B * L1 * dm if BST_POOLS[pool] == 0 else B * dm)
-    ip, iw = _bst_ids(ids, B, L1)
-    check(_lib.load().fx_bst_block_fwd(C.byref(_bst_input(seqs, tgts, pos, "bst_block_fwd")), ip, iw, B, L1, dm, H,
-                                       C.byref(_bst_weights(w)), 1 if layer_norm else 0, 1 if residual else 0,
+    ip, iw = _seq_ids(ids, B, L1 - 1, nullable=True)
+    check(_lib.load().fx_bst_block_fwd(C.byref(_seq_parts(seqs, tgts, "bst_block_fwd")), ip, iw, B, L1, dm, H,
+                                       C.byref(_bst_weights(w, pos, D)), 1 if layer_norm else 0, 1 if residual else 0,
                                        1 if causal else 0, BST_POOLS[pool], ptr(Y), stream_ptr(Y.device)),
           "fx_bst_block_fwd")
     return Y
@@ -1736,10 +1747,10 @@ def bst_block_bwd(seqs, tgts, pos, ids, w, H, layer_norm, residual, causal, pool
     assert dY.is_contiguous() and dY.numel() == (B * L1 * dm if BST_POOLS[pool] == 0 else B * dm)
     assert grads.is_contiguous() and grads.numel() == bst_grad_floats(L1, dm, pos_D)
     assert workspace.is_contiguous() and workspace.numel() >= bst_workspace_floats(B, L1, dm, pos_D)
-    ip, iw = _bst_ids(ids, B, L1)
-    din = _bst_input(dseqs, dtgts, None, "bst_block_bwd")
-    check(_lib.load().fx_bst_block_bwd(C.byref(_bst_input(seqs, tgts, pos, "bst_block_bwd")), ip, iw, B, L1, dm, H,
-                                       C.byref(_bst_weights(w)), 1 if layer_norm else 0, 1 if residual else 0,
+    ip, iw = _seq_ids(ids, B, L1 - 1, nullable=True)
+    din = _seq_parts(dseqs, dtgts, "bst_block_bwd", D)
+    check(_lib.load().fx_bst_block_bwd(C.byref(_seq_parts(seqs, tgts, "bst_block_bwd")), ip, iw, B, L1, dm, H,
+                                       C.byref(_bst_weights(w, pos, D)), 1 if layer_norm else 0, 1 if residual else 0,
                                        1 if causal else 0, BST_POOLS[pool], ptr(dY), C.byref(din),
                                        1 if dx_accumulate else 0, ptr(grads), ptr(workspace),
                                        stream_ptr(dY.device)), "fx_bst_block_bwd")
@@ -1787,39 +1798,6 @@ def seq_score_workspace_floats(B, H):
     return int(_lib.load().fx_seq_score_workspace_floats(B, H))
 
 
-def _gru_input(parts, who, D=None):
-    n = len(parts)
-    assert 1 <= n <= GRU_MAX_PARTS, who
-    d = _lib.GruInput()
-    D = D or next(t.shape[-1] for t in parts if t is not None)
-    for i, s in enumerate(parts):
-        if s is not None:
-            assert s.dim() == 3 and s.shape[2] == D and s.stride(2) == 1 and s.dtype == torch.float32, who
-            d.seq[i] = s.data_ptr()
-            d.seq_row_ld[i] = s.stride(1) if s.shape[1] > 1 else D
-            d.seq_ld[i] = s.stride(0) if s.shape[0] > 1 else s.shape[1] * d.seq_row_ld[i]
-    d.n_parts, d.D = n, D
-    return d
-
-
-def _seq_target(parts, who, D=None):
-    n = len(parts)
-    assert 1 <= n <= GRU_MAX_PARTS, who
-    d = _lib.SeqTarget()
-    D = D or next(t.shape[-1] for t in parts if t is not None)
-    for i, t in enumerate(parts):
-        if t is not None:
-            assert t.dim() == 2 and t.shape[1] == D and t.stride(1) == 1 and t.dtype == torch.float32, who
-            d.tgt[i], d.tgt_ld[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else D)
-    d.n_parts, d.D = n, D
-    return d
-
-
-def _seq_ids(ids, B, L):
-    assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L) and (L == 1 or ids.stride(1) == 1)
-    return ptr(ids), (ids.stride(0) if B > 1 else L)
-
-
 def _gru_shape(parts):
     B, L, D = parts[0].shape
     return B, L, D * len(parts)
@@ -1853,7 +1831,7 @@ def gru_seq_fwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, final)
     assert tuple(w_ih.shape) == (3 * H, H) and tuple(w_hh.shape) == (3 * H, H)
     assert scores is None or (scores.is_contiguous() and tuple(scores.shape) == (B, L))
     ip, iw = _seq_ids(ids, B, L)
-    check(_lib.load().fx_gru_seq_fwd(C.byref(_gru_input(parts, "gru_seq_fwd")), ip, iw, ptr(scores), B, L, H,
+    check(_lib.load().fx_gru_seq_fwd(C.byref(_seq_parts(parts, None, "gru_seq_fwd")), ip, iw, ptr(scores), B, L, H,
                                      GRU_MODES[mode], ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(states),
                                      ptr(final), stream_ptr(states.device)), "fx_gru_seq_fwd")
     return states, final
@@ -1876,10 +1854,11 @@ def gru_seq_bwd(parts, ids, scores, mode, w_ih, w_hh, b_ih, b_hh, states, d_stat
     assert grads.is_contiguous() and grads.numel() == gru_grad_floats(H)
     assert workspace.is_contiguous() and workspace.numel() >= gru_workspace_floats(B, H)
     ip, iw = _seq_ids(ids, B, L)
-    check(_lib.load().fx_gru_seq_bwd(C.byref(_gru_input(parts, "gru_seq_bwd")), ip, iw, ptr(scores), B, L, H,
+    check(_lib.load().fx_gru_seq_bwd(C.byref(_seq_parts(parts, None, "gru_seq_bwd")), ip, iw, ptr(scores), B, L, H,
                                      GRU_MODES[mode], ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(states),
-                                     ptr(d_states), ptr(d_final), C.byref(_gru_input(dparts, "gru_seq_bwd", H // len(parts))),
-                                     ptr(d_scores), ptr(grads), ptr(workspace), stream_ptr(grads.device)),
+                                     ptr(d_states), ptr(d_final),
+                                     C.byref(_seq_parts(dparts, None, "gru_seq_bwd", H // len(parts))), ptr(d_scores),
+                                     ptr(grads), ptr(workspace), stream_ptr(grads.device)),
           "fx_gru_seq_bwd")
     return grads
 
@@ -1901,7 +1880,7 @@ def seq_score_fwd(interest, tgts, ids, W, softmax, scores):
     assert scores.is_contiguous() and tuple(scores.shape) == (B, L)
     assert W is None or (W.is_contiguous() and tuple(W.shape) == (H, H) and W.dtype == torch.float32)
     ip, iw = _seq_ids(ids, B, L)
-    check(_lib.load().fx_seq_score_fwd(ptr(interest), C.byref(_seq_target(tgts, "seq_score_fwd")), ip, iw, B, L, H,
+    check(_lib.load().fx_seq_score_fwd(ptr(interest), C.byref(_seq_parts(None, tgts, "seq_score_fwd")), ip, iw, B, L, H,
                                        ptr(W), 1 if softmax else 0, ptr(scores), stream_ptr(scores.device)),
           "fx_seq_score_fwd")
     return scores
@@ -1920,10 +1899,10 @@ def seq_score_bwd(interest, tgts, ids, W, softmax, scores, d_scores, d_interest,
     assert W is None or (dW.is_contiguous() and dW.numel() == H * H
                          and workspace.numel() >= seq_score_workspace_floats(B, H))
     ip, iw = _seq_ids(ids, B, L)
-    check(_lib.load().fx_seq_score_bwd(ptr(interest), C.byref(_seq_target(tgts, "seq_score_bwd")), ip, iw, B, L, H,
+    check(_lib.load().fx_seq_score_bwd(ptr(interest), C.byref(_seq_parts(None, tgts, "seq_score_bwd")), ip, iw, B, L, H,
                                        ptr(W), 1 if softmax else 0, ptr(scores), ptr(d_scores), ptr(d_interest),
-                                       C.byref(_seq_target(dtgts, "seq_score_bwd", H // len(tgts))), ptr(dW), ptr(workspace),
-                                       stream_ptr(d_scores.device)), "fx_seq_score_bwd")
+                                       C.byref(_seq_parts(None, dtgts, "seq_score_bwd", H // len(tgts))), ptr(dW),
+                                       ptr(workspace), stream_ptr(d_scores.device)), "fx_seq_score_bwd")
     return dW
 
 

@@ -49,6 +49,13 @@ class _ZooModel(BaseModel):
         """The model's `fused` keyword; without it the environment switch `env_name` (on unless "0")."""
         return bool(kwargs.get("fused", _os.environ.get(env_name, "1") != "0"))
 
+    def _first_seq_ids(self, X, sequence, fallback):
+        """The packed int32 ids of a pair's FIRST sequence field (0 = padding: the mask and the lengths, on the
+        device); a batch that was not packed gets the model's own `fallback(X[name])`."""
+        name = _fields(sequence)[0]
+        ids = self.embedding_layer.packed_ids(X, name)
+        return ids if ids is not None else fallback(X[name])
+
     def _tower(self, input_dim, units, activations, dropout, batch_norm, output_dim=1,
                output_activation=None):
         return MLP_Block(input_dim=input_dim, output_dim=output_dim, hidden_units=units,
@@ -145,6 +152,19 @@ def _fields(spec):
     return tuple(spec) if isinstance(spec, (list, tuple)) else (spec,)
 
 
+def _field_list(option):
+    """A *_target_field / *_sequence_field / *_neg_seq_field option as the reference's public attribute: a list
+    whose entries are a str, or a tuple for grouped fields."""
+    return [tuple(f) if isinstance(f, list) else f for f in (option if isinstance(option, list) else [option])]
+
+
+def _field_pairs(target_option, sequence_option, mismatch):
+    """-> (targets, sequences), one entry per (target, sequence) pair; `mismatch` is the model's own assertion text."""
+    targets, sequences = _field_list(target_option), _field_list(sequence_option)
+    assert len(targets) == len(sequences), mismatch
+    return targets, sequences
+
+
 class DIN(_ZooModel):
     def __init__(self, feature_map, model_id="DIN", gpu=-1, dnn_hidden_units=[512, 128, 64],
                  dnn_activations="ReLU", attention_hidden_units=[64],
@@ -154,13 +174,8 @@ class DIN(_ZooModel):
                  din_sequence_field=[("click_history", "cate_history")], din_use_softmax=False,
                  embedding_regularizer=None, net_regularizer=None, **kwargs):
         self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
-        targets = din_target_field if isinstance(din_target_field, list) else [din_target_field]
-        sequences = din_sequence_field if isinstance(din_sequence_field, list) \
-            else [din_sequence_field]
-        assert len(targets) == len(sequences), "len(din_target_field) != len(din_sequence_field)"
-        # the public attributes keep the reference's shape: a str, or a tuple for grouped fields
-        self.din_target_field = [tuple(f) if isinstance(f, list) else f for f in targets]
-        self.din_sequence_field = [tuple(f) if isinstance(f, list) else f for f in sequences]
+        self.din_target_field, self.din_sequence_field = _field_pairs(
+            din_target_field, din_sequence_field, "len(din_target_field) != len(din_sequence_field)")
         self.embedding_dim = embedding_dim
         self.embedding_layer = FeatureEmbeddingDict(feature_map, embedding_dim)
         self.attention_layers = nn.ModuleList(
@@ -217,9 +232,7 @@ class DIN(_ZooModel):
             seq_names = _fields(sequence)
             # padding_idx 0 marks the empty positions (DIN.py:125: `X[field].long() != 0`); the packed
             # int32 id columns themselves serve as the mask (kept when != 0): no cast / compare launches
-            valid = self.embedding_layer.packed_ids(X, seq_names[0])
-            if valid is None:
-                valid = X[seq_names[0]].long() != 0
+            valid = self._first_seq_ids(X, sequence, lambda ids: ids.long() != 0)
             pooled = attend(self.get_embedding(target, emb), self.get_embedding(sequence, emb),
                             valid)
             # the attended vector replaces each sequence field's [B,L,D] entry by its [B,D] share
@@ -757,11 +770,8 @@ class BST(_ZooModel):
                  seq_pooling_type="mean", use_position_emb=True, use_causal_mask=False, embedding_regularizer=None,
                  net_regularizer=None, **kwargs):
         self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
-        targets = bst_target_field if isinstance(bst_target_field, list) else [bst_target_field]
-        sequences = bst_sequence_field if isinstance(bst_sequence_field, list) else [bst_sequence_field]
-        assert len(targets) == len(sequences), "len(self.bst_target_field) != len(self.bst_sequence_field)"
-        self.bst_target_field = [tuple(f) if isinstance(f, list) else f for f in targets]
-        self.bst_sequence_field = [tuple(f) if isinstance(f, list) else f for f in sequences]
+        self.bst_target_field, self.bst_sequence_field = _field_pairs(
+            bst_target_field, bst_sequence_field, "len(self.bst_target_field) != len(self.bst_sequence_field)")
         if seq_pooling_type not in ("mean", "sum", "target", "concat"):
             raise ValueError("seq_pooling_type={} not supported.".format(seq_pooling_type))
         self.use_causal_mask = use_causal_mask
@@ -802,9 +812,7 @@ class BST(_ZooModel):
             seq_names = _fields(sequence)
             # padding_idx 0 marks the empty positions (BST.py:193 on the FIRST sequence field); the packed int32 id
             # columns themselves are the mask: no cast / compare / [B * H, L1, L1] tensor
-            ids = self.embedding_layer.packed_ids(X, seq_names[0])
-            if ids is None:
-                ids = (X[seq_names[0]].long() != 0).to(torch.int32).contiguous()
+            ids = self._first_seq_ids(X, sequence, lambda ids: (ids.long() != 0).to(torch.int32).contiguous())
             pooled.append(encoder.forward_parts([emb[f] for f in seq_names], [emb[f] for f in _fields(target)],
                                                 ids=ids, causal=self.use_causal_mask, pool=self.seq_pooling_type))
             dropped.update(seq_names)
@@ -840,13 +848,9 @@ class DIEN(_ZooModel):
                  aux_hidden_units=[100, 50], aux_activation="ReLU", aux_loss_alpha=0, embedding_regularizer=None,
                  net_regularizer=None, **kwargs):
         self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
-        as_list = lambda f: f if isinstance(f, list) else [f]                  # noqa: E731
-        as_field = lambda f: tuple(f) if isinstance(f, list) else f            # noqa: E731
-        self.dien_target_field = [as_field(f) for f in as_list(dien_target_field)]
-        self.dien_sequence_field = [as_field(f) for f in as_list(dien_sequence_field)]
-        assert len(self.dien_target_field) == len(self.dien_sequence_field), \
-            "dien_sequence_field or dien_target_field not supported."
-        self.dien_neg_seq_field = [as_field(f) for f in as_list(dien_neg_seq_field)]
+        self.dien_target_field, self.dien_sequence_field = _field_pairs(
+            dien_target_field, dien_sequence_field, "dien_sequence_field or dien_target_field not supported.")
+        self.dien_neg_seq_field = _field_list(dien_neg_seq_field)
         if aux_loss_alpha > 0:
             raise NotImplementedError("DIEN: aux_loss_alpha > 0 is not native; the reference's own auxiliary loss "
                                       "raises at DIEN.py:228 (the .view of a non-contiguous cat; the mask and loss "
@@ -939,9 +943,7 @@ class DIEN(_ZooModel):
             seqs = [emb[f] for f in seq_names]
             # padding_idx 0 (DIEN.py:177 on the FIRST sequence field): the packed int32 id columns are the lengths
             # and the mask; they never leave the device
-            ids = self.embedding_layer.packed_ids(X, seq_names[0])
-            if ids is None:
-                ids = X[seq_names[0]].to(torch.int32).contiguous()
+            ids = self._first_seq_ids(X, sequence_field, lambda ids: ids.to(torch.int32).contiguous())
             interest_emb, final = self.extraction_modules[idx].forward_parts(seqs, ids)
             if self.gru_type == "GRU":
                 _, final = self.evolving_modules[idx].forward_parts([interest_emb], ids)

@@ -966,6 +966,27 @@ int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_
                   float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A sample's column parts (new functionality: the layout BST and DIEN below share).  A behaviour history of width
+ * n_parts * D per position is n_parts column parts of D floats; so is the target item.  Each part is a view (of the
+ * gather record, say) with strides of its own, read in place:
+ *     history, part i, sample b, position t :  seq[i] + b * seq_ld[i] + t * seq_row_ld[i]      (D floats)
+ *     target,  part i, sample b             :  tgt[i] + b * tgt_ld[i]                          (D floats)
+ * Column c of the concatenated row is column c - i * D of part i = c / D.  A user without a sequence side (the
+ * scores' target) or without a target side (the GRU input) leaves those pointers NULL.  A gradient is written
+ * through a second description of the same n_parts and D: a NULL pointer there means "not wanted", nothing of
+ * that part is written and its strides are not read.  Room for 3 parts; each entry point states its own limit.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fx_seq_parts {
+    const float* seq[3];
+    int64_t seq_ld[3];
+    int64_t seq_row_ld[3];
+    const float* tgt[3];
+    int64_t tgt_ld[3];
+    int32_t n_parts;
+    int32_t D;
+} fx_seq_parts;
+
+/* ------------------------------------------------------------------------------------------
  * BST (csrc/fx_bst.hip): one transformer block of the Behavior Sequence Transformer over the L1 = L + 1 positions
  * of a sample (the history's L positions, then the target), fused (model_zoo/BST/src/BST.py:317-366; the masks of
  * BST.py:183-207, the pooling of BST.py:209-229; torch.nn.MultiheadAttention's packed in_proj):
@@ -976,9 +997,9 @@ int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_
  *     out  = w2 LeakyReLU_0.01(w1 s + b1) + b2 (+ s when residual);   out = LN2(out) when layer_norm
  *     masked(i, j) = (pad[j] and i != j) or (causal and j > i);  pad[j] = (ids[b, j] == 0) for j < L, pad[L] = 0
  *   The diagonal is always open: an all-padding history is legal and gives finite numbers.
- *   fx_bst_input: part i of position f < L is seq[i] + b * seq_ld[i] + f * seq_row_ld[i], of the target
- *   tgt[i] + b * tgt_ld[i], D floats each (views into the gather record are read in place); pos (nullable) is
- *   position_emb [L1, D].  A later block takes its [B, L1, dm] input as one part of D = dm.
+ *   `in`: the sample's 1 to 3 parts (fx_seq_parts above: seq the L history positions, tgt the target); pos
+ *   (nullable, a field of fx_bst_weights: a trained parameter like the others) is position_emb [L1, D].  A later
+ *   block takes its [B, L1, dm] input as one part of D = dm.
  *   pool: 0 none: Y [B, L1, dm] (also BST's "concat");  1 mean over the unpadded positions (sum / (count + 1e-12));
  *   2 sum over them;  3 target (row L): Y [B, dm] (BST.py:219-227).
  *   fx_bst_block_fwd : one launch.  Neither Q / K / V nor scores nor any intermediate reaches memory.
@@ -993,28 +1014,18 @@ int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_
  *   fx_bst_limits : limits[4] = {most L1, most dm, forward grid, backward grid} (housekeeping).
  *   fx_bst_workspace_floats : floats of fx_bst_block_bwd's workspace, pos_D = D with pos, else 0 (housekeeping).
  * ------------------------------------------------------------------------------------------ */
-typedef struct fx_bst_input {
-    const float* seq[3];
-    const float* tgt[3];
-    int64_t seq_ld[3];
-    int64_t seq_row_ld[3];
-    int64_t tgt_ld[3];
-    const float* pos;
-    int32_t n_parts;
-    int32_t D;
-} fx_bst_input;
 typedef struct fx_bst_weights {
-    const float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+    const float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *ln1_w, *ln1_b, *ln2_w, *ln2_b, *pos;
 } fx_bst_weights;
 void fx_bst_limits(int32_t* limits);
 int64_t fx_bst_grad_floats(int32_t L1, int32_t dm, int32_t pos_D);
 int64_t fx_bst_workspace_floats(int64_t B, int32_t L1, int32_t dm, int32_t pos_D);
-int fx_bst_block_fwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
+int fx_bst_block_fwd(const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
                      int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual, int32_t causal,
                      int32_t pool, float* Y, fx_stream_t stream);
-int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
+int fx_bst_block_bwd(const fx_seq_parts* in, const int32_t* ids, int64_t ids_ld, int64_t B, int32_t L1, int32_t dm,
                      int32_t H, const fx_bst_weights* w, int32_t layer_norm, int32_t residual, int32_t causal,
-                     int32_t pool, const float* dY, const fx_bst_input* din, int32_t dx_accumulate, float* grads,
+                     int32_t pool, const float* dY, const fx_seq_parts* din, int32_t dx_accumulate, float* grads,
                      float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1030,8 +1041,7 @@ int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld,
  *         mode 1 AGRU  chunks (u, r, n): g = scores[b, t]                      (the u chunk is unused)
  *         mode 2 AUGRU chunks (u, r, n): g = sigmoid(gx_u + gh_u) * scores[b, t]
  *     states [B, L, H] = h' per position, 0 past len;  final_state [B, H] = h after position len-1, 0 for len = 0.
- *   fx_gru_input: X [B, L, H] as n_parts (1 or 2) column parts of D = H / n_parts floats: part i of position t is
- *   seq[i] + b * seq_ld[i] + t * seq_row_ld[i] (views into the gather record are read in place).
+ *   `x`: X [B, L, H] as the sequence side of 1 or 2 parts of D = H / n_parts floats (fx_seq_parts above).
  *   fx_gru_seq_fwd : one launch; a workgroup keeps a tile of fx_gru_tile_rows(H) samples' hidden states and both
  *                    weight matrices in LDS for the whole sequence.
  *   fx_gru_seq_bwd : back-propagation through time in one launch from d_states [B, L, H] and / or d_final [B, H]
@@ -1043,7 +1053,7 @@ int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld,
  *   fx_seq_score_fwd : scores[b, t] = (interest[b, t] W) . target[b]  (W [H, H]; NULL: the plain dot), times
  *                    mask[b, t] = (ids[b, t] != 0); with `softmax` then + -1e9 (1 - mask) and a soft-max over all L
  *                    positions.  A row without any open position gives zeros (the reference never sees one).
- *                    interest [B, L, H] contiguous, 16-byte aligned; fx_seq_target: the target's column parts.
+ *                    interest [B, L, H] contiguous, 16-byte aligned; `tgt`: the target side of 1 or 2 parts.
  *   fx_seq_score_bwd : from d_scores and the forward's `scores`: d_interest [B, L, H] (nullable), the target's
  *                    gradient through `d_tgt` (a NULL part: not wanted), dW [H, H] (with W) by per-workgroup rows
  *                    in `workspace` and a fixed-order sum.
@@ -1053,36 +1063,23 @@ int fx_bst_block_bwd(const fx_bst_input* in, const int32_t* ids, int64_t ids_ld,
  *   fx_gru_tile_rows : samples per workgroup tile (housekeeping).
  *   fx_gru_workspace_floats, fx_seq_score_workspace_floats : floats of the backward workspaces (housekeeping).
  * ------------------------------------------------------------------------------------------ */
-typedef struct fx_gru_input {
-    const float* seq[2];
-    int64_t seq_ld[2];
-    int64_t seq_row_ld[2];
-    int32_t n_parts;
-    int32_t D;
-} fx_gru_input;
-typedef struct fx_seq_target {
-    const float* tgt[2];
-    int64_t tgt_ld[2];
-    int32_t n_parts;
-    int32_t D;
-} fx_seq_target;
 void fx_gru_limits(int32_t* limits);
 int32_t fx_gru_tile_rows(int32_t H);
 int64_t fx_gru_grad_floats(int32_t H);
 int64_t fx_gru_workspace_floats(int64_t B, int32_t H);
-int fx_gru_seq_fwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
+int fx_gru_seq_fwd(const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
                    int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, float* states, float* final_state, fx_stream_t stream);
-int fx_gru_seq_bwd(const fx_gru_input* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
+int fx_gru_seq_bwd(const fx_seq_parts* x, const int32_t* ids, int64_t ids_ld, const float* scores, int64_t B,
                    int32_t L, int32_t H, int32_t mode, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, const float* states, const float* d_states, const float* d_final,
-                   const fx_gru_input* dx, float* d_scores, float* grads, float* workspace, fx_stream_t stream);
+                   const fx_seq_parts* dx, float* d_scores, float* grads, float* workspace, fx_stream_t stream);
 int64_t fx_seq_score_workspace_floats(int64_t B, int32_t H);
-int fx_seq_score_fwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
+int fx_seq_score_fwd(const float* interest, const fx_seq_parts* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
                      int32_t L, int32_t H, const float* W, int32_t softmax, float* scores, fx_stream_t stream);
-int fx_seq_score_bwd(const float* interest, const fx_seq_target* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
+int fx_seq_score_bwd(const float* interest, const fx_seq_parts* tgt, const int32_t* ids, int64_t ids_ld, int64_t B,
                      int32_t L, int32_t H, const float* W, int32_t softmax, const float* scores,
-                     const float* d_scores, float* d_interest, const fx_seq_target* d_tgt, float* dW,
+                     const float* d_scores, float* d_interest, const fx_seq_parts* d_tgt, float* dW,
                      float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

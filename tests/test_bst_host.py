@@ -235,7 +235,7 @@ def test_entry_points_are_declared_and_validate_before_the_device():
                  "fx_bst_limits"):
         assert name in _lib.SIGNATURES
     lib = _lib.load()
-    inp, w = _lib.BstInput(), _lib.BstWeights()
+    inp, w = _lib.SeqParts(), _lib.BstWeights()
     inp.n_parts, inp.D = 2, 16
 
     def fwd(L1, dm, H):

@@ -266,7 +266,7 @@ def test_entry_points_are_declared_and_validate_before_the_device():
                  "fx_seq_score_workspace_floats"):
         assert name in _lib.SIGNATURES
     lib = _lib.load()
-    x, tgt = _lib.GruInput(), _lib.SeqTarget()
+    x, tgt = _lib.SeqParts(), _lib.SeqParts()
     x.n_parts, x.D = 2, 16
     tgt.n_parts, tgt.D = 2, 16
 
@@ -292,6 +292,79 @@ def test_entry_points_are_declared_and_validate_before_the_device():
     lim = (ctypes.c_int32 * 4)()
     lib.fx_gru_limits(lim)
     assert list(lim)[:2] == [64, 256]
+
+
+def _packed(d):
+    """The pointer and stride fields of a packed struct fx_seq_parts as plain tuples (a null pointer reads as None)."""
+    return {"seq": tuple(d.seq), "seq_ld": tuple(d.seq_ld), "seq_row_ld": tuple(d.seq_row_ld), "tgt": tuple(d.tgt),
+            "tgt_ld": tuple(d.tgt_ld), "n_parts": d.n_parts, "D": d.D}
+
+
+def test_the_one_packer_gives_the_fields_of_the_three_it_replaced():
+    """ops._seq_parts on the layouts the three earlier packers met: contiguous tensors, column slices of a wider
+    record, and B = 1 / L = 1, where the stride of the axis of extent 1 is replaced by the dense one.  The expected
+    fields are written out from data_ptr() and stride()."""
+    from fuxictr_amd import ops
+    B, L, D = 5, 4, 3
+    none3, zero3 = (None,) * 3, (0,) * 3
+    # contiguous history and target, two parts (BST's input: both sides)
+    s = [torch.zeros(B, L, D), torch.zeros(B, L, D)]
+    t = [torch.zeros(B, D), torch.zeros(B, D)]
+    assert _packed(ops._seq_parts(s, t, "t")) == {
+        "seq": (s[0].data_ptr(), s[1].data_ptr(), None), "seq_ld": (L * D, L * D, 0), "seq_row_ld": (D, D, 0),
+        "tgt": (t[0].data_ptr(), t[1].data_ptr(), None), "tgt_ld": (D, D, 0), "n_parts": 2, "D": D}
+    # views of a wider record [B, L + 3, D + 3] at slot and column offsets of their own
+    rec = torch.zeros(B, L + 3, D + 3)
+    W, R = D + 3, (L + 3) * (D + 3)
+    s = [rec[:, 1:1 + L, :D], rec[:, 2:2 + L, 2:2 + D]]
+    t = [rec[:, 0, :D], rec[:, L + 2, 3:3 + D]]
+    base = rec.data_ptr()
+    assert s[1].stride() == (R, W, 1) and t[1].stride() == (R, 1)
+    want_seq = (base + 4 * W, base + 4 * (2 * W + 2), None)
+    want_tgt = (base, base + 4 * ((L + 2) * W + 3), None)
+    assert _packed(ops._seq_parts(s, t, "t")) == {
+        "seq": want_seq, "seq_ld": (R, R, 0), "seq_row_ld": (W, W, 0), "tgt": want_tgt, "tgt_ld": (R, R, 0),
+        "n_parts": 2, "D": D}
+    # the GRU input has no target side, the scores' target no sequence side; three parts fill the struct
+    assert _packed(ops._seq_parts(s, None, "t")) == {
+        "seq": want_seq, "seq_ld": (R, R, 0), "seq_row_ld": (W, W, 0), "tgt": none3, "tgt_ld": zero3, "n_parts": 2,
+        "D": D}
+    assert _packed(ops._seq_parts(None, t, "t")) == {
+        "seq": none3, "seq_ld": zero3, "seq_row_ld": zero3, "tgt": want_tgt, "tgt_ld": (R, R, 0), "n_parts": 2, "D": D}
+    t3 = [rec[:, i, :D] for i in range(3)]
+    assert _packed(ops._seq_parts(None, t3, "t"))["tgt"] == (base, base + 4 * W, base + 8 * W)
+    # a gradient description: a part nobody wants stays null, D comes from the caller
+    g = torch.zeros(B, L, D)
+    assert _packed(ops._seq_parts([None, g], None, "t", D)) == {
+        "seq": (None, g.data_ptr(), None), "seq_ld": (0, L * D, 0), "seq_row_ld": (0, D, 0), "tgt": none3,
+        "tgt_ld": zero3, "n_parts": 2, "D": D}
+    assert _packed(ops._seq_parts([None], [None], "t", D)) == {
+        "seq": none3, "seq_ld": zero3, "seq_row_ld": zero3, "tgt": none3, "tgt_ld": zero3, "n_parts": 1, "D": D}
+    # B = 1: the sample stride of a view is whatever the slicing left; the packer hands on the dense one
+    one = rec[2:3]
+    s1, t1 = one[:, 1:1 + L, :D], one[:, 0, 1:1 + D]
+    assert s1.stride(0) == R and t1.stride(0) == R
+    assert _packed(ops._seq_parts([s1], [t1], "t")) == {
+        "seq": (s1.data_ptr(), None, None), "seq_ld": (L * W, 0, 0), "seq_row_ld": (W, 0, 0),
+        "tgt": (t1.data_ptr(), None, None), "tgt_ld": (D, 0, 0), "n_parts": 1, "D": D}
+    # L = 1: the position stride likewise; an empty history (BST with L1 = 1) leaves the sequence side null
+    sl = rec[:, 3:4, 1:1 + D]
+    assert sl.stride(1) == W
+    assert _packed(ops._seq_parts([sl], None, "t")) == {
+        "seq": (sl.data_ptr(), None, None), "seq_ld": (R, 0, 0), "seq_row_ld": (D, 0, 0), "tgt": none3,
+        "tgt_ld": zero3, "n_parts": 1, "D": D}
+    s11 = rec[1:2, 3:4, :D]
+    assert _packed(ops._seq_parts([s11], None, "t"))["seq_ld"] == (D, 0, 0)
+    assert _packed(ops._seq_parts([rec[:, :0, :D]], [rec[:, 0, :D]], "t"))["seq"] == none3
+    # the ids of the first sequence field: own row stride, the dense one at B = 1, null only where the caller allows
+    ids = torch.zeros(B, L + 2, dtype=torch.int32)[:, :L]
+    p, ld = ops._seq_ids(ids, B, L)
+    assert (p.value, ld) == (ids.data_ptr(), L + 2)
+    assert ops._seq_ids(ids[:1], 1, L)[1] == L
+    p, ld = ops._seq_ids(None, B, L, nullable=True)
+    assert (p.value, ld) == (None, 0)
+    with pytest.raises((AssertionError, AttributeError)):
+        ops._seq_ids(None, B, L)
 
 
 def test_the_batch_dict_order_does_not_change_the_logits(tmp_path, monkeypatch):

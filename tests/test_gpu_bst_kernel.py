@@ -256,7 +256,7 @@ def test_limits_are_rejected_before_any_launch():
     with pytest.raises(NotImplementedError, match="L1 <= 64"):
         run_hip(case, 2, (True, True, False, "mean"), torch.zeros(3, 16, dtype=torch.float64), dev)
     lib = _lib.load()
-    inp, wt = _lib.BstInput(), _lib.BstWeights()
+    inp, wt = _lib.SeqParts(), _lib.BstWeights()
     inp.n_parts, inp.D = 1, 8
     st = lib.fx_bst_block_fwd(ctypes.byref(inp), None, 0, 3, 65, 8, 2, ctypes.byref(wt), 1, 1, 0, 1, None, None)
     assert st == 1 and b"L1 <= 64" in lib.fx_last_error()

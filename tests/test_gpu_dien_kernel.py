@@ -233,6 +233,109 @@ def test_scores_against_fp64(shape, bilinear, softmax):
     assert float(hip["scores"][closed].abs().max() if closed.any() else 0) == 0
 
 
+SENTINEL = 3.0
+
+
+def _only_views_written(records, views):
+    """Every element of the sentinel-filled `records` outside the listed (record index, slices) is still the sentinel."""
+    for k, rec in enumerate(records):
+        touched = torch.zeros_like(rec, dtype=torch.bool)
+        for r, where in views:
+            if r == k:
+                touched[where] = True
+        assert bool((rec[~touched] == SENTINEL).all()), "record %d written outside its views" % k
+
+
+def test_gru_parts_in_a_wider_record_and_null_destinations():
+    """The two parts are views into NaN-filled records [B, L + 3, D + 3] at slot and column offsets of their own
+    (one record per part: two [L, D] blocks at different offsets do not fit one [L + 3, D + 3] slab side by side),
+    read in place; the gradients go through views of sentinel-filled records with the same strides and the bytes
+    around them stay untouched; a null destination is skipped and changes nothing else."""
+    B, L, D, mode = 9, 6, 4, "AUGRU"
+    H = 2 * D
+    case = gru_case(B, L, H, 2, mode, seed=77)
+    parts, ids, scores, w, gs, gf = case
+    r64, r32 = gru_reference(case, mode, torch.float64), gru_reference(case, mode, torch.float32)
+    where = [(slice(None), slice(1, 1 + L), slice(0, D)), (slice(None), slice(3, 3 + L), slice(2, 2 + D))]
+    recs = [torch.full((B, L + 3, D + 3), float("nan"), dtype=torch.float32, device=DEV) for _ in range(2)]
+    views = [rec[s] for rec, s in zip(recs, where)]
+    for view, src in zip(views, parts):
+        view.copy_(src.float())
+    assert all(v.stride() == ((L + 3) * (D + 3), D + 3, 1) for v in views)
+
+    def d(t):
+        return t.float().to(DEV).contiguous()
+    hw, ha, hid = [d(t) for t in w], d(scores), ids.to(DEV)
+    states = torch.full((B, L, H), float("nan"), dtype=torch.float32, device=DEV)
+    final = torch.full((B, H), float("nan"), dtype=torch.float32, device=DEV)
+    ops.gru_seq_fwd(views, hid, ha, mode, *hw, states, final)
+    torch.cuda.synchronize()
+    bound_check("wide", "states", states.cpu(), r64["states"], r32["states"])
+    bound_check("wide", "final", final.cpu(), r64["final"], r32["final"])
+
+    def backward(wanted):
+        drecs = [torch.full_like(rec, SENTINEL) for rec in recs]
+        dparts = [drec[s] if keep else None for drec, s, keep in zip(drecs, where, wanted)]
+        dsc = torch.full((B, L), float("nan"), dtype=torch.float32, device=DEV)
+        grads = torch.empty(ops.gru_grad_floats(H), dtype=torch.float32, device=DEV)
+        ws = torch.empty(ops.gru_workspace_floats(B, H), dtype=torch.float32, device=DEV)
+        ops.gru_seq_bwd(views, hid, ha, mode, *hw, states, d(gs), d(gf), dparts, dsc, grads, ws)
+        torch.cuda.synchronize()
+        _only_views_written(drecs, [(k, where[k]) for k in range(2) if wanted[k]])
+        return dparts, dsc, grads
+    dparts, dsc, grads = backward((True, True))
+    for i in range(2):
+        bound_check("wide", "dx%d" % i, dparts[i].cpu(), r64["dx%d" % i], r32["dx%d" % i])
+    bound_check("wide", "dscores", dsc.cpu(), r64["dscores"], r32["dscores"])
+    bound_check("wide", "dw_ih", grads[:3 * H * H].view(3 * H, H).cpu(), r64["dw_ih"], r32["dw_ih"])
+    again, dsc2, grads2 = backward((True, False))
+    assert again[1] is None and torch.equal(again[0], dparts[0])
+    assert torch.equal(dsc2, dsc) and torch.equal(grads2, grads)
+
+
+def test_score_targets_in_a_wider_record_and_null_destinations():
+    """The same for the scores' target: two parts as views rec[:, 1, :D] and rec[:, 2, 1:D + 1] of one NaN-filled
+    record, their gradients through the same views of a sentinel-filled one, then with part 0's destination null."""
+    B, L, D = 9, 6, 4
+    H = 2 * D
+    case = score_case(B, L, H, 2, True, seed=78)
+    interest, tgts, ids, W, gy = case
+    r64, r32 = score_reference(case, True, torch.float64), score_reference(case, True, torch.float32)
+    where = [(slice(None), 1, slice(0, D)), (slice(None), 2, slice(1, D + 1))]
+    rec = torch.full((B, 4, D + 3), float("nan"), dtype=torch.float32, device=DEV)
+    views = [rec[s] for s in where]
+    for view, src in zip(views, tgts):
+        view.copy_(src.float())
+    assert all(v.stride() == (4 * (D + 3), 1) for v in views)
+
+    def d(t):
+        return t.float().to(DEV).contiguous()
+    hi, hw, hid = d(interest), d(W), ids.to(DEV)
+    scores = torch.full((B, L), float("nan"), dtype=torch.float32, device=DEV)
+    ops.seq_score_fwd(hi, views, hid, hw, True, scores)
+    torch.cuda.synchronize()
+    bound_check("wide", "scores", scores.cpu(), r64["scores"], r32["scores"])
+
+    def backward(wanted):
+        drec = torch.full_like(rec, SENTINEL)
+        dtgts = [drec[s] if keep else None for s, keep in zip(where, wanted)]
+        di = torch.full_like(hi, float("nan"))
+        dW = torch.empty(H, H, dtype=torch.float32, device=DEV)
+        ws = torch.empty(ops.seq_score_workspace_floats(B, H), dtype=torch.float32, device=DEV)
+        ops.seq_score_bwd(hi, views, hid, hw, True, scores, d(gy), di, dtgts, dW, ws)
+        torch.cuda.synchronize()
+        _only_views_written([drec], [(0, where[k]) for k in range(2) if wanted[k]])
+        return dtgts, di, dW
+    dtgts, di, dW = backward((True, True))
+    for i in range(2):
+        bound_check("wide", "dtgt%d" % i, dtgts[i].cpu(), r64["dtgt%d" % i], r32["dtgt%d" % i])
+    bound_check("wide", "dinterest", di.cpu(), r64["dinterest"], r32["dinterest"])
+    bound_check("wide", "dW", dW.cpu(), r64["dW"], r32["dW"])
+    again, di2, dW2 = backward((False, True))
+    assert again[0] is None and torch.equal(again[1], dtgts[1])
+    assert torch.equal(di2, di) and torch.equal(dW2, dW)
+
+
 def test_two_runs_give_the_same_bits():
     case = gru_case(33, 51, 32, 2, "AUGRU", seed=5)
     a, b = gru_hip(case, "AUGRU"), gru_hip(case, "AUGRU")
