@@ -486,6 +486,8 @@ extern "C" int fx_fm_fwd(const float* emb, int64_t emb_ld, int32_t F, int32_t D,
     if (B <= 0) return FX_OK;
     FX_CHECK_ARG(emb && out, "fx_fm_fwd: null pointer");
     const FxRowGeom g = fx_row_geom(D);
+    // the sample's lanes are reduced with wave shuffles: a row of more than 64 lanes would span waves
+    FX_CHECK_ARG(g.lanes <= 64, "fx_fm_fwd: D=%d needs %d lanes per row (max 64)", D, g.lanes);
     FX_CHECK_ARG(emb_ld % g.vec == 0, "fx_fm_fwd: emb_ld not a multiple of %d", g.vec);
     FmArgs a{emb, emb_ld, addend, nullptr, out, nullptr, 0, B, F, D, 0, 0, 0};
     return fx_fm_launch(false, a, stream);

@@ -1584,7 +1584,17 @@ class LogisticRegression(nn.Module):
 
 
 class _FMFn(torch.autograd.Function):
-    """0.5 * sum_d((sum_f e)^2 - sum_f e^2) (+ addend), inner_product.py:55-62."""
+    """0.5 * sum_d((sum_f e)^2 - sum_f e^2) (+ addend), inner_product.py:55-62.  fx_fm_fwd reduces a sample with wave
+    shuffles and refuses rows of more than 64 lanes (odd D >= 65, D = 2 mod 4 >= 130): those widths take the same
+    expression in torch, differentiated by autograd."""
+
+    @classmethod
+    def apply(cls, emb, addend):
+        if _lib.row_lanes(emb.shape[2]) > 64:
+            s = emb.sum(dim=1)
+            out = 0.5 * ((s * s).sum(dim=1, keepdim=True) - (emb * emb).sum(dim=(1, 2)).view(-1, 1))
+            return out if addend is None else out + addend.view(-1, 1)
+        return super(_FMFn, cls).apply(emb, addend)
 
     @staticmethod
     def forward(ctx, emb, addend):

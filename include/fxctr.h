@@ -369,7 +369,8 @@ int fx_mt_sgd(float* const* params_host, const float* const* grads_host,
  * FM second-order term + LR first-order term (DeepFM / FM / xDeepFM).
  *  fx_fm_fwd : out[b] = 0.5 * sum_d ((sum_f e[b,f,d])^2 - sum_f e[b,f,d]^2) (+ addend[b])
  *              (fuxictr/pytorch/layers/interactions/inner_product.py:55-62, "product_sum";
- *              the addend fuses factorization_machine.py:58).
+ *              the addend fuses factorization_machine.py:58).  D <= 256 whose row takes at most
+ *              64 lanes (not odd D >= 65, not D = 2 mod 4 >= 130): a sample is reduced inside a wave.
  *  fx_fm_bwd : demb[b,f,d] (+)= g[b] * (sum_f e[b,f,d] - e[b,f,d])   (accumulate != 0: +=)
  *  fx_lr_fwd : out[b] = sum_c table1[col_row_base[c] + ids[b,c]] + sum_j dense[b,j]*num_w1[j] + bias
  *              (logistic_regression.py:55-58: a D=1 FeatureEmbedding summed over fields).
