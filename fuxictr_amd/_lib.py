@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfxctr.so")
 
 FX_OK = 0
+FX_ABI_VERSION = 2     # include/fxctr.h: moves with any prototype or exported struct layout change
 FX_F32, FX_F64, FX_I32, FX_I64, FX_BF16 = 0, 1, 2, 3, 4
 FX_FLAG_BAD_ID = 1
 FX_FLAG_A2A_OVERFLOW = 2
@@ -111,9 +112,6 @@ SIGNATURES = {
     "fx_adam_series_words": (i64, [i32]),
     "fx_adam_series_build": (i32, [vp, i32, vp]),
     "fx_clip_coef": (i32, [C.POINTER(vp), C.POINTER(i64), i32, vp, vp]),
-    "fx_sparse_adam": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp]),
-    "fx_adam_catchup": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, vp, vp]),
-    "fx_sparse_sgd": (i32, [vp, vp, i32, vp, vp, i64, vp, vp, vp]),
     "fx_reg_stats": (i32, [vp, i64, vp, vp, vp]),
     "fx_reg_cross": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, vp]),
     "fx_reg_dense_update": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp]),
@@ -273,8 +271,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     ver = lib.fx_abi_version()
-    if ver != 1:
-        raise FxError("libfxctr.so ABI version %d, expected 1" % ver)
+    if ver != FX_ABI_VERSION:
+        raise FxError("libfxctr.so ABI version %d, expected %d" % (ver, FX_ABI_VERSION))
     _lib = lib
     return lib
 

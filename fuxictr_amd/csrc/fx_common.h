@@ -79,12 +79,12 @@ int fx_dedup_columns_launch(const int32_t* ids, int64_t ids_ld, int64_t B, int32
 
 // ---- fx_rowopt.hip: the exact-mode catch-up of the unique rows of a de-dup result in 1..FX_MAX_TABLES table
 // groups, for fx_dedup_catchup (fx_fused.hip).  _check reports the argument errors of `tables_host` without
-// launching anything; quad_ok = false keeps the plain replays for the D = 16 (+ D = 1) shapes too.
+// launching anything.
 #define FX_MAX_TABLES 4
 int fx_catchup_rows_check(const fx_row_state* tables_host, int32_t n_tables, const char* who);
 int fx_catchup_rows_launch(const fx_row_state* tables_host, int32_t n_tables, const uint32_t* uniq_row,
                            const int32_t* n_unique, int64_t n_max, int32_t upto_offset,
-                           const fx_scalars* scal, bool quad_ok, const char* who, hipStream_t s);
+                           const fx_scalars* scal, const char* who, hipStream_t s);
 
 // ---- fx_dedup_lds.hip: the bucketed in-LDS de-dup of the generic (n_shards = 1) path: rows hashed into 256
 // buckets by their low 8 bits (one stable partition pass), one workgroup sorts a bucket in LDS.  4 launches.

@@ -290,7 +290,7 @@ extern "C" int fx_dedup_catchup(const int32_t* ids, int64_t ids_ld, int64_t B, i
                                            col_scan, sorted_key, sorted_pos, uniq_row, seg_start, n_unique,
                                            sorted_uid, begin_scal, s);
     if (st != FX_OK || n_tables == 0) return st;
-    return fx_catchup_rows_launch(tables_host, n_tables, uniq_row, n_unique, n, upto_offset, scal, true,
+    return fx_catchup_rows_launch(tables_host, n_tables, uniq_row, n_unique, n, upto_offset, scal,
                                   "fx_dedup_catchup", s);
 }
 

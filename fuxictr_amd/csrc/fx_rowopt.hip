@@ -9,8 +9,7 @@
 //   fetch      k_owner_fetch_rows      owner side of the row-sharded forward: catch-up + gather into the send block
 //   regularizer k_reg_stats / k_reg_cross / k_reg_dense   the dense embedding-regularizer term
 //
-// Tables are fp32 or bf16, packed or fields of a row record (fx_row_state).  fx_sparse_adam, fx_adam_catchup and
-// fx_sparse_sgd — one packed fp32 table, the entry points of round 1 — wrap the same launches.
+// Tables are fp32 or bf16, packed or fields of a row record (fx_row_state).
 //
 // What this replaces in the reference (paths relative to the reference checkout):
 //   torch.optim.Adam / SGD step over every table row          rank_model.py:322, torch_utils.py:76
@@ -355,16 +354,6 @@ int fx_catchup_rows_check(const fx_row_state* tables_host, int32_t n_tables, con
     return fx_fill_tables(tables_host, n_tables, t, &gl, who, true);
 }
 
-// one packed fp32 table, as the entry points of round 1 name it
-static fx_row_state fx_packed_f32(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                                  const float* G) {
-    fx_row_state h;
-    memset(&h, 0, sizeof(h));
-    h.table = table; h.m = m; h.v = v; h.last_step = last_step; h.G = G; h.D = D;
-    h.table_dtype = FX_F32;
-    return h;
-}
-
 // which form of fx_catchup_quad a catch-up of these tables takes: 1 the D = 16 + D = 1 pair, 2 a D = 16 table
 // alone, 0 the plain replays
 static int fx_quad_mode(const FxTableDev* t, int n_tables, int gl) {
@@ -525,23 +514,6 @@ extern "C" int fx_sparse_sgd_multi(const fx_row_state* tables_host, int32_t n_ta
                                   stream, "fx_sparse_sgd_multi");
 }
 
-// the round-1 entry points: one packed fp32 table through the same launch
-extern "C" int fx_sparse_adam(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                              const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                              const float* G, const fx_scalars* scal, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_sparse_adam: D=%d not in [1,256]", D);
-    const fx_row_state h = fx_packed_f32(table, m, v, last_step, D, G);
-    return fx_sparse_update_multi(true, &h, 1, uniq_row, n_unique, n_max, scal, stream, "fx_sparse_adam");
-}
-
-extern "C" int fx_sparse_sgd(float* table, int32_t* last_step, int32_t D, const uint32_t* uniq_row,
-                             const int32_t* n_unique, int64_t n_max, const float* G,
-                             const fx_scalars* scal, fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_sparse_sgd: D=%d not in [1,256]", D);
-    const fx_row_state h = fx_packed_f32(table, nullptr, nullptr, last_step, D, G);
-    return fx_sparse_update_multi(false, &h, 1, uniq_row, n_unique, n_max, scal, stream, "fx_sparse_sgd");
-}
-
 // ---------------------------------------------------------------------------------------------
 // fx_adam_catchup_all: flush of the exact mode for fp32 or bf16 tables — every row of the table is
 // brought up to step + upto_offset (before evaluate / save / a learning-rate change).
@@ -628,11 +600,10 @@ __global__ __launch_bounds__(256) void k_catchup_rows(CatchRowsArgs a) {
         fx_catchup_tables(a.t, a.n_tables, (int64_t)a.uniq_row[u], sub, sc, upto, lg, ser);
 }
 
-// the one launch of k_catchup_rows (declared in fx_common.h: fx_dedup_catchup of fx_fused.hip ends with it).
-// quad_ok = false keeps the plain replays whatever the shape.
+// the one launch of k_catchup_rows (declared in fx_common.h: fx_dedup_catchup of fx_fused.hip ends with it)
 int fx_catchup_rows_launch(const fx_row_state* tables_host, int32_t n_tables, const uint32_t* uniq_row,
                            const int32_t* n_unique, int64_t n_max, int32_t upto_offset,
-                           const fx_scalars* scal, bool quad_ok, const char* who, hipStream_t s) {
+                           const fx_scalars* scal, const char* who, hipStream_t s) {
     CatchRowsArgs a;
     memset(&a, 0, sizeof(a));
     int gl = 0;
@@ -644,7 +615,7 @@ int fx_catchup_rows_launch(const fx_row_state* tables_host, int32_t n_tables, co
     a.n_tables = n_tables;
     a.group_log2 = gl;
     a.upto_offset = upto_offset;
-    a.quad = quad_ok ? fx_quad_mode(a.t, n_tables, gl) : 0;
+    a.quad = fx_quad_mode(a.t, n_tables, gl);
     int64_t blocks = fx_ceil_div(n_max, 256 >> gl);
     if (blocks > 256 * 64) blocks = 256 * 64;
     hipLaunchKernelGGL(k_catchup_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
@@ -660,26 +631,8 @@ extern "C" int fx_adam_catchup_rows(const fx_row_state* tables_host, int32_t n_t
                  "fx_adam_catchup_rows: n_tables=%d not in [1,%d]", n_tables, FX_MAX_TABLES);
     if (n_max <= 0) return FX_OK;
     FX_CHECK_ARG(tables_host && uniq_row && n_unique && scal, "fx_adam_catchup_rows: null pointer");
-    return fx_catchup_rows_launch(tables_host, n_tables, uniq_row, n_unique, n_max, upto_offset, scal, true,
+    return fx_catchup_rows_launch(tables_host, n_tables, uniq_row, n_unique, n_max, upto_offset, scal,
                                   "fx_adam_catchup_rows", fx_hip_stream(stream));
-}
-
-// round 1's entry point: the listed rows (uniq_row != NULL; always the plain replay — the tests hold the quad
-// replay against it) or every row of one packed fp32 table
-extern "C" int fx_adam_catchup(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                               const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                               int64_t total_rows, int32_t upto_offset, const fx_scalars* scal,
-                               fx_stream_t stream) {
-    FX_CHECK_ARG(D >= 1 && D <= 256, "fx_adam_catchup: D=%d not in [1,256]", D);
-    FX_CHECK_ARG(table && m && v && last_step && scal, "fx_adam_catchup: null pointer");
-    FX_CHECK_ARG(uniq_row == nullptr || n_unique != nullptr,
-                 "fx_adam_catchup: uniq_row given without n_unique");
-    const fx_row_state h = fx_packed_f32(table, m, v, last_step, D, nullptr);
-    hipStream_t s = fx_hip_stream(stream);
-    if (uniq_row == nullptr) return fx_catchup_all_launch(&h, total_rows, upto_offset, scal, "fx_adam_catchup", s);
-    if (n_max <= 0) return FX_OK;
-    return fx_catchup_rows_launch(&h, 1, uniq_row, n_unique, n_max, upto_offset, scal, false,
-                                  "fx_adam_catchup", s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -895,6 +848,17 @@ extern "C" int fx_reg_stats(const float* x, int64_t n, const fx_scalars* scal, f
     return FX_OK;
 }
 
+// the packed fp32 table that fx_reg_cross / fx_reg_dense_update are given, as the kernels take it
+static int fx_reg_table(const float* table, float* m, float* v, const int32_t* last_step, int32_t D,
+                        const float* G, FxTableDev* out, int* group_log2, const char* who) {
+    fx_row_state h;
+    memset(&h, 0, sizeof(h));
+    h.table = const_cast<float*>(table); h.m = m; h.v = v; h.last_step = const_cast<int32_t*>(last_step);
+    h.G = G; h.D = D;
+    h.table_dtype = FX_F32;
+    return fx_fill_tables(&h, 1, out, group_log2, who, false);
+}
+
 template <int VEC>
 __global__ __launch_bounds__(256) void k_reg_cross(FxTableDev a, const uint32_t* uniq_row,
                                                    const int32_t* n_unique, const fx_scalars* scal,
@@ -928,10 +892,9 @@ extern "C" int fx_reg_cross(const float* table, int32_t D, const uint32_t* uniq_
     FX_CHECK_ARG(D >= 1 && D <= 256, "fx_reg_cross: D=%d not in [1,256]", D);
     FX_CHECK_ARG(table && uniq_row && n_unique && G && scal && partials,
                  "fx_reg_cross: null pointer");
-    const fx_row_state h = fx_packed_f32(const_cast<float*>(table), nullptr, nullptr, nullptr, D, G);
     FxTableDev a;
     int gl = 0;
-    const int st = fx_fill_tables(&h, 1, &a, &gl, "fx_reg_cross", false);
+    const int st = fx_reg_table(table, nullptr, nullptr, nullptr, D, G, &a, &gl, "fx_reg_cross");
     if (st != FX_OK) return st;
     hipStream_t s = fx_hip_stream(stream);
     dim3 grid(FX_REG_CROSS_BLOCKS);       // fixed: every block writes its (possibly zero) partial
@@ -983,10 +946,9 @@ extern "C" int fx_reg_dense_update(float* table, float* m, float* v, const int32
     if (total_rows <= 0) return FX_OK;
     FX_CHECK_ARG(table && last_step && scal && (!adam || (m && v)),
                  "fx_reg_dense_update: null pointer");
-    const fx_row_state h = fx_packed_f32(table, m, v, const_cast<int32_t*>(last_step), D, nullptr);
     FxTableDev a;
     int gl = 0;
-    const int st = fx_fill_tables(&h, 1, &a, &gl, "fx_reg_dense_update", false);
+    const int st = fx_reg_table(table, m, v, last_step, D, nullptr, &a, &gl, "fx_reg_dense_update");
     if (st != FX_OK) return st;
     int64_t blocks = fx_ceil_div(total_rows, 256 >> gl);
     if (blocks > 256 * 32) blocks = 256 * 32;

@@ -6,7 +6,7 @@ Replaces, for one training step (reference lines):
 The reference's tables are dense-gradient nn.Embedding, so its Adam moves every row each step.
 `sparse_update="exact"` (default) reproduces exactly that trajectory while touching only the rows a
 batch reads: a row's missed zero-gradient steps are replayed in registers when it is next read
-(fx_adam_catchup), and `flush()` replays all rows before evaluate/save/lr change.
+(fx_adam_catchup_rows), and `flush()` replays all rows before evaluate/save/lr change.
 `sparse_update="lazy"` is torch.optim.SparseAdam semantics (rows move only when touched).
 Plain SGD is identical sparse or dense.
 

@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 1
+/* moves with any change of a prototype or of an exported struct's layout */
+#define FX_ABI_VERSION 2
 
 typedef void* fx_stream_t; /* hipStream_t; NULL = the null stream */
 
@@ -300,32 +301,6 @@ int fx_clip_coef(const float* const* parts_host, const int64_t* counts_host, int
                  fx_scalars* scal, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Sparse-row optimizers on the packed table (replace the dense torch.optim step over every row,
- * rank_model.py:322 / torch_utils.py:76).  All take the unique rows of fx_dedup and the reduced
- * gradient rows G (scaled by scal->clip_coef inside).
- *  fx_sparse_adam   : p,m,v of the touched rows, Adam step t = scal->step; last_step[row] = t.
- *  fx_adam_catchup  : "exact" mode — dense Adam also moves rows whose gradient is zero (their
- *                     m/(sqrt(v)+eps) is non-zero once touched).  Replays the zero-gradient
- *                     steps last_step[row]+1 .. upto for the given rows (uniq_row != NULL) or for
- *                     all rows [0,total_rows) (uniq_row == NULL, flush before evaluate/save), so
- *                     the table equals the reference's dense-Adam table.  upto_offset is added
- *                     to scal->step (-1: bring rows to t-1 before the forward of step t; 0: flush).
- *  fx_sparse_sgd    : p -= lr * clip * g (exactly the dense SGD result); last_step (nullable) is
- *                     marked like fx_sparse_adam's.
- * With scal->reg_l1/reg_l2 set, both add the regularizer gradient r(p) = l1 sign(p) + l2 p to g.
- * ------------------------------------------------------------------------------------------ */
-int fx_sparse_adam(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                   const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                   const float* G, const fx_scalars* scal, fx_stream_t stream);
-int fx_adam_catchup(float* table, float* m, float* v, int32_t* last_step, int32_t D,
-                    const uint32_t* uniq_row, const int32_t* n_unique, int64_t n_max,
-                    int64_t total_rows, int32_t upto_offset, const fx_scalars* scal,
-                    fx_stream_t stream);
-int fx_sparse_sgd(float* table, int32_t* last_step, int32_t D, const uint32_t* uniq_row,
-                  const int32_t* n_unique, int64_t n_max, const float* G, const fx_scalars* scal,
-                  fx_stream_t stream);
-
-/* ------------------------------------------------------------------------------------------
  * embedding_regularizer != 0 (BaseModel.regularization_loss, rank_model.py:95-112): the loss gets
  * sum over every FeatureEmbeddingDict parameter of (l1 |p|_1 + l2/2 |p|_2^2), so EVERY table row
  * has a gradient each step — the reference's dense pass, kept dense here (but fused: 2 reads +
@@ -336,7 +311,7 @@ int fx_sparse_sgd(float* table, int32_t* last_step, int32_t D, const uint32_t* u
  *                        |G + r|^2 over all rows = sum r^2 + sum G^2 + this  (for the global clip)
  *  fx_reg_dense_update : Adam (adam=1) / SGD (adam=0) step with g = r(p) * clip for every row
  *                        whose last_step != scal->step (touched rows were stepped, with G + r, by
- *                        fx_sparse_adam / fx_sparse_sgd, which mark last_step).
+ *                        fx_sparse_adam_multi / fx_sparse_sgd_multi, which mark last_step).
  * ------------------------------------------------------------------------------------------ */
 #define FX_REG_BLOCKS 1024
 #define FX_REG_CROSS_BLOCKS 256
@@ -1129,7 +1104,7 @@ int fx_group_metrics(const float* y_pred, const float* y_true, const uint32_t* g
  * (the D=16 tables of FeatureEmbedding and the D=1 tables LogisticRegression builds at
  * logistic_regression.py:44 have identical row layouts).
  *
- * fx_dedup_catchup = fx_dedup (column fast path) + fx_opt_begin_step + fx_adam_catchup, 2 launches:
+ * fx_dedup_catchup = fx_dedup (column fast path) + fx_opt_begin_step + fx_adam_catchup_rows, 2 launches:
  *   launch 1 sorts every id column in LDS and, when begin_scal != NULL, opens the optimizer step
  *   (step += 1, Adam bias corrections: torch.optim.Adam as stepped at rank_model.py:322);
  *   launch 2 derives uniq_row / seg_start / n_unique / sorted_uid (as fx_dedup) and replays the
@@ -1168,17 +1143,24 @@ int fx_group_metrics(const float* y_pred, const float* y_true, const uint32_t* g
  *   and logistic_regression.py:55-58), partial sums in launch 1, finals in launch 2.
  *   workspace: fx_emb_fm_bwd_workspace_floats(n_max, D, Fd) floats.
  *
- * fx_sparse_adam_multi / fx_sparse_sgd_multi: fx_sparse_adam / fx_sparse_sgd for every table group
- *   of one de-dup result in one launch (tables[t].G = that group's reduced gradient).
+ * fx_sparse_adam_multi / fx_sparse_sgd_multi: the sparse-row optimizers (replace the dense torch.optim
+ *   step over every row, rank_model.py:322 / torch_utils.py:76) for every table group of one de-dup
+ *   result in one launch.  They take the unique rows of fx_dedup and tables[t].G = that group's reduced
+ *   gradient rows (scaled by scal->clip_coef inside).  Adam: p, m, v of the touched rows, step
+ *   t = scal->step; last_step[row] = t.  SGD: p -= lr * clip * g (exactly the dense SGD result); m, v are
+ *   not read and last_step (nullable) is marked like Adam's.  With scal->reg_l1 / reg_l2 set, both add
+ *   the regularizer gradient r(p) = l1 sign(p) + l2 p to g.
  *
- * fx_adam_catchup_all: fx_adam_catchup over EVERY row of one table (uniq_row = NULL there), for fp32
- *   or bf16 tables: the flush of the exact mode before evaluate / save / a learning-rate change.
+ * fx_adam_catchup_rows: "exact" mode — dense Adam also moves rows whose gradient is zero (their
+ *   m/(sqrt(v)+eps) is non-zero once touched; torch_utils.py:76, rank_model.py:322).  Replays the
+ *   zero-gradient steps last_step[row]+1 .. upto of the unique rows of ANY de-dup result, so the table
+ *   equals the reference's dense-Adam table; upto_offset is added to scal->step (-1: bring rows to t-1
+ *   before the forward of step t; 0: flush).  For fp32 or bf16 tables and for every table group that
+ *   shares the id plan (<= 4) in ONE launch: the catch-up of the generic de-dup path (sequence columns
+ *   that alias a table, batches beyond fx_dedup_catchup's limits).
  *
- * fx_adam_catchup_rows: fx_adam_catchup over the unique rows of ANY de-dup result, for fp32 or bf16
- *   tables and for every table group that shares the id plan (<= 4) in ONE launch: the catch-up of the
- *   generic de-dup path (sequence columns that alias a table, batches beyond fx_dedup_catchup's
- *   limits).  Replaces what dense torch.optim.Adam does to untouched rows (torch_utils.py:76,
- *   rank_model.py:322), like fx_adam_catchup.
+ * fx_adam_catchup_all: the same replay over EVERY row [0, total_rows) of one table: the flush of the
+ *   exact mode before evaluate / save / a learning-rate change.
  *
  * fx_pack_columns_multi: fx_pack_columns with one destination per column (outs_host[c] = address of
  *   out[0, first column], out_lds_host[c] its row stride, out_dtypes_host[c] FX_I32 | FX_F32), so the

@@ -1,7 +1,7 @@
-"""What do the single-table row optimizer entry points cost?  ops.sparse_adam, ops.sparse_sgd (N unique rows of a
-packed fp32 [R, 16] table, every launch on a different row set so that no row is cache-resident) and the
-full-table flush ops.adam_catchup(..., None, ...), each as launches serialised in one hipGraph between one pair
-of HIP events (what the training step does).  Prints the median of REPS replays per launch, then every replay.
+"""What do the row optimizer launches cost on one table?  ops.sparse_update_multi, "adam" and "sgd" (N unique rows of
+a packed fp32 [R, 16] table, every launch on a different row set so that no row is cache-resident) and the
+full-table flush ops.adam_catchup_all, each as launches serialised in one hipGraph between one pair of HIP events
+(what the training step does).  Prints the median of REPS replays per launch, then every replay.
 usage: python scripts/rowopt_probe.py [R] [N]"""
 import sys
 
@@ -67,16 +67,19 @@ def main():
     gaps = torch.from_numpy(np.minimum((300 * rng.random(R) ** 3).astype(np.int64) + 1, 300)).to(DEV)
     stale = (STEP - gaps).to(torch.int32)         # gaps as in an aged run: 1 .. 300, power-law
 
+    state = ops.RowState(table, m, v, last, D, G=G)
+    sgd_state = ops.RowState(table, None, None, last, D, G=G)
+
     def adam():
         for dd in dds:
-            ops.sparse_adam(table, m, v, last, D, dd, G, scal)
+            ops.sparse_update_multi("adam", [state], dd, scal)
 
     def sgd():
         for dd in dds:
-            ops.sparse_sgd(table, D, dd, G, scal, last_step=last)
+            ops.sparse_update_multi("sgd", [sgd_state], dd, scal)
 
     def flush():
-        ops.adam_catchup(table, m, v, last, D, None, R, 0, scal)
+        ops.adam_catchup_all(state, R, 0, scal)
 
     def age():                                    # (a flush decays the moments: every replay sees the same rows)
         last.copy_(stale)

@@ -142,6 +142,20 @@ def guards_intact(state, rows=ROWS):
                                   % (k, state.layout, D, bad[:4].tolist()))
 
 
+def flush_listed(state, rows, total_rows, upto, upto_offset, scal):
+    """The plain replay of `rows` alone up to step `upto` (= the step of `scal` + upto_offset): fx_adam_catchup_all on
+    `state` with every other row stamped `upto` for the launch, so that the flush skips it, and its stamp put back.
+    fx_adam_catchup_rows hands a D = 16 table alone to the quad replay; the flush is k_catchup_all, which calls the
+    fx_catchup_row of the non-quad arm of k_catchup_rows with the same scalars."""
+    last = state.last_step
+    unlisted = torch.ones(total_rows, dtype=torch.bool, device=last.device)
+    unlisted[torch.as_tensor(rows, dtype=torch.long, device=last.device)] = False
+    stale = last[unlisted].clone()
+    last[unlisted] = upto
+    ops.adam_catchup_all(state, total_rows, upto_offset, scal)
+    last[unlisted] = stale
+
+
 def _reg_grad(p, l1, l2):
     """d/dp of the embedding regularizer as ctr_oracle.OracleTrainer.regularization_loss states it
     (rank_model.py:95-118): sum over (norm, lambda) of lambda / norm * ||p||_norm ^ norm."""

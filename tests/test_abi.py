@@ -18,7 +18,7 @@ def _header_functions():
 
 def test_header_declares_functions():
     names = _header_functions()
-    assert "fx_emb_gather_fwd" in names and "fx_gemm_f32" in names and "fx_sparse_adam" in names
+    assert "fx_emb_gather_fwd" in names and "fx_gemm_f32" in names and "fx_sparse_adam_multi" in names
     assert len(names) >= 25
 
 
@@ -34,7 +34,7 @@ def test_ctypes_table_matches_header():
 
 def test_load_and_version_and_error_string():
     lib = _lib.load()
-    assert lib.fx_abi_version() == 1
+    assert lib.fx_abi_version() == _lib.FX_ABI_VERSION == 2
     assert isinstance(lib.fx_last_error(), bytes)
 
 

@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import rowopt_cases as RC  # noqa: E402
 from fuxictr_amd import _lib, ops  # noqa: E402
 
 DEV = "cuda:0"
@@ -73,13 +74,18 @@ def test_dedup_catchup_equals_dedup_plus_catchup(B, mode):
     scal_b = ops.new_scalars(DEV)
     for s in (scal_a, scal_b):
         s.view(torch.int32)[_lib.SC_STEP] = 8
-    # reference path: begin-step, generic de-dup (column fast path), one catch-up launch per group
+    # reference path: begin-step, generic de-dup (column fast path), one plain replay per group.  (The D = 16 table
+    # alone would take the quad replay in fx_adam_catchup_rows: its plain replay is RC.flush_listed up to step 8.)
     ops.opt_begin_step(scal_a)
     dd_a = ops.dedup(*args, R, ws, columns_sorted=True, want_uid=True)
+    listed = dd_a.uniq_row[:int(dd_a.n_unique.item())].long()
     ref = {}
     for D in (16, 1):
         t, m, v, last = (x.clone().to(DEV) for x in st[D])
-        ops.adam_catchup(t, m, v, last, D, dd_a, R, -1, scal_a)
+        if D == 16:
+            RC.flush_listed(ops.RowState(t, m, v, last, D), listed, R, 8, -1, scal_a)
+        else:
+            ops.adam_catchup_rows([ops.RowState(t, m, v, last, D)], dd_a, -1, scal_a)
         ref[D] = (t, m, v, last)
     # fused path
     got = {D: tuple(x.clone().to(DEV) for x in st[D]) for D in (16, 1)}
@@ -101,7 +107,7 @@ def test_dedup_catchup_equals_dedup_plus_catchup(B, mode):
             else:
                 # (round 5: the D = 16 + D = 1 pair leaves through the quad replay — fx_catchup_quad: the same
                 # terms summed before they meet p, the moments' decay as one power — not the two plain replays
-                # the single-table entry point runs: equal to fp32 rounding, not to the bit)
+                # of the reference path: equal to fp32 rounding, not to the bit)
                 assert (a - b).abs().max().item() <= 2e-6 * max(1.0, a.abs().max().item()), (D, what)
 
 
@@ -396,10 +402,9 @@ def test_sparse_update_multi_equals_one_launch_per_table(kind, dims):
         states_b.append(ops.RowState(b[0], b[1] if kind == "adam" else None,
                                      b[2] if kind == "adam" else None, b[3], D, G=b[4]))
     for D, (t, m, v, last, G) in states_a:
-        if kind == "adam":
-            ops.sparse_adam(t, m, v, last, D, dd, G, scal)
-        else:
-            ops.sparse_sgd(t, D, dd, G, scal, last_step=last)
+        adam = kind == "adam"
+        ops.sparse_update_multi(kind, [ops.RowState(t, m if adam else None, v if adam else None, last, D, G=G)],
+                                dd, scal)
     ops.sparse_update_multi(kind, states_b, dd, scal)
     torch.cuda.synchronize()
     for (D, (t, m, v, last, G)), sb in zip(states_a, states_b):
@@ -412,11 +417,11 @@ def test_sparse_update_multi_equals_one_launch_per_table(kind, dims):
 @pytest.mark.parametrize("series", [False, True])
 @pytest.mark.parametrize("D", [10, 16, 1])
 def test_single_table_catchup_equals_the_row_state_entry_points(D, series):
-    """fx_adam_catchup (one packed fp32 table) against fx_adam_catchup_rows / fx_adam_catchup_all on the same
-    state, to the bit: the plain replay of a row does not depend on the entry point it came in through.  D = 16
-    is the shape fx_adam_catchup_rows hands to the quad replay (equal to fp32 rounding only, see
-    test_dedup_catchup_equals_dedup_plus_catchup); fx_adam_catchup must keep the plain replay there, which is
-    pinned against the same rows of a flush."""
+    """fx_adam_catchup_rows on one table against fx_adam_catchup_all (the flush) on the same state at the listed rows:
+    the plain replay of a row does not depend on the entry point it came in through, to the bit.  D = 16 alone is
+    the shape fx_adam_catchup_rows hands to the quad replay, equal to fp32 rounding only (see
+    test_dedup_catchup_equals_dedup_plus_catchup): there the listed rows are held to dense zero-gradient torch Adam
+    by the fp64 yardstick, and the flush, which is the plain replay, with them."""
     rng = np.random.default_rng(17 + D)
     R = 300
     t, m, v = _tables(rng, R, D)
@@ -437,26 +442,23 @@ def test_single_table_catchup_equals_the_row_state_entry_points(D, series):
         return [x.clone().to(DEV) for x in (t, m, v, last)]
 
     names = ("table", "m", "v", "last_step")
-    one = fresh()
-    ops.adam_catchup(*one, D, dd, R, -1, scal)
-    assert int(one[3].cpu()[rows].min()) == 7 and not torch.equal(one[0].cpu(), t)
+    sel = torch.from_numpy(np.sort(rows))
+    rest = torch.from_numpy(np.setdiff1d(np.arange(R), rows))
+    one, every = fresh(), fresh()
+    ops.adam_catchup_rows([ops.RowState(*one, D)], dd, -1, scal)
+    ops.adam_catchup_all(ops.RowState(*every, D), R, -1, scal)
+    one, every = [x.cpu() for x in one], [x.cpu() for x in every]
+    assert int(one[3][rows].min()) == 7 and not torch.equal(one[0], t)
+    for a, b, what in zip(one, (t, m, v, last), names):
+        assert torch.equal(a[rest], b[rest]), (D, "a row that is not listed", what)
     if D != 16:
-        rs = fresh()
-        ops.adam_catchup_rows([ops.RowState(*rs, D)], dd, -1, scal)
-        for a, b, what in zip(one, rs, names):
-            assert torch.equal(a, b), (D, "rows", what)
-    else:
-        every = fresh()
-        ops.adam_catchup_all(ops.RowState(*every, D), R, -1, scal)
-        sel = torch.from_numpy(np.sort(rows)).to(DEV)
         for a, b, what in zip(one, every, names):
             assert torch.equal(a[sel], b[sel]), (D, "plain replay of the listed rows", what)
-    flush_a, flush_b = fresh(), fresh()
-    ops.adam_catchup(*flush_a, D, None, R, 0, scal)
-    ops.adam_catchup_all(ops.RowState(*flush_b, D), R, 0, scal)
-    assert int(flush_a[3].min()) == 8
-    for a, b, what in zip(flush_a, flush_b, names):
-        assert torch.equal(a, b), (D, "flush", what)
+    else:
+        refs = [RC.ref_catchup(t[sel], m[sel], v[sel], last[sel], 7, 1e-3, f64) for f64 in (False, True)]
+        for got, what in ((one, "quad replay"), (every, "flush")):
+            RC.check_fp32(tuple(x[sel] for x in got), refs[0], refs[1], 7, (D, what, "of the listed rows"))
+    assert int(every[3].min()) == 7
 
 
 def test_pack_columns_multi_all_dtypes():

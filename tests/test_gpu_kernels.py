@@ -246,6 +246,7 @@ def test_sparse_adam_exact_mode_equals_dense_adam(D, series):
     p64, m64, v64 = table0.double(), torch.zeros(R, D, dtype=torch.float64), torch.zeros(R, D, dtype=torch.float64)
     table, m, v = _dev(table0), torch.zeros(R, D, device=DEV), torch.zeros(R, D, device=DEV)
     last = torch.zeros(R, dtype=torch.int32, device=DEV)
+    state = ops.RowState(table, m, v, last, D)
     scal = ops.new_scalars(DEV, lr=lr, series=series)
     assert (int(scal.view(torch.int32)[_lib.SC_SERIES_TCAP].item()) > 0) == series
     ws = torch.empty(ops.dedup_workspace_bytes(64), dtype=torch.uint8, device=DEV)
@@ -261,7 +262,7 @@ def test_sparse_adam_exact_mode_equals_dense_adam(D, series):
         ops.opt_begin_step(scal)
         dd = ops.dedup(_dev(ids, torch.int32), _dev([0], torch.int64), _dev([R], torch.int32),
                        _dev([-1], torch.int32), R, ws)
-        ops.adam_catchup(table, m, v, last, D, dd, R, -1, scal)
+        ops.adam_catchup_rows([state], dd, -1, scal)
         nu = int(dd.n_unique.item())
         rows = dd.uniq_row[:nu].cpu().long()
         # the rows a forward would read now equal the dense-Adam table after t-1 steps
@@ -273,8 +274,9 @@ def test_sparse_adam_exact_mode_equals_dense_adam(D, series):
         g_dense[rows] = G[:nu]
         _adam_ref_step(p_ref, g_dense, m_ref, v_ref, t, lr)
         O.adam_dense(p64, g_dense.double(), m64, v64, t, lr)
-        ops.sparse_adam(table, m, v, last, D, dd, _dev(G), scal)
-    ops.adam_catchup(table, m, v, last, D, None, R, 0, scal)       # flush
+        state.G = _dev(G)
+        ops.sparse_update_multi("adam", [state], dd, scal)
+    ops.adam_catchup_all(state, R, 0, scal)       # flush
     assert int(last.min()) == n_steps
     seen.append(_within_yardstick(table.cpu(), p_ref, p64, 2e-6, "flush"))
     assert (m.cpu() - m_ref).abs().max().item() <= 1e-6
@@ -300,7 +302,7 @@ def test_sparse_sgd_and_clip():
     coef = min(1.0, 1.0 / (total + 1e-6))
     np.testing.assert_allclose(float(scal[_lib.SC_CLIP]), coef, rtol=1e-6)
     np.testing.assert_allclose(float(scal[_lib.SC_TOTAL_NORM]), total, rtol=1e-6)
-    ops.sparse_sgd(table, D, dd, _dev(G), scal)
+    ops.sparse_update_multi("sgd", [ops.RowState(table, None, None, None, D, G=_dev(G))], dd, scal)
     ref = table0.clone()
     ref[[3, 7, 9]] -= 0.5 * coef * G[:3]
     assert (table.cpu() - ref).abs().max().item() <= 1e-6
@@ -319,8 +321,8 @@ def _wide_row_state(D, R=50):
 @pytest.mark.parametrize("kind", ["adam", "sgd"])
 @pytest.mark.parametrize("D", [65, 130, 255])
 def test_sparse_update_of_rows_wider_than_a_wave(D, kind):
-    """Rows of 128 / 256 lanes (odd D > 64, D % 4 == 2 above 128): one step of fx_sparse_adam / fx_sparse_sgd
-    against the fp32 torch step, and the multi-table entry point on the same state to the bit."""
+    """Rows of 128 / 256 lanes (odd D > 64, D % 4 == 2 above 128): one step of fx_sparse_adam_multi /
+    fx_sparse_sgd_multi on one table against the fp32 torch step."""
     g, rows, p0, m0, v0 = _wide_row_state(D)
     R, lr = p0.shape[0], 1e-2
     ids = np.concatenate([rows, rows[:4]]).reshape(12, 1)
@@ -336,9 +338,8 @@ def test_sparse_update_of_rows_wider_than_a_wave(D, kind):
     scal = ops.new_scalars(DEV, lr=lr)
     ops.opt_begin_step(scal)
     one = [_dev(x) for x in (p0, m0, v0)] + [torch.zeros(R, dtype=torch.int32, device=DEV)]
-    two = [x.clone() for x in one]
     if kind == "adam":
-        ops.sparse_adam(*one, D, dd, _dev(G), scal)
+        ops.sparse_update_multi(kind, [ops.RowState(*one, D, G=_dev(G))], dd, scal)
         p_ref, m_ref, v_ref = p0.clone(), m0.clone(), v0.clone()
         _adam_ref_step(p_ref, g_dense, m_ref, v_ref, 1, lr)
         p64, m64, v64 = p0.double(), m0.double(), v0.double()
@@ -346,20 +347,16 @@ def test_sparse_update_of_rows_wider_than_a_wave(D, kind):
         _within_yardstick(one[0].cpu(), p_ref, p64, 2e-6, ("wide adam", D))
         assert (one[1].cpu() - m_ref).abs().max().item() <= 1e-6
         assert (one[2].cpu() - v_ref).abs().max().item() <= 1e-6
-        state = ops.RowState(*two, D, G=_dev(G))
     else:
-        ops.sparse_sgd(one[0], D, dd, _dev(G), scal, last_step=one[3])
+        ops.sparse_update_multi(kind, [ops.RowState(one[0], None, None, one[3], D, G=_dev(G))], dd, scal)
         assert (one[0].cpu() - (p0 - lr * g_dense)).abs().max().item() <= 1e-6
-        state = ops.RowState(two[0], None, None, two[3], D, G=_dev(G))
+        assert torch.equal(one[1].cpu(), m0) and torch.equal(one[2].cpu(), v0)
     assert one[3].cpu().nonzero().view(-1).tolist() == rows.tolist()
-    ops.sparse_update_multi(kind, [state], dd, scal)
-    for a, b, what in zip(one, two, ("table", "m", "v", "last_step")):
-        assert torch.equal(a, b), (D, kind, what)
 
 
 @pytest.mark.parametrize("D", [65, 130, 255])
 def test_adam_catchup_of_rows_wider_than_a_wave(D):
-    """The same widths through fx_adam_catchup, as a row list and as the flush: k zero-gradient steps of dense
+    """The same widths through fx_adam_catchup_rows and the flush fx_adam_catchup_all: k zero-gradient steps of dense
     torch Adam (the fp64 trajectory is the yardstick).  The state the rows idle from is one Adam reaches — t0 real
     steps from zero moments — so |m| / sqrt(v) is bounded as in a run and a row moves by at most ~lr a step: the
     yardstick's 2e-6 floor is an absolute bound on p, written for such moves."""
@@ -382,7 +379,11 @@ def test_adam_catchup_of_rows_wider_than_a_wave(D):
     for form in ("rows", "flush"):
         p, m, v = _dev(p0), _dev(m0), _dev(v0)
         last = torch.full((R,), t0, dtype=torch.int32, device=DEV)
-        ops.adam_catchup(p, m, v, last, D, dd if form == "rows" else None, R, 0, scal)
+        state = ops.RowState(p, m, v, last, D)
+        if form == "rows":
+            ops.adam_catchup_rows([state], dd, 0, scal)
+        else:
+            ops.adam_catchup_all(state, R, 0, scal)
         sel = rows if form == "rows" else np.arange(R)
         rest = np.setdiff1d(np.arange(R), sel)
         _within_yardstick(p.cpu()[sel], p_ref[sel], p64[sel], 2e-6, ("wide catch-up", form, D))
@@ -1129,11 +1130,11 @@ def test_embedding_regularizer_dense_step_equals_dense_optimizer(D, adam):
         total = grad.double().norm().item()
         np.testing.assert_allclose(float(scal[_lib.SC_TOTAL_NORM]), total, rtol=2e-5)
         coef = min(1.0, 0.5 / (total + 1e-6))
+        state = ops.RowState(table, m if adam else None, v if adam else None, last, D, G=_dev(G))
+        ops.sparse_update_multi("adam" if adam else "sgd", [state], dd, scal)
         if adam:
-            ops.sparse_adam(table, m, v, last, D, dd, _dev(G), scal)
             O.adam_dense(p_ref, grad * coef, m_ref, v_ref, step, lr)
         else:
-            ops.sparse_sgd(table, D, dd, _dev(G), scal, last_step=last)
             p_ref -= lr * coef * grad
         ops.reg_dense_update(table, m if adam else None, v if adam else None, last, D, adam, scal)
         assert (table.cpu() - p_ref).abs().max().item() <= 2e-6
@@ -1444,7 +1445,7 @@ def test_catchup_replay_early_exit_matches_the_step_by_step_reference():
     scal = ops.new_scalars(DEV, lr=lr)
     for _ in range(T):
         ops.opt_begin_step(scal)
-    ops.adam_catchup(table, m, v, last, D, None, R, 0, scal)
+    ops.adam_catchup_all(ops.RowState(table, m, v, last, D), R, 0, scal)
     assert int(last.min()) == T and int(last.max()) == T
     p_ref, m_ref, v_ref = p0.clone(), m0.clone(), v0.clone()
     zero = torch.zeros(1, D)

@@ -260,15 +260,42 @@ def test_update_of_several_tables_equals_one_launch_per_table(dims, layout, kind
 
 @functools.lru_cache(maxsize=None)
 def _catchup_one_by_one(dims, widened):
-    """The plain replay of every table of a list: fx_adam_catchup on the packed fp32 arrays (a D = 16 table alone in
-    fx_adam_catchup_rows would take the quad replay)."""
+    """The plain replay of every table of a list, one launch per packed fp32 table: fx_adam_catchup_rows, which for one
+    table is fx_catchup_row on each listed row.  A D = 16 table alone would take the quad replay there; its plain
+    replay is RC.flush_listed.  With the stamps put back, guards_intact holds every unlisted row, all fields, to its
+    first bits."""
     out = []
     for st in _multi_states(dims, "bf16first" if widened else "packed", True, widened):
-        ops.adam_catchup(st.table, st.m, st.v, st.last_step, st.D, _dd(), R, 0, _catchup_scal())
+        if st.D == 16:
+            RC.flush_listed(st, ROWS, R, UPTO, 0, _catchup_scal())
+        else:
+            ops.adam_catchup_rows([st], _dd(), 0, _catchup_scal())
         torch.cuda.synchronize()
         RC.guards_intact(st)
         out.append(st.fields())
     return out
+
+
+@pytest.mark.parametrize("D", [12, 16])
+def test_flush_of_the_listed_rows_is_the_plain_replay(D):
+    """RC.flush_listed, the twin _catchup_one_by_one builds for D = 16.  At D = 12, where fx_adam_catchup_rows has no
+    quad replay, it is that launch bit for bit, unlisted rows included.  At D = 16 this test only holds it to the
+    references of the listed rows, which the quad replay meets too: that it is the plain replay there rests on the
+    code (k_catchup_all and the non-quad arm of k_catchup_rows call the same fx_catchup_row with the same sc, upto,
+    lg, ser) and on the lists (1, 16) and (130, 16, 1, 6) below, whose D = 16 table leaves k_catchup_rows by the
+    non-quad arm and equals this twin to the bit."""
+    _, _, _, _, twin = _state(D, "fp32-packed")
+    RC.flush_listed(twin, ROWS, R, UPTO, 0, _catchup_scal())
+    torch.cuda.synchronize()
+    RC.guards_intact(twin)
+    if D == 12:
+        _, _, _, _, st = _state(D, "fp32-packed")
+        ops.adam_catchup_rows([st], _dd(), 0, _catchup_scal())
+        torch.cuda.synchronize()
+        RC.check_same_bits(twin.fields(), st.fields(), ("flush of the listed rows == fx_adam_catchup_rows", D))
+    refs = _catchup_refs(D, False)
+    RC.check_fp32(_listed(twin.fields(), ROWS), _listed(refs[0], ROWS), _listed(refs[1], ROWS), UPTO,
+                  ("flush of the listed rows", D))
 
 
 def _check_catchup_list(dims, layout, sts, plain, quad_from):
