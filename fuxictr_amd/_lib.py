@@ -204,6 +204,14 @@ SIGNATURES = {
     "fx_seq_score_fwd": (i32, [vp, C.POINTER(SeqParts), vp, i64, i64, i32, i32, vp, i32, vp, vp]),
     "fx_seq_score_bwd": (i32, [vp, C.POINTER(SeqParts), vp, i64, i64, i32, i32, vp, i32, vp, vp, vp,
                                C.POINTER(SeqParts), vp, vp, vp]),
+    "fx_fignn_limits": (None, [vp]),
+    "fx_fignn_tile_rows": (i32, [i32, i32, i32, i32]),
+    "fx_fignn_grad_floats": (i64, [i32, i32, i32, i32]),
+    "fx_fignn_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
+    "fx_fignn_fwd": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fx_fignn_bwd": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "fx_fignn_head_fwd": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    "fx_fignn_head_bwd": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

@@ -16,7 +16,7 @@ SOURCES = ["fx_api.cpp", "fx_embed.hip", "fx_sparse.hip", "fx_gemm.hip", "fx_gem
            "fx_gemm_skinny.hip", "fx_gemm_x6.hip", "fx_dense_misc.hip", "fx_din.hip", "fx_dice.hip", "fx_din_attn.hip", "fx_cin.hip",
            "fx_cin_mfma.hip", "fx_metrics.hip", "fx_fused.hip", "fx_rowopt.hip", "fx_sort.hip", "fx_series.hip", "fx_dedup_lds.hip",
            "fx_mhsa.hip", "fx_group_metrics.hip", "fx_bilinear.hip", "fx_layernorm.hip", "fx_finalmlp.hip", "fx_gatecross.hip",
-           "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip", "fx_gru.hip"]
+           "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip", "fx_gru.hip", "fx_fignn.hip"]
 HEADERS = [os.path.join(CSRC, "fx_common.h"), os.path.join(CSRC, "fx_cin.h"), os.path.join(CSRC, "fx_gemm_int.h"),
            os.path.join(CSRC, "fx_dice_int.h"), os.path.join(CSRC, "fx_rowsum.h"), os.path.join(CSRC, "fx_attn_lds.h"),
            os.path.join(CSRC, "fx_seq_parts.h"),

@@ -4394,6 +4394,174 @@ class AttentionLayer(nn.Module):
         return self.forward_parts(sequence_emb, [target_emb], ids)
 
 
+class _FiGNNFn(torch.autograd.Function):
+    """FiGNN's graph propagation (FiGNN.py:128-172, 200-203) as ONE autograd node over the [B, F, D] record: the
+    attentional graph and all gnn_layers in one launch (ops.fignn_fwd), the backward in one launch and the fixed-order
+    reduce of the per-workgroup parameter gradients (ops.fignn_bwd).  Kept for the backward: the record (a view, no
+    copy) and the inputs of layers 1 .. L-1; the graph, the messages and the gates are recomputed.
+    `params`: per graph layer W_in, W_out, bias_p (views of `packed`), then the GRU's four (with FIGNN_GRU), then
+    W_attn.weight."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, stash, packed, *params):
+        layers, flags = cfg
+        B, F, D = x.shape
+        rows = _field_rows(x)
+        gru = tuple(t.contiguous() for t in params[-5:-1]) if flags & ops.FIGNN_GRU else None
+        w_attn = params[-1].contiguous().view(-1)
+        h_out = _empty(B, F * D, device=x.device)
+        hs = _empty(layers - 1, B, F * D, device=x.device) if stash and layers > 1 else None
+        ops.fignn_fwd(rows, F, D, layers, flags, packed, gru, w_attn, h_out, hs)
+        ctx.save_for_backward(rows, hs, packed, w_attn, *(gru or ()))
+        ctx.cfg = (layers, flags, B, F, D, [p.shape for p in params])
+        return h_out.view(B, F, D)
+
+    @staticmethod
+    def backward(ctx, d_h):
+        layers, flags, B, F, D, shapes = ctx.cfg
+        rows, hs, packed, w_attn = ctx.saved_tensors[:4]
+        gru = tuple(ctx.saved_tensors[4:]) or None
+        dev = rows.device
+        dx = _empty(B, F, D, device=dev)
+        grads = _empty(ops.fignn_grad_floats(F, D, layers, flags), device=dev)
+        ws = _Workspace.get(dev, ops.fignn_workspace_floats(B, F, D, layers, flags), tag="fignn")
+        ops.fignn_bwd(d_h.contiguous().view(B, F * D), rows, F, D, layers, flags, packed, gru, w_attn, hs,
+                      dx.view(B, F * D), grads, ws)
+        out, at = [], 0
+        for shape in shapes:                   # grads is laid out in the order of `params`
+            n = shape.numel()
+            out.append(grads[at:at + n].view(shape))
+            at += n
+        return (dx, None, None, None) + tuple(out)
+
+
+class GraphLayer(nn.Module):
+    """FiGNN.py:175-203: the parameters of one graph layer, `W_in` / `W_out` [F, D, D] (xavier_normal_) and `bias_p`
+    [D] (zeros).  Parameters only: FiGNN_Layer's fused node does the arithmetic for all layers at once."""
+
+    def __init__(self, num_fields, embedding_dim):
+        super(GraphLayer, self).__init__()
+        dev = _alloc_device()
+        self.W_in = nn.Parameter(torch.empty(num_fields, embedding_dim, embedding_dim, device=dev))
+        self.W_out = nn.Parameter(torch.empty(num_fields, embedding_dim, embedding_dim, device=dev))
+        nn.init.xavier_normal_(self.W_in)
+        nn.init.xavier_normal_(self.W_out)
+        self.bias_p = nn.Parameter(torch.zeros(embedding_dim, device=dev))
+
+
+class _GRUCellParams(nn.Module):
+    """torch.nn.GRUCell(D, D)'s parameters under its names and default initialisation."""
+
+    def __init__(self, D):
+        super(_GRUCellParams, self).__init__()
+        dev = _alloc_device()
+        self.weight_ih = nn.Parameter(torch.empty(3 * D, D, device=dev))
+        self.weight_hh = nn.Parameter(torch.empty(3 * D, D, device=dev))
+        self.bias_ih = nn.Parameter(torch.empty(3 * D, device=dev))
+        self.bias_hh = nn.Parameter(torch.empty(3 * D, device=dev))
+        for p in self.parameters():
+            nn.init.uniform_(p, -1.0 / math.sqrt(D), 1.0 / math.sqrt(D))
+
+
+class FiGNN_Layer(_PackedViews, nn.Module):
+    """FiGNN.py:94-172: same constructor, attributes and keys (`gnn.<i>.W_in|W_out|bias_p`, or `gnn.W_in` .. under
+    reuse_graph_layer; `gru.weight_ih|weight_hh|bias_ih|bias_hh`; `W_attn.weight` [1, 2 D]).  The graph layers'
+    Parameters are views of ONE packed [LW, 2 F D D + D] storage, which the kernel reads from one pointer."""
+    _PACKED = ("_packed",)
+
+    def __init__(self, num_fields, embedding_dim, gnn_layers=3, reuse_graph_layer=False, use_gru=True,
+                 use_residual=True):
+        super(FiGNN_Layer, self).__init__()
+        ops.fignn_check(num_fields, embedding_dim, gnn_layers, "FiGNN_Layer")
+        self.num_fields, self.embedding_dim, self.gnn_layers = num_fields, embedding_dim, gnn_layers
+        self.use_residual, self.reuse_graph_layer = use_residual, reuse_graph_layer
+        if reuse_graph_layer:
+            self.gnn = GraphLayer(num_fields, embedding_dim)
+        else:
+            self.gnn = nn.ModuleList([GraphLayer(num_fields, embedding_dim) for _ in range(gnn_layers)])
+        self.gru = _GRUCellParams(embedding_dim) if use_gru else None
+        self.W_attn = FxLinear(embedding_dim * 2, 1, bias=False, device=_alloc_device())
+        self._flags = ops.fignn_flags(use_gru, use_residual, reuse_graph_layer)
+        mods = self._graph_layers()
+        self._packed = torch.empty(len(mods), ops.fignn_layer_floats(num_fields, embedding_dim),
+                                   device=_alloc_device())
+        n = num_fields * embedding_dim * embedding_dim
+        for i, m in enumerate(mods):
+            self._packed[i, :n].copy_(m.W_in.data.reshape(-1))
+            self._packed[i, n:2 * n].copy_(m.W_out.data.reshape(-1))
+            self._packed[i, 2 * n:].copy_(m.bias_p.data)
+        self._bind_views()
+
+    def _graph_layers(self):
+        return [self.gnn] if self.reuse_graph_layer else list(self.gnn)
+
+    def _bind_views(self):
+        F, D = self.num_fields, self.embedding_dim
+        n = F * D * D
+        for i, m in enumerate(self._graph_layers()):
+            m.W_in.data = self._packed[i, :n].view(F, D, D)
+            m.W_out.data = self._packed[i, n:2 * n].view(F, D, D)
+            m.bias_p.data = self._packed[i, 2 * n:]
+
+    def forward(self, feature_emb):
+        F, D = self.num_fields, self.embedding_dim
+        if feature_emb.dim() != 3 or tuple(feature_emb.shape[1:]) != (F, D):
+            raise NotImplementedError("FiGNN_Layer: input {}, built for [batch, {}, {}]".format(
+                tuple(feature_emb.shape), F, D))
+        params = []
+        for m in self._graph_layers():
+            params += [m.W_in, m.W_out, m.bias_p]
+        if self.gru is not None:
+            params += [self.gru.weight_ih, self.gru.weight_hh, self.gru.bias_ih, self.gru.bias_hh]
+        params.append(self.W_attn.weight)
+        stash = torch.is_grad_enabled() and (feature_emb.requires_grad or any(p.requires_grad for p in params))
+        return _FiGNNFn.apply(feature_emb, (self.gnn_layers, self._flags), stash, self._packed, *params)
+
+
+class _FiGNNHeadFn(torch.autograd.Function):
+    """FiGNN.py:228-231 after the mlp2 product: logit = sum_f sigmoid(Z[:, f]) (mlp1 . h_f), one launch per direction
+    (ops.fignn_head_fwd / _bwd).  -> [B, 1].  Z's gradient goes back into the GEMM's node, h gets the score's share."""
+
+    @staticmethod
+    def forward(ctx, h, Z, w1):
+        B, F, D = h.shape
+        H = h.contiguous().view(B, F * D)
+        Z = Z.contiguous()
+        w = w1.contiguous().view(-1)
+        logit = _empty(B, 1, device=h.device)
+        ops.fignn_head_fwd(H, Z, w, F, D, logit)
+        ctx.save_for_backward(H, Z, w)
+        ctx.shape = (B, F, D, w1.shape)
+        return logit
+
+    @staticmethod
+    def backward(ctx, g):
+        H, Z, w = ctx.saved_tensors
+        B, F, D, wshape = ctx.shape
+        dev = H.device
+        dH, dZ, dw = _empty(B, F * D, device=dev), _empty(B, F, device=dev), _empty(D, device=dev)
+        ws = _Workspace.get(dev, ops.fignn_workspace_floats(B, 0, 0, 0, 0), tag="fignn_head")
+        ops.fignn_head_bwd(g.contiguous(), H, Z, w, F, D, dH, dZ, dw, ws)
+        return dH.view(B, F, D), dZ, dw.view(wshape)
+
+
+class AttentionalPrediction(nn.Module):
+    """FiGNN.py:206-231: `mlp1` Linear(D, 1, no bias) and `mlp2` Sequential(Linear(F D, F, no bias), Sigmoid), the
+    same keys.  The [B, F D] x [F D, F] product is the project's GEMM; the scores, the sigmoid and the weighted sum
+    are the head node."""
+
+    def __init__(self, num_fields, embedding_dim):
+        super(AttentionalPrediction, self).__init__()
+        dev = _alloc_device()
+        self.mlp1 = FxLinear(embedding_dim, 1, bias=False, device=dev)
+        self.mlp2 = nn.Sequential(FxLinear(num_fields * embedding_dim, num_fields, bias=False, device=dev),
+                                  nn.Sigmoid())
+
+    def forward(self, h):
+        Z = self.mlp2[0](h.flatten(start_dim=1))
+        return _FiGNNHeadFn.apply(h, Z, self.mlp1.weight)
+
+
 class _SideBySideFn(torch.autograd.Function):
     """`buf` [B, Da + Db] already holds a in its first Da columns and b in the rest (both were written in place):
     hand it on as the concatenation of the two, with the gradient's two column slices (row-strided views, read in

@@ -1926,6 +1926,141 @@ def group_metrics(y_pred, y_true, group_key, key_bits, ndcg_ks=()):
                        for s, name in enumerate(names))
 
 
+# ---- FiGNN: the gated graph propagation over the fields and the attentional head (csrc/fx_fignn.hip) -----
+FIGNN_GRU, FIGNN_RES, FIGNN_REUSE = 1, 2, 4
+
+
+def fignn_flags(use_gru=True, use_residual=True, reuse_graph_layer=False):
+    return (FIGNN_GRU if use_gru else 0) | (FIGNN_RES if use_residual else 0) | (FIGNN_REUSE if reuse_graph_layer else 0)
+
+
+def fignn_limits():
+    """The native envelope of fignn_fwd / fignn_bwd, stated once in the library."""
+    lim = (C.c_int32 * 5)()
+    _lib.load().fx_fignn_limits(lim)
+    return dict(zip(("F_min", "FD_max", "D_max", "layers_max", "F_max"), (int(v) for v in lim)))
+
+
+def fignn_check(F, D, layers, who="fignn"):
+    """The limits of fx_fignn_*, raised here before anything is launched."""
+    lim = fignn_limits()
+    if not lim["F_min"] <= F <= lim["F_max"]:
+        raise NotImplementedError("{}: F={}, the kernel's limit is {} <= F <= {} (a single field has no neighbour: "
+                                  "the reference's soft-max row is all -inf)".format(who, F, lim["F_min"], lim["F_max"]))
+    if not 1 <= D <= lim["D_max"] or F * D > lim["FD_max"]:
+        raise NotImplementedError("{}: D={}, F*D={}, the kernel's limits are 1 <= D <= {} and F*D <= {}"
+                                  .format(who, D, F * D, lim["D_max"], lim["FD_max"]))
+    if not 1 <= layers <= lim["layers_max"]:
+        raise NotImplementedError("{}: gnn_layers={}, the kernel's limit is 1 <= gnn_layers <= {}"
+                                  .format(who, layers, lim["layers_max"]))
+
+
+def fignn_tile_rows(F, D, flags=FIGNN_GRU | FIGNN_RES, backward=False):
+    """Samples one workgroup of fx_fignn_fwd (or _bwd) keeps in LDS for all layers."""
+    return int(_lib.load().fx_fignn_tile_rows(F, D, flags, 1 if backward else 0))
+
+
+def fignn_layer_floats(F, D):
+    """One layer's block of the packed graph weights: [W_in F D D | W_out F D D | bias_p D]."""
+    return 2 * F * D * D + D
+
+
+def fignn_grad_floats(F, D, layers, flags):
+    """grads of fignn_bwd: [LW x (d W_in | d W_out | d bias_p) | d w_ih | d w_hh | d b_ih | d b_hh (GRU) | d w_attn]."""
+    return int(_lib.load().fx_fignn_grad_floats(F, D, layers, flags))
+
+
+def fignn_workspace_floats(B, F, D, layers, flags):
+    """Floats of a workspace that serves fignn_bwd and fignn_head_bwd."""
+    return int(_lib.load().fx_fignn_workspace_floats(B, F, D, layers, flags))
+
+
+def _fignn_check(rec, F, D, layers, flags, W, gru, w_attn):
+    _need_cuda(rec, "rec")
+    fignn_check(F, D, layers)
+    assert rec.dim() == 2 and rec.shape[1] == F * D and rec.stride(1) == 1 and rec.dtype == torch.float32
+    LW = 1 if flags & FIGNN_REUSE else layers
+    assert W.numel() == LW * fignn_layer_floats(F, D) and W.is_contiguous() and W.dtype == torch.float32
+    assert w_attn.numel() == 2 * D and w_attn.is_contiguous()
+    if flags & FIGNN_GRU:
+        w_ih, w_hh, b_ih, b_hh = gru
+        assert tuple(w_ih.shape) == (3 * D, D) and tuple(w_hh.shape) == (3 * D, D)
+        assert b_ih.numel() == 3 * D and b_hh.numel() == 3 * D and all(t.is_contiguous() for t in gru)
+    else:
+        gru = (None,) * 4
+    return rec.shape[0], gru
+
+
+def _fignn_flops(rec, F, D, layers, flags, *a, **kw):
+    per = F * D * (2 * D + F + (6 * D if flags & FIGNN_GRU else 0))
+    return 2.0 * rec.shape[0] * (layers * per + F * F)
+
+
+@_timed("fignn_fwd", "fignn", _fignn_flops)
+def fignn_fwd(rec, F, D, layers, flags, W, gru, w_attn, h_out, hs):
+    """h_out [B, F * D] = the FiGNN layer of rec [B, F * D] (unit column stride, any row stride): the attentional
+    graph, then `layers` rounds of W_out / aggregation / W_in and the GRU cell (or the plain sum) with the residual.
+    W: the packed graph weights, gru: (w_ih, w_hh, b_ih, b_hh) or None, w_attn [2 D]; hs [layers - 1, B, F * D] or None:
+    the layers' inputs, kept for fignn_bwd."""
+    B, gru = _fignn_check(rec, F, D, layers, flags, W, gru, w_attn)
+    assert tuple(h_out.shape) == (B, F * D) and h_out.is_contiguous()
+    assert hs is None or (hs.numel() == (layers - 1) * B * F * D and hs.is_contiguous())
+    check(_lib.load().fx_fignn_fwd(ptr(rec), _rows(rec), B, F, D, layers, flags, ptr(W), ptr(gru[0]), ptr(gru[1]),
+                                   ptr(gru[2]), ptr(gru[3]), ptr(w_attn), ptr(h_out), ptr(hs),
+                                   stream_ptr(rec.device)), "fx_fignn_fwd")
+    return h_out
+
+
+@_timed("fignn_bwd", "fignn", lambda dh, rec, F, D, layers, flags, *a, **kw: 3.0 * _fignn_flops(rec, F, D, layers, flags))
+def fignn_bwd(d_h_out, rec, F, D, layers, flags, W, gru, w_attn, hs, drec, grads, workspace):
+    """From d_h_out [B, F * D]: drec [B, F * D] (own row stride) and grads [fignn_grad_floats(..)], summed over the
+    batch in a fixed order (per-workgroup rows in workspace, then the column sums)."""
+    B, gru = _fignn_check(rec, F, D, layers, flags, W, gru, w_attn)
+    assert tuple(d_h_out.shape) == (B, F * D) and d_h_out.is_contiguous()
+    assert layers == 1 or (hs is not None and hs.numel() == (layers - 1) * B * F * D and hs.is_contiguous())
+    assert tuple(drec.shape) == (B, F * D) and drec.stride(1) == 1
+    assert grads.numel() == fignn_grad_floats(F, D, layers, flags) and grads.is_contiguous()
+    assert workspace.numel() >= fignn_workspace_floats(B, F, D, layers, flags) and workspace.is_contiguous()
+    check(_lib.load().fx_fignn_bwd(ptr(d_h_out), ptr(rec), _rows(rec), B, F, D, layers, flags, ptr(W), ptr(gru[0]),
+                                   ptr(gru[1]), ptr(gru[2]), ptr(gru[3]), ptr(w_attn), ptr(hs), ptr(drec),
+                                   _rows(drec), ptr(grads), ptr(workspace), stream_ptr(rec.device)), "fx_fignn_bwd")
+    return drec, grads
+
+
+def _fignn_head_check(H, Z, w1, F, D):
+    _need_cuda(H, "H")
+    B = H.shape[0]
+    assert tuple(H.shape) == (B, F * D) and H.is_contiguous() and H.dtype == torch.float32
+    assert tuple(Z.shape) == (B, F) and Z.is_contiguous() and w1.numel() == D and w1.is_contiguous()
+    if not 1 <= D <= fignn_limits()["D_max"]:
+        raise NotImplementedError("fignn_head: D={}, the kernel's limit is 1 <= D <= {}"
+                                  .format(D, fignn_limits()["D_max"]))
+    return B
+
+
+@_timed("fignn_head_fwd", "fignn")
+def fignn_head_fwd(H, Z, w1, F, D, logit):
+    """logit [B, 1] = sum_f sigmoid(Z[:, f]) (w1 . H[:, f]): H [B, F * D], Z [B, F] (the mlp2 product), w1 [D]."""
+    B = _fignn_head_check(H, Z, w1, F, D)
+    assert logit.numel() == B and logit.is_contiguous()
+    check(_lib.load().fx_fignn_head_fwd(ptr(H), ptr(Z), ptr(w1), B, F, D, ptr(logit), stream_ptr(H.device)),
+          "fx_fignn_head_fwd")
+    return logit
+
+
+@_timed("fignn_head_bwd", "fignn")
+def fignn_head_bwd(g, H, Z, w1, F, D, dH, dZ, dw1, workspace):
+    """From g = dlogit [B, 1]: dH [B, F * D] (the score's share), dZ [B, F] and dw1 [D] (a fixed-order sum)."""
+    B = _fignn_head_check(H, Z, w1, F, D)
+    assert g.numel() == B and g.is_contiguous()
+    assert tuple(dH.shape) == (B, F * D) and dH.is_contiguous() and tuple(dZ.shape) == (B, F) and dZ.is_contiguous()
+    assert dw1.numel() == D and dw1.is_contiguous()
+    assert workspace.numel() >= fignn_workspace_floats(B, 0, 0, 0, 0) and workspace.is_contiguous()
+    check(_lib.load().fx_fignn_head_bwd(ptr(g), ptr(H), ptr(Z), ptr(w1), B, F, D, ptr(dH), ptr(dZ), ptr(dw1),
+                                        ptr(workspace), stream_ptr(H.device)), "fx_fignn_head_bwd")
+    return dH, dZ, dw1
+
+
 # ---- fused sparse front end / back end (csrc/fx_fused.hip) ----------------------------------------
 class RowState(object):
     """One packed table + its optimizer state (struct fx_row_state)."""

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST and DIEN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN and FiGNN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -10,7 +10,8 @@ model_zoo/GDCN/src/GDCN.py:24-172, model_zoo/AFM/src/AFM.py:24-96,
 model_zoo/DCN/DCN_torch/src/DCN.py:24-101, model_zoo/FwFM/src/FwFM.py:24-91,
 model_zoo/FmFM/src/FmFM.py:25-94,
 model_zoo/BST/src/BST.py:33-366,
-model_zoo/DIEN/src/DIEN.py:27-503), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/DIEN/src/DIEN.py:27-503,
+model_zoo/FiGNN/src/FiGNN.py:27-231), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -20,7 +21,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (AttentionLayer, BehaviorTransformer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -821,6 +822,30 @@ class BST(_ZooModel):
         # so the dict's order is nothing to build the DNN's input on)
         rest = [emb[f] for f in self.feature_map.features if f in emb and f not in dropped]
         return {"y_pred": self.dnn(torch.cat(rest + pooled, dim=-1))}
+
+
+class FiGNN(_ZooModel):
+    """Feature Interaction Graph Neural Network (FiGNN.py:27-231): the fields of a sample as the nodes of a gated
+    graph network (layers.FiGNN_Layer: the attentional graph and all gnn_layers in one launch per direction) under
+    an attentional prediction head (layers.AttentionalPrediction)."""
+
+    def __init__(self, feature_map, model_id="FiGNN", gpu=-1, learning_rate=1e-3, embedding_dim=10, gnn_layers=3,
+                 use_residual=True, use_gru=True, reuse_graph_layer=False, embedding_regularizer=None,
+                 net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        num_fields = feature_map.num_fields
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.fignn = FiGNN_Layer(num_fields, embedding_dim, gnn_layers=gnn_layers,
+                                 reuse_graph_layer=reuse_graph_layer, use_gru=use_gru, use_residual=use_residual)
+        self.fc = AttentionalPrediction(num_fields, embedding_dim)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        h_out = self.fignn(feature_emb)
+        y_pred = self.fc(h_out)
+        return {"y_pred": self.output_activation(y_pred)}
 
 
 def _flat_len(fields):

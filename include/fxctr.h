@@ -1059,6 +1059,55 @@ int fx_seq_score_bwd(const float* interest, const fx_seq_parts* tgt, const int32
                      float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FiGNN (csrc/fx_fignn.hip): the gated graph propagation over the fields of one sample and the attentional
+ * prediction head (model_zoo/FiGNN/src/FiGNN.py:128-231), fused over X [B, F * D] (unit column stride, row stride
+ * ldx).  Per sample, x [F, D]:
+ *     g[i] = softmax_{j != i} leaky_relu_0.01(w_src . x_i + w_dst . x_j),  w_attn [2 D] = w_src | w_dst, built once
+ *     layer l = 0 .. layers-1 from h = x:  o_f = W_out[l][f] h_f,  aggr_i = sum_j g[i][j] o_j,
+ *         a_i = W_in[l][i] aggr_i + bias_p[l];  h = GRUCell(a, h) (FX_FIGNN_GRU: torch's cell, chunks r, z, n,
+ *         w_ih / w_hh [3 D, D], b_ih / b_hh [3 D], shared by fields and layers) or h = a + h;  FX_FIGNN_RES: h += x.
+ *     W: [LW][W_in F D D | W_out F D D | bias_p D] packed, LW = layers, or 1 with FX_FIGNN_REUSE (every layer reads
+ *     the same block and the gradients sum over the layers).
+ *   fx_fignn_fwd : one launch: h_out [B, F * D] contiguous; with layers > 1 and `hs` not NULL also the inputs of
+ *                  layers 1 .. layers-1, hs [layers - 1, B, F * D] (what the backward reads; g is recomputed).
+ *   fx_fignn_bwd : one launch from d_h_out [B, F * D] back through the layers and the graph: dX [B, F * D] (row stride
+ *                  lddx; layers + residual + graph, plain stores) and one row of parameter gradients per workgroup in
+ *                  `workspace`, then a fixed-order sum (one workgroup: straight into grads):
+ *                  grads = [LW x (d W_in | d W_out | d bias_p) | d w_ih | d w_hh | d b_ih | d b_hh (FX_FIGNN_GRU) |
+ *                  d w_attn (2 D)] (fx_fignn_grad_floats).
+ *   fx_fignn_head_fwd : logit[b] = sum_f sigmoid(Z[b, f]) (w1 . h[b, f]);  H [B, F * D], Z [B, F] contiguous (Z is the
+ *                  [B, F * D] x [F * D, F] product of the project's GEMM), w1 [D].
+ *   fx_fignn_head_bwd : from g [B]: dH [B, F * D] (the score's share; Z's share comes back through the GEMM), dZ [B, F],
+ *                  dw1 [D] by per-workgroup rows in `workspace` and a fixed-order sum.
+ *   A workgroup owns a tile of samples (fx_fignn_tile_rows) in LDS for all layers; W streams past the tile.
+ *   No atomics: two runs give the same bits.  fp32.
+ *   fx_fignn_limits : limits[5] = {least F, most F * D, most D, most layers, most F}: the native envelope
+ *                  (housekeeping); a shape outside it is FX_ERR_INVALID, never a launch.
+ *   fx_fignn_tile_rows : samples one workgroup owns at a time, forward (backward = 0) or backward; 0 outside the
+ *                  envelope (housekeeping).
+ *   fx_fignn_grad_floats : floats of `grads` (housekeeping).
+ *   fx_fignn_workspace_floats : floats of a workspace that serves fx_fignn_bwd and fx_fignn_head_bwd (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+#define FX_FIGNN_GRU 1
+#define FX_FIGNN_RES 2
+#define FX_FIGNN_REUSE 4
+void fx_fignn_limits(int32_t* limits);
+int32_t fx_fignn_tile_rows(int32_t F, int32_t D, int32_t flags, int32_t backward);
+int64_t fx_fignn_grad_floats(int32_t F, int32_t D, int32_t layers, int32_t flags);
+int64_t fx_fignn_workspace_floats(int64_t B, int32_t F, int32_t D, int32_t layers, int32_t flags);
+int fx_fignn_fwd(const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t layers, int32_t flags,
+                 const float* W, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                 const float* w_attn, float* h_out, float* hs, fx_stream_t stream);
+int fx_fignn_bwd(const float* d_h_out, const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t layers,
+                 int32_t flags, const float* W, const float* w_ih, const float* w_hh, const float* b_ih,
+                 const float* b_hh, const float* w_attn, const float* hs, float* dX, int64_t lddx, float* grads,
+                 float* workspace, fx_stream_t stream);
+int fx_fignn_head_fwd(const float* H, const float* Z, const float* w1, int64_t B, int32_t F, int32_t D, float* logit,
+                      fx_stream_t stream);
+int fx_fignn_head_bwd(const float* g, const float* H, const float* Z, const float* w1, int64_t B, int32_t F, int32_t D,
+                      float* dH, float* dZ, float* dw1, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
