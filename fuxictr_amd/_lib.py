@@ -212,6 +212,11 @@ SIGNATURES = {
     "fx_fignn_bwd": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     "fx_fignn_head_fwd": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
     "fx_fignn_head_bwd": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "fx_crossmix_limits": (None, [vp]),
+    "fx_crossmix_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
+    "fx_crossmix_fwd": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "fx_crossmix_bwd": (i32, [vp, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp,
+                              vp, vp, vp, vp]),
     "fx_binary_metrics_workspace_bytes": (C.c_size_t, [i64]),
     "fx_binary_metrics": (i32, [vp, vp, i64, vp, C.c_size_t, vp, vp, vp]),
     "fx_group_metrics_workspace_bytes": (C.c_size_t, [i64]),

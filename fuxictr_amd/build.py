@@ -16,7 +16,7 @@ SOURCES = ["fx_api.cpp", "fx_embed.hip", "fx_sparse.hip", "fx_gemm.hip", "fx_gem
            "fx_gemm_skinny.hip", "fx_gemm_x6.hip", "fx_dense_misc.hip", "fx_din.hip", "fx_dice.hip", "fx_din_attn.hip", "fx_cin.hip",
            "fx_cin_mfma.hip", "fx_metrics.hip", "fx_fused.hip", "fx_rowopt.hip", "fx_sort.hip", "fx_series.hip", "fx_dedup_lds.hip",
            "fx_mhsa.hip", "fx_group_metrics.hip", "fx_bilinear.hip", "fx_layernorm.hip", "fx_finalmlp.hip", "fx_gatecross.hip",
-           "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip", "fx_gru.hip", "fx_fignn.hip"]
+           "fx_afm.hip", "fx_crossnet.hip", "fx_pairfm.hip", "fx_bst.hip", "fx_gru.hip", "fx_fignn.hip", "fx_crossmix.hip"]
 HEADERS = [os.path.join(CSRC, "fx_common.h"), os.path.join(CSRC, "fx_cin.h"), os.path.join(CSRC, "fx_gemm_int.h"),
            os.path.join(CSRC, "fx_dice_int.h"), os.path.join(CSRC, "fx_rowsum.h"), os.path.join(CSRC, "fx_attn_lds.h"),
            os.path.join(CSRC, "fx_seq_parts.h"),
@@ -27,7 +27,9 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-un
             "--offload-arch=" + ARCH]
 # per-file additions.  fx_cin_mfma.hip: the arithmetic on MFMA result tiles must stay scalar v_fma_f32 (a
 # packed v_pk_fma_f32 holds the matrix pipe ~22 cycles per issue)
-EXTRA_FLAGS = {"fx_cin_mfma.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"fx_cin_mfma.hip": ["-fno-slp-vectorize"],
+               # fx_crossmix.hip: the same, and no packed fp32 arithmetic at all next to its MFMAs
+               "fx_crossmix.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _digest(paths):

@@ -2934,6 +2934,74 @@ class CrossNetV2(nn.Module):
         return _CrossNetV2Fn.apply(X_0, *wb)
 
 
+class _CrossNetMixFn(torch.autograd.Function):
+    """The whole CrossNetMix stack (cross_net.py:158-201) as ONE autograd node: one launch forward
+    (ops.crossmix_fwd), one launch backward and the weight-gradient products over the batch (ops.crossmix_bwd).
+    Kept for the backward: x (a view, no copy), x_1 .. x_{L-1} and the down products [L, B, E r + E]; both tanh, the
+    soft-max and the low-rank outputs are recomputed.  `params`: U_list, V_list, C_list, bias (L each), then the
+    E gating weights."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, stash, *params):
+        L, E = cfg
+        U, V, Cs, bias, gate, _ = _split(params, L, L, L, L, E)
+        x = _unit_cols(x)
+        B, W = x.shape
+        r, dev = U[0].shape[2], x.device
+        out = _empty(B, W, device=dev)
+        xs = _empty(L - 1, B, W, device=dev) if L > 1 else None
+        zs = _empty(L, B, E * r + E, device=dev) if stash else None
+        ops.crossmix_fwd(x, U, V, Cs, bias, gate, out, xs, zs)
+        ctx.save_for_backward(x, xs, zs, *params)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        L, E = ctx.cfg
+        x, xs, zs = ctx.saved_tensors[:3]
+        U, V, Cs, bias, gate, _ = _split(ctx.saved_tensors[3:], L, L, L, L, E)
+        B, W = x.shape
+        r = U[0].shape[2]
+        dx = _empty(B, W, device=x.device)
+        ws = _Workspace.get(x.device, ops.crossmix_workspace_floats(B, W, r, E, L), tag="crossmix")
+        dU, dV, dC, dbias, dgate = ops.crossmix_bwd(_unit_cols(d_out), x, U, V, Cs, bias, gate, xs, zs, dx, ws)
+        grads = list(dU) + list(dV) + list(dC) + [dbias[l].view(W, 1) for l in range(L)] + \
+            [dgate[e].view(1, W) for e in range(E)]
+        return (dx, None, None) + tuple(grads)
+
+
+class CrossNetMix(nn.Module):
+    """cross_net.py:132-201: same constructor, attributes, initialisers and state_dict keys (`U_list.<l>`, `V_list.<l>`
+    [E, W, r], `C_list.<l>` [E, r, r], `gating.<e>.weight` [1, W], `bias.<l>` [W, 1]).  All layers run as one node
+    (_CrossNetMixFn) that reads the Parameters in place."""
+
+    def __init__(self, in_features, layer_num=2, low_rank=32, num_experts=4):
+        super(CrossNetMix, self).__init__()
+        ops.crossmix_check(in_features, low_rank, num_experts, layer_num, "CrossNetMix")
+        self.layer_num, self.num_experts = layer_num, num_experts
+        dev = _alloc_device()
+
+        def xavier(*shape):
+            return nn.Parameter(nn.init.xavier_normal_(torch.empty(*shape, device=dev)))
+        self.U_list = nn.ParameterList([xavier(num_experts, in_features, low_rank) for _ in range(layer_num)])
+        self.V_list = nn.ParameterList([xavier(num_experts, in_features, low_rank) for _ in range(layer_num)])
+        self.C_list = nn.ParameterList([xavier(num_experts, low_rank, low_rank) for _ in range(layer_num)])
+        self.gating = nn.ModuleList([FxLinear(in_features, 1, bias=False, device=dev) for _ in range(num_experts)])
+        self.bias = nn.ParameterList([nn.Parameter(torch.zeros(in_features, 1, device=dev))
+                                      for _ in range(layer_num)])
+
+    def forward(self, inputs):
+        if inputs.dim() != 2 or inputs.shape[1] != self.bias[0].shape[0]:
+            raise NotImplementedError("CrossNetMix: input {}, built for [batch, {}]".format(
+                tuple(inputs.shape), self.bias[0].shape[0]))
+        params = list(self.U_list) + list(self.V_list) + list(self.C_list) + list(self.bias) + \
+            [g.weight for g in self.gating]
+        stash = torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in params))
+        out = _CrossNetMixFn.apply(inputs, (self.layer_num, self.num_experts), stash, *params)
+        return out.squeeze()                    # the reference's bare squeeze(): [W] for a batch of one
+
+
 class _MHSAFn(torch.autograd.Function):
     """One self-attention layer over the fields as ONE autograd node (AutoInt.py:157-191): forward one
     launch, backward two (ops.mhsa_fwd / mhsa_bwd).  Kept for the backward: the layer's output (the ReLU

@@ -2061,6 +2061,122 @@ def fignn_head_bwd(g, H, Z, w1, F, D, dH, dZ, dw1, workspace):
     return dH, dZ, dw1
 
 
+# ---- CrossNetMix: DCNv2's low-rank mixture cross network, the whole stack per launch (csrc/fx_crossmix.hip) ----
+def crossmix_limits():
+    """The native envelope of crossmix_fwd / crossmix_bwd, stated once in the library."""
+    lim = (C.c_int32 * 7)()
+    _lib.load().fx_crossmix_limits(lim)
+    return dict(zip(("tile_rows", "W_max", "r_max", "E_max", "Er_max", "layers_max", "workgroups_max"),
+                    (int(v) for v in lim)))
+
+
+def crossmix_check(W, r, E, layers, who="crossmix"):
+    """The limits of fx_crossmix_*, raised here before anything is launched."""
+    lim = crossmix_limits()
+    if not (1 <= W <= lim["W_max"] and 1 <= r <= lim["r_max"] and 1 <= E <= lim["E_max"] and E * r <= lim["Er_max"]
+            and 1 <= layers <= lim["layers_max"]):
+        raise NotImplementedError(
+            "{}: in_features={}, low_rank={}, num_experts={}, layers={}; the kernel's limits are in_features <= {}, "
+            "low_rank <= {}, num_experts <= {}, num_experts*low_rank <= {}, 1 <= layers <= {}".format(
+                who, W, r, E, layers, lim["W_max"], lim["r_max"], lim["E_max"], lim["Er_max"], lim["layers_max"]))
+
+
+def _crossmix_split_k(B):
+    return max(1, min(16, B // 256))
+
+
+def crossmix_workspace_floats(B, W, r, E, layers):
+    """Floats of crossmix_bwd's workspace: the kernel's part (fx_crossmix_workspace_floats: the x_0 share of dX and
+    one row of dC / dbias sums per workgroup), the split-K slabs of its layers * (2 E + 1) weight-gradient products
+    and the partial sums of the gate gradient over the layers."""
+    sk = _crossmix_split_k(B)
+    slabs = 0 if sk == 1 else layers * (2 * E * gemm_workspace_floats(W, r, sk) + gemm_workspace_floats(E, W, sk))
+    gate_sum = _lib.FX_COLSUM_CHUNKS * E * W if layers > 1 else 0
+    return int(_lib.load().fx_crossmix_workspace_floats(B, W, r, E, layers)) + slabs + gate_sum
+
+
+def _crossmix_check(x, U, V, Cs, bias, gate):
+    _need_cuda(x, "x")
+    layers, (E, W, r) = len(U), U[0].shape
+    crossmix_check(W, r, E, layers)
+    assert x.dim() == 2 and x.shape[1] == W and x.stride(1) == 1 and x.dtype == torch.float32
+    assert len(V) == len(Cs) == len(bias) == layers and len(gate) == E
+    for u, v, c, b in zip(U, V, Cs, bias):
+        assert tuple(u.shape) == (E, W, r) and tuple(v.shape) == (E, W, r) and tuple(c.shape) == (E, r, r)
+        assert b.numel() == W and all(t.is_contiguous() and t.dtype == torch.float32 for t in (u, v, c, b))
+    assert all(g.numel() == W and g.is_contiguous() and g.dtype == torch.float32 for g in gate)
+    lists = tuple(_lib.ptr_array(list(ts)) for ts in (U, V, Cs, bias, gate))
+    return x.shape[0], W, r, E, layers, lists
+
+
+def _crossmix_flops(x, U, *a, **kw):
+    E, W, r = U[0].shape
+    return 2.0 * x.shape[0] * len(U) * (W * (E * r + E) + E * r * r + E * r * W)
+
+
+@_timed("crossmix_fwd", "crossmix", _crossmix_flops)
+def crossmix_fwd(x, U, V, Cs, bias, gate, out, xs, zs):
+    """out [B, W] = CrossNetMix of x [B, W] (unit column stride, any row stride; so `out`).  U, V: per layer
+    [E, W, r]; Cs: per layer [E, r, r]; bias: per layer W floats; gate: per expert W floats (shared by the layers).
+    xs [layers - 1, B, W] (None with one layer): x_1 .., zs [layers, B, E r + E] or None: the down products, both kept
+    for crossmix_bwd."""
+    B, W, r, E, layers, (pU, pV, pC, pb, pg) = _crossmix_check(x, U, V, Cs, bias, gate)
+    assert tuple(out.shape) == (B, W) and out.stride(1) == 1
+    assert layers == 1 or (xs is not None and xs.numel() == (layers - 1) * B * W and xs.is_contiguous())
+    assert zs is None or (zs.numel() == layers * B * (E * r + E) and zs.is_contiguous())
+    check(_lib.load().fx_crossmix_fwd(ptr(x), _rows(x), B, W, r, E, layers, pU, pV, pC, pb, pg, ptr(out), _rows(out),
+                                      ptr(xs), ptr(zs), stream_ptr(x.device)), "fx_crossmix_fwd")
+    return out
+
+
+@_timed("crossmix_bwd", "crossmix", lambda d, x, U, *a, **kw: 3.0 * _crossmix_flops(x, U))
+def crossmix_bwd(d_out, x, U, V, Cs, bias, gate, xs, zs, dX, workspace):
+    """From d_out [B, W]: dX [B, W] (own row stride) in one launch, and the parameter gradients
+    -> (dU [layers, E, W, r], dV [layers, E, W, r], dC [layers, E, r, r], dbias [layers, W], dgate [E, W]):
+    dC and dbias from the kernel's per-workgroup rows in a fixed order, the other three as [W x B] . [B x n] products of
+    one fx_gemm_f32_batch call over what the kernel wrote (dpre, the scaled low-rank operand, the down product's
+    gradient), one problem per layer and expert."""
+    B, W, r, E, layers, (pU, pV, pC, pb, pg) = _crossmix_check(x, U, V, Cs, bias, gate)
+    N1, NG, dev = E * r, E * r + E, x.device
+    assert tuple(d_out.shape) == (B, W) and d_out.stride(1) == 1 and tuple(dX.shape) == (B, W) and dX.stride(1) == 1
+    assert layers == 1 or (xs is not None and xs.numel() == (layers - 1) * B * W and xs.is_contiguous())
+    assert zs is not None and zs.numel() == layers * B * NG and zs.is_contiguous()
+    assert workspace.numel() >= crossmix_workspace_floats(B, W, r, E, layers) and workspace.is_contiguous()
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    dpre, P, dZ = new(layers, B, W), new(layers, B, N1), new(layers, B, NG)
+    dU, dV, dC, dbias = new(layers, E, W, r), new(layers, E, W, r), new(layers, E, r, r), new(layers, W)
+    dgl = new(layers, E, W)
+    check(_lib.load().fx_crossmix_bwd(ptr(d_out), _rows(d_out), ptr(x), _rows(x), B, W, r, E, layers, pU, pV, pC, pb,
+                                      pg, ptr(zs), ptr(dX), _rows(dX), ptr(dpre), ptr(P), ptr(dZ), ptr(dC), ptr(dbias),
+                                      ptr(workspace), stream_ptr(dev)), "fx_crossmix_bwd")
+    sk = _crossmix_split_k(B)
+    at = [int(_lib.load().fx_crossmix_workspace_floats(B, W, r, E, layers))]
+
+    def slab(M, N):
+        if sk == 1:
+            return None
+        n = gemm_workspace_floats(M, N, sk)
+        at[0] += n
+        return workspace[at[0] - n:at[0]]
+    problems = []
+    for l in range(layers):
+        xl = x if l == 0 else xs.view(layers - 1, B, W)[l - 1]
+        for e in range(E):
+            cols = slice(e * r, (e + 1) * r)
+            problems.append(gemm_problem(dpre[l], P[l][:, cols], dU[l, e], transa=True, split_k=sk,
+                                         workspace=slab(W, r)))
+            problems.append(gemm_problem(xl, dZ[l][:, cols], dV[l, e], transa=True, split_k=sk, workspace=slab(W, r)))
+        problems.append(gemm_problem(dZ[l][:, N1:], xl, dgl[l], transa=True, split_k=sk, workspace=slab(E, W)))
+    gemm_batch(problems)
+    if layers == 1:
+        return dU, dV, dC, dbias, dgl[0]
+    dgate = new(E, W)           # the gate is shared: its gradient sums over the layers
+    colsum(dgl.view(layers, E * W), dgate.view(-1), workspace[at[0]:at[0] + _lib.FX_COLSUM_CHUNKS * E * W])
+    return dU, dV, dC, dbias, dgate
+
+
 # ---- fused sparse front end / back end (csrc/fx_fused.hip) ----------------------------------------
 class RowState(object):
     """One packed table + its optimizer state (struct fx_row_state)."""

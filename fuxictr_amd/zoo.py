@@ -21,7 +21,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetV2, DIN_Attention, Dice,
+from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -96,13 +96,14 @@ class DCNv2(_ZooModel):
         self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
         assert model_structure in self._STRUCTURES, \
             "model_structure={} not supported!".format(model_structure)
-        if use_low_rank_mixture:
-            raise NotImplementedError("CrossNetMix is outside the hot-path scope (SURVEY §2 #5)")
         self.model_structure = model_structure
         stacked, parallel = self._STRUCTURES[model_structure]
         width = feature_map.sum_emb_out_dim()
         self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
-        self.crossnet = CrossNetV2(width, num_cross_layers)
+        if use_low_rank_mixture:
+            self.crossnet = CrossNetMix(width, num_cross_layers, low_rank=low_rank, num_experts=num_experts)
+        else:
+            self.crossnet = CrossNetV2(width, num_cross_layers)
         head_in = 0 if stacked else width                   # what feeds `fc` from the cross branch
         if stacked:                                         # cross output -> DNN
             self.stacked_dnn = self._tower(width, stacked_dnn_hidden_units, dnn_activations,
@@ -135,6 +136,8 @@ class DCNv2(_ZooModel):
         tower is a plain Linear / ReLU stack over 16-byte aligned rows; else None."""
         from .layers import _CrossDeepFn
         fz = getattr(self.parallel_dnn, "_fused", None)
+        if isinstance(self.crossnet, CrossNetMix):          # the mixture keeps the cat route
+            return None
         if fz is None or fz[1] or flat.dim() != 2 or flat.shape[1] % 4 or self.crossnet.num_layers < 1:
             return None
         stack = fz[0]

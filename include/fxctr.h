@@ -1108,6 +1108,39 @@ int fx_fignn_head_bwd(const float* g, const float* H, const float* Z, const floa
                       float* dH, float* dZ, float* dw1, float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CrossNetMix (csrc/fx_crossmix.hip): DCNv2's low-rank mixture cross network, the whole stack of `layers` layers in
+ * one launch per direction on fp32 MFMA (fuxictr/pytorch/layers/interactions/cross_net.py:132-201).  X [B, W] (unit
+ * column stride, row stride ldx); per layer l: U[l], V[l] [E, W, r], C[l] [E, r, r], bias[l] [W]; gate[e] [W], shared
+ * by the layers.  U, V, C, bias are host arrays of `layers` device pointers, gate one of E; all read in place.
+ *     s_e = gate[e] . x_l,  g = softmax_e(s),  h_e = tanh(C_e tanh(V_e^T x_l)),
+ *     x_{l+1} = x_0 * (sum_e g_e U_e h_e + bias) + x_l           (sum_e g_e = 1: the bias is added once)
+ *   fx_crossmix_fwd : out [B, W] (row stride ldo) = x_layers; xs [layers - 1, B, W] = x_1 .. x_{layers-1} (needed
+ *                  with layers > 1: the kernel reads a layer's input back from it); zs [layers, B, E r + E] or NULL:
+ *                  the down products x_l [V_1 | .. | V_E | gate] that fx_crossmix_bwd reads.
+ *   fx_crossmix_bwd : from dOut [B, W] (row stride lddo) back through the layers: dX [B, W] (row stride lddx, both
+ *                  shares of x_0, plain stores), dC [layers, E, r, r] and dbias [layers, W] (per-workgroup rows in
+ *                  `workspace`, summed in a fixed order), and what the weight-gradient products over the batch take:
+ *                  dpre [layers, B, W] = dx_{l+1} * x_0, P [layers, B, E r] = the scaled low-rank operand g_e h_e, dZ
+ *                  [layers, B, E r + E] = the gradient of the down product; then dU[l][e] = dpre_l^T P_l[:, e],
+ *                  dV[l][e] = x_l^T dZ_l[:, e] and dgate[e] = sum_l dZ_l[:, E r + e]^T x_l are fx_gemm_f32_batch
+ *                  problems.  tanh, the soft-max and h are recomputed from zs.
+ *   A workgroup owns fx_crossmix_limits' tile of samples for all layers.  No atomics: two runs give the same bits.
+ *   fx_crossmix_limits : limits[7] = {samples per tile, most W, most r, most E, most E r, most layers, most
+ *                  workgroups of a launch}: the native envelope (housekeeping); a shape outside it is
+ *                  FX_ERR_INVALID, never a launch.
+ *   fx_crossmix_workspace_floats : floats of fx_crossmix_bwd's workspace; 0 outside the envelope (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+void fx_crossmix_limits(int32_t* limits);
+int64_t fx_crossmix_workspace_floats(int64_t B, int32_t W, int32_t r, int32_t E, int32_t layers);
+int fx_crossmix_fwd(const float* X, int64_t ldx, int64_t B, int32_t W, int32_t r, int32_t E, int32_t layers,
+                    const float* const* U, const float* const* V, const float* const* C, const float* const* bias,
+                    const float* const* gate, float* out, int64_t ldo, float* xs, float* zs, fx_stream_t stream);
+int fx_crossmix_bwd(const float* dOut, int64_t lddo, const float* X, int64_t ldx, int64_t B, int32_t W, int32_t r,
+                    int32_t E, int32_t layers, const float* const* U, const float* const* V, const float* const* C,
+                    const float* const* bias, const float* const* gate, const float* zs, float* dX, int64_t lddx,
+                    float* dpre, float* P, float* dZ, float* dC, float* dbias, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device evaluation metrics for BaseModel.evaluate (rank_model.py:350-381, metrics.py:49-51):
  * binary logloss (sklearn.metrics.log_loss on float64: probabilities clipped to
  * [DBL_EPSILON, 1-DBL_EPSILON]) and AUC (sklearn.metrics.roc_auc_score = Mann-Whitney U with
