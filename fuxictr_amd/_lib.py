@@ -149,6 +149,10 @@ SIGNATURES = {
     "fx_mhsa_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "fx_mhsa_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp,
                           i64, i32, vp, vp, vp]),
+    "fx_dsa_limits": (None, [vp]),
+    "fx_dsa_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
+    "fx_dsa_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "fx_dsa_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp]),
     "fx_senet_workspace_floats": (i64, [i64, i32, i32]),
     "fx_senet_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
     "fx_senet_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),

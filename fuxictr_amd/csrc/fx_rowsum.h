@@ -10,7 +10,7 @@
 // four waves whatever the row count, and the fp64 sum of fp32 partials rounds once, at the end.  The other
 // combinations stay because their callers' results are pinned to the bit, not because they are better:
 //   <float,  SLICES>  fx_colsum (fx_dense_misc.hip; through it AFM, FwFM / FmFM, BST and the bias gradient)
-//   <double, SLICES>  fx_mhsa_bwd, fx_bilinear_bwd (its slabs), fx_senet_bwd
+//   <double, SLICES>  fx_mhsa_bwd, fx_dsa_bwd, fx_bilinear_bwd (its slabs), fx_senet_bwd
 //   <float,  RUNS>    fx_gate2_bwd, fx_biagg_bwd (fx_finalmlp.hip)
 //   <float,  SERIAL>  fx_layernorm_bwd, fx_emb_numeric_grad
 // Fewer rows than waves (one row included) take no arm of their own: a wave without rows adds an exact 0.

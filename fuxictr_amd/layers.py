@@ -3079,6 +3079,88 @@ class MultiHeadSelfAttention(nn.Module):
         return out
 
 
+class _DSAFn(torch.autograd.Function):
+    """One disentangled self-attention layer as ONE autograd node (DESTINE.py:179-227): forward one launch,
+    backward two (ops.dsa_fwd / dsa_bwd).  Kept for the backward: X; everything else is recomputed.
+    params: W_q, W_k, W_v, W_res | None, W_unary, then their biases in the same order."""
+
+    @staticmethod
+    def forward(ctx, x, num_heads, use_scale, relu_before_att, *params):
+        if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
+            x = x.contiguous()
+        W, bias = params[:5], params[5:]
+        B, F, _ = x.shape
+        y = torch.empty(B, F, W[0].shape[0], dtype=torch.float32, device=x.device)
+        ops.dsa_fwd(x, W, bias, num_heads, use_scale, relu_before_att, y)
+        ctx.x, ctx.w, ctx.bias = x, W, bias
+        ctx.cfg = (num_heads, use_scale, relu_before_att)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W, bias = ctx.x, ctx.w, ctx.bias
+        H, use_scale, relu_before_att = ctx.cfg
+        B, F, D = x.shape
+        A = W[0].shape[0]
+        has_res = W[3] is not None
+        n_w = 4 if has_res else 3
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        dW = torch.empty(ops.dsa_grad_floats(D, A, H, has_res), dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(x.device, ops.dsa_workspace_floats(B, D, A, H, has_res), tag="dsa")
+        ops.dsa_bwd(x, W, bias, H, use_scale, relu_before_att, dy.contiguous(), dx, dW, ws)
+        # dW's segments: the [A, D] matrices, W_unary [H, D], the [A] biases, the unary bias [H]
+        dWm = dW[:n_w * A * D].view(n_w, A, D)
+        dWu = dW[n_w * A * D:(n_w * A + H) * D].view(H, D)
+        db = dW[(n_w * A + H) * D:(n_w * A + H) * D + n_w * A].view(n_w, A)
+        dbu = dW[(n_w * A + H) * D + n_w * A:]
+        return (dx, None, None, None, dWm[0], dWm[1], dWm[2], dWm[3] if has_res else None, dWu,
+                db[0], db[1], db[2], db[3] if has_res else None, dbu)
+
+
+class DisentangledSelfAttention(nn.Module):
+    """The interaction layer of DESTINE (model_zoo/DESTINE/src/DESTINE.py:143-227): same constructor, same
+    parameter containers (`W_q`, `W_k`, `W_v`, `W_unary`, `W_res`, every one an nn.Linear with bias) and keys; the
+    arithmetic is fx_dsa_*.  forward(X, X, X): [batch, fields, embedding_dim] -> [batch, fields, attention_dim]."""
+
+    def __init__(self, embedding_dim, attention_dim=64, num_heads=1, dropout_rate=0.1, use_residual=True,
+                 use_scale=False, relu_before_att=False):
+        nn.Module.__init__(self)
+        if dropout_rate > 0:
+            raise NotImplementedError("DisentangledSelfAttention(dropout_rate > 0): dropout on the attention "
+                                      "probabilities is outside the fused kernel's scope")
+        lim = ops.dsa_limits()
+        for what, n, most in (("embedding_dim", embedding_dim, lim["D_max"]),
+                              ("attention_dim", attention_dim, lim["A_max"]), ("num_heads", num_heads, lim["H_max"])):
+            if not 1 <= n <= most:
+                raise NotImplementedError("DisentangledSelfAttention: {}={}, the fused kernel's limit is "
+                                          "{} <= {}".format(what, n, what, most))
+        if attention_dim % num_heads:
+            raise ValueError("DisentangledSelfAttention: {} heads do not split an attention width of {} evenly"
+                             .format(num_heads, attention_dim))
+        dev = _alloc_device()
+        self.attention_dim, self.num_heads, self.head_dim = attention_dim, num_heads, attention_dim // num_heads
+        self.use_scale, self.relu_before_att = bool(use_scale), bool(relu_before_att)
+        self._fields_max = lim["F_max"]
+        self.W_q = nn.Linear(embedding_dim, attention_dim, device=dev)
+        self.W_k = nn.Linear(embedding_dim, attention_dim, device=dev)
+        self.W_v = nn.Linear(embedding_dim, attention_dim, device=dev)
+        self.W_unary = nn.Linear(embedding_dim, num_heads, device=dev)
+        self.W_res = nn.Linear(embedding_dim, attention_dim, device=dev) if use_residual else None
+        self.dropout = None
+
+    def forward(self, query, key, value):
+        if key is not query or value is not query:
+            raise NotImplementedError("DisentangledSelfAttention: query, key and value must be the same tensor "
+                                      "(self-attention); the fused kernel projects one input")
+        if query.dim() != 3 or query.shape[1] > self._fields_max:
+            raise NotImplementedError("DisentangledSelfAttention: input {}, the fused kernel takes [batch, "
+                                      "fields <= {}, dim]".format(tuple(query.shape), self._fields_max))
+        lin = (self.W_q, self.W_k, self.W_v, self.W_res, self.W_unary)
+        return _DSAFn.apply(query, self.num_heads, self.use_scale, self.relu_before_att,
+                            *([None if m is None else m.weight for m in lin]
+                              + [None if m is None else m.bias for m in lin]))
+
+
 class _SENetFn(torch.autograd.Function):
     """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
     three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are

@@ -1070,6 +1070,65 @@ def mhsa_bwd(X, Wq, Wk, Wv, Wres, H, use_scale, residual, relu, Y, dY, dX, dW, w
     return dX, dW
 
 
+# ---- disentangled self-attention over the fields (DESTINE, csrc/fx_dsa.hip) --------------------------
+def dsa_limits():
+    """The native envelope of dsa_fwd / dsa_bwd, stated once in the library."""
+    lim = (C.c_int32 * 6)()
+    _lib.load().fx_dsa_limits(lim)
+    return dict(zip(("F_max", "D_max", "A_max", "H_max", "fwd_workgroups", "bwd_workgroups"), (int(v) for v in lim)))
+
+
+def _dsa_flops(X, W, *a, **kw):
+    # per sample: 3 (+1) projections 2 F D A each and the unary one, scores and P V 2 F F A each
+    B, F, D = X.shape
+    A, H = W[0].shape[0], W[4].shape[0]
+    return 2.0 * B * F * (A * ((4 if W[3] is not None else 3) * D + 2 * F) + H * D)
+
+
+def dsa_grad_floats(D_in, A, H, has_wres):
+    """Floats of dsa_bwd's dW: dWq | dWk | dWv (| dWres) | dWu | dbq | dbk | dbv (| dbres) | dbu."""
+    return ((4 if has_wres else 3) * A + H) * (D_in + 1)
+
+
+def dsa_workspace_floats(B, D_in, A, H, has_wres):
+    return int(_lib.load().fx_dsa_workspace_floats(B, D_in, A, H, 1 if has_wres else 0))
+
+
+def _dsa_tables(W, bias):
+    """(Wq, Wk, Wv, Wres | None, Wunary) and their biases as the two pointer tables of fx_dsa_*."""
+    assert len(W) == 5 and len(bias) == 5 and (W[3] is None) == (bias[3] is None)
+    assert all(t is None or t.is_contiguous() for t in tuple(W) + tuple(bias))
+    return (C.c_void_p * 5)(*[ptr(t) for t in W]), (C.c_void_p * 5)(*[ptr(t) for t in bias])
+
+
+@_timed("dsa_fwd", "dsa", _dsa_flops)
+def dsa_fwd(X, W, bias, H, use_scale, relu_before_att, Y):
+    """One disentangled self-attention layer: Y [B, F, A] contiguous.  W = (Wq, Wk, Wv, Wres | None, Wunary),
+    bias alike."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    Wt, bt = _dsa_tables(W, bias)
+    check(_lib.load().fx_dsa_fwd(ptr(X), _mhsa_x(X), B, F, D, Wt, bt, W[0].shape[0], H, 1 if use_scale else 0,
+                                 1 if relu_before_att else 0, ptr(Y), stream_ptr(X.device)), "fx_dsa_fwd")
+    return Y
+
+
+@_timed("dsa_bwd", "dsa", lambda *a, **kw: 3.0 * _dsa_flops(*a, **kw))     # recompute + dX + dW passes
+def dsa_bwd(X, W, bias, H, use_scale, relu_before_att, dY, dX, dW, workspace, dx_accumulate=False):
+    """dX [B, F, D] (sample stride free); dW: dsa_grad_floats(.) floats in that order; dY contiguous."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    A = W[0].shape[0]
+    assert dY.is_contiguous() and dW.is_contiguous() and dW.numel() >= dsa_grad_floats(D, A, H, W[3] is not None)
+    assert workspace.numel() >= dsa_workspace_floats(B, D, A, H, W[3] is not None)
+    Wt, bt = _dsa_tables(W, bias)
+    check(_lib.load().fx_dsa_bwd(ptr(X), _mhsa_x(X), B, F, D, Wt, bt, A, H, 1 if use_scale else 0,
+                                 1 if relu_before_att else 0, ptr(dY), ptr(dX), _mhsa_x(dX),
+                                 1 if dx_accumulate else 0, ptr(dW), ptr(workspace), stream_ptr(X.device)),
+          "fx_dsa_bwd")
+    return dX, dW
+
+
 # ---- FiBiNET: squeeze-excitation and bilinear interaction -------------------------------------------
 BILINEAR_MAX = 64    # F, D (and the excitation's hidden width) of fx_senet_* / fx_bilinear_*
 BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}

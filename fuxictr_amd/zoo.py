@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN and FiGNN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN and DESTINE, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -11,7 +11,8 @@ model_zoo/DCN/DCN_torch/src/DCN.py:24-101, model_zoo/FwFM/src/FwFM.py:24-91,
 model_zoo/FmFM/src/FmFM.py:25-94,
 model_zoo/BST/src/BST.py:33-366,
 model_zoo/DIEN/src/DIEN.py:27-503,
-model_zoo/FiGNN/src/FiGNN.py:27-231), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/FiGNN/src/FiGNN.py:27-231,
+model_zoo/DESTINE/src/DESTINE.py:37-227), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -21,7 +22,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice,
+from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -849,6 +850,52 @@ class FiGNN(_ZooModel):
         h_out = self.fignn(feature_emb)
         y_pred = self.fc(h_out)
         return {"y_pred": self.output_activation(y_pred)}
+
+
+class DESTINE(_ZooModel):
+    """Disentangled Self-Attentive Neural Network (DESTINE.py:37-140): a stack of layers.DisentangledSelfAttention
+    (one launch per direction each) under a linear head, next to the wide part and the deep tower."""
+
+    def __init__(self, feature_map, model_id="DESTINE", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 attention_dim=16, num_heads=2, attention_layers=2, dnn_hidden_units=[], dnn_activations="ReLU",
+                 net_dropout=0.1, att_dropout=0.1, relu_before_att=False, batch_norm=False, use_scale=False,
+                 use_wide=True, residual_mode="each_layer", embedding_regularizer=None, net_regularizer=None,
+                 **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        if residual_mode not in ("each_layer", "last_layer", None):
+            raise ValueError("DESTINE: residual_mode={!r} ('each_layer', 'last_layer' or None)".format(residual_mode))
+        fields_max = ops.dsa_limits()["F_max"]
+        if feature_map.num_fields > fields_max:
+            raise NotImplementedError("DESTINE: {} fields, the fused self-attention takes fields <= {}"
+                                      .format(feature_map.num_fields, fields_max))
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.lr = LogisticRegression(feature_map) if use_wide else None
+        self.dnn = self._tower(feature_map.num_fields * embedding_dim, dnn_hidden_units, dnn_activations,
+                               net_dropout, batch_norm) if dnn_hidden_units else None
+        # (att_dropout > 0 raises in the layer: dropout on the attention weights is outside the kernel)
+        self.self_attns = nn.ModuleList([
+            DisentangledSelfAttention(embedding_dim if i == 0 else attention_dim, attention_dim, num_heads,
+                                      att_dropout, residual_mode == "each_layer", use_scale, relu_before_att)
+            for i in range(attention_layers)])
+        self.attn_fc = FxLinear(feature_map.num_fields * attention_dim, 1, device=self.device)
+        self.W_res = FxLinear(embedding_dim, attention_dim, device=self.device) \
+            if residual_mode == "last_layer" else None
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        cross_X = feature_emb
+        for self_attn in self.self_attns:
+            cross_X = self_attn(cross_X, cross_X, cross_X)  # [B, F, A]
+        if self.W_res is not None:                          # += in the GEMM's epilogue
+            cross_X = self.W_res(feature_emb, out_add=cross_X.reshape(-1, cross_X.shape[-1]))
+        # attention head + wide part (+ deep tower): the sums ride in the GEMM epilogues
+        logit = self.lr(X) if self.lr is not None else None
+        logit = self.attn_fc(cross_X.flatten(start_dim=1), out_add=logit)
+        if self.dnn is not None:
+            logit = self.dnn(feature_emb.flatten(start_dim=1), out_add=logit)
+        return {"y_pred": self.output_activation(logit)}
 
 
 def _flat_len(fields):

@@ -699,6 +699,35 @@ int fx_mhsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in
                 float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DESTINE's disentangled self-attention over the fields of a sample, one layer per launch (csrc/fx_dsa.hip;
+ * DisentangledSelfAttention.forward, model_zoo/DESTINE/src/DESTINE.py:179-227; its autograd at rank_model.py:320).
+ * W and bias are host arrays of five device pointers, in the order q, k, v, res, unary: W[0..3] [A, D_in],
+ * W[4] [H, D_in], bias[0..3] [A], bias[4] [H]; W[3] and bias[3] are both NULL without a residual.
+ *     q = X Wq^T + bq, k, v alike (relu(.) when relu_before_att);  u = X Wu^T + bu;  us = softmax_fields(u)
+ *     heads by the reference's flat view(B H, -1, A / H), no transpose: token t of a sample is field t / H, columns
+ *     (t % H) hd .. + hd; group g is tokens g F .. g F + F - 1.  Per group: Q~ = Q - mean_rows(Q), K~ alike,
+ *     P = softmax_rows(Q~ K~^T (/ sqrt(hd) when use_scale)), O_i = sum_j (P_ij + us_j) V_j
+ *     Y = O back through the token map (+ X Wres^T + bres)            Y: [B, F, A] contiguous
+ * Nothing but Y reaches memory, and the backward keeps nothing but X.
+ *   fx_dsa_bwd  : from dY [B, F, A]: dX [B, F, D_in] (sample stride dx_ld; added to when dx_accumulate) and
+ *                 dW = [dWq | dWk | dWv (| dWres) | dWu | dbq | dbk | dbv (| dbres) | dbu], (3 | 4) A D_in + H D_in +
+ *                 (3 | 4) A + H floats.  Summed per workgroup into workspace, reduced in a fixed order by a second
+ *                 launch (deterministic, no atomics).
+ *   fx_dsa_limits : limits[6] = {most F, most D_in, most A, most H, most workgroups forward, backward}: the native
+ *                 envelope (housekeeping); a shape outside it is FX_ERR_INVALID, never a launch.
+ * workspace: fx_dsa_workspace_floats(B, D_in, A, H, Wres != NULL) floats.  H divides A.
+ * ------------------------------------------------------------------------------------------ */
+void fx_dsa_limits(int32_t* limits);
+int64_t fx_dsa_workspace_floats(int64_t B, int32_t D_in, int32_t A, int32_t H, int32_t has_wres);
+int fx_dsa_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in, const float* const* W,
+               const float* const* bias, int32_t A, int32_t H, int32_t use_scale, int32_t relu_before_att,
+               float* Y, fx_stream_t stream);
+int fx_dsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in, const float* const* W,
+               const float* const* bias, int32_t A, int32_t H, int32_t use_scale, int32_t relu_before_att,
+               const float* dY, float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dW, float* workspace,
+               fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * FiBiNET's squeeze-excitation over the fields of a sample (SqueezeExcitation.forward,
  * fuxictr/pytorch/layers/attentions/squeeze_excitation.py:51-64; its autograd at rank_model.py:320):
  *     Z[b,f] = mean_d X[b,f,d]                      X: [B, F, D] (sample stride x_ld)
