@@ -153,6 +153,12 @@ SIGNATURES = {
     "fx_dsa_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
     "fx_dsa_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "fx_dsa_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp]),
+    "fx_lognet_limits": (None, [vp]),
+    "fx_lognet_workspace_floats": (i64, [i64, i32, i32, i32]),
+    "fx_lognet_fwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp,
+                            vp, vp, vp, vp]),
+    "fx_lognet_bwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, vp, vp, C.c_float, vp, vp, vp, i64, i32, vp, vp, vp, vp,
+                            vp, vp, vp]),
     "fx_senet_workspace_floats": (i64, [i64, i32, i32]),
     "fx_senet_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
     "fx_senet_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),

@@ -3161,6 +3161,64 @@ class DisentangledSelfAttention(nn.Module):
                               + [None if m is None else m.bias for m in lin]))
 
 
+class _LogNetFn(torch.autograd.Function):
+    """AFN's logarithmic net as ONE autograd node (AFN.py:121-138; ops.lognet_fwd / lognet_bwd).  Kept for the
+    backward: x and the 2 (F + L) batch statistics; exp(.) [B, L, D] is recomputed, never stored."""
+
+    @staticmethod
+    def forward(ctx, x, W, gamma1, beta1, gamma2, beta2, log_bn, exp_bn, training):
+        if x.stride(2) != 1 or (x.shape[1] > 1 and x.stride(1) != x.shape[2]):
+            x = x.contiguous()
+        B, F, D = x.shape
+        L = W.shape[0]
+        if log_bn.momentum is None or log_bn.momentum != exp_bn.momentum or log_bn.eps != exp_bn.eps:
+            raise NotImplementedError("logarithmic_net: the fused kernel takes one eps and one (not None) momentum "
+                                      "for both BatchNorm1d")
+        y = torch.empty(B, L * D, dtype=torch.float32, device=x.device)
+        stats = torch.empty(ops.lognet_stats_floats(F, L), dtype=torch.float32, device=x.device) if training else None
+        ws = _Workspace.get(x.device, ops.lognet_workspace_floats(B, F, D, L), tag="lognet") if training else None
+        ops.lognet_fwd(x, W, gamma1, beta1, gamma2, beta2, log_bn.eps, log_bn.momentum, training,
+                       (log_bn.running_mean, log_bn.running_var, log_bn.num_batches_tracked),
+                       (exp_bn.running_mean, exp_bn.running_var, exp_bn.num_batches_tracked), stats, y, ws)
+        ctx.x, ctx.w, ctx.affine, ctx.stats, ctx.eps = x, W, (gamma1, beta1, gamma2), stats, log_bn.eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W, (gamma1, beta1, gamma2), stats = ctx.x, ctx.w, ctx.affine, ctx.stats
+        if stats is None:
+            raise NotImplementedError("logarithmic_net: the backward of the eval-mode forward (running statistics) "
+                                      "has no kernel")
+        B, F, D = x.shape
+        L = W.shape[0]
+        dx = torch.empty(B, F, D, dtype=torch.float32, device=x.device)
+        dW = torch.empty(L, F, dtype=torch.float32, device=x.device)
+        d1 = torch.empty(2, F, dtype=torch.float32, device=x.device)
+        d2 = torch.empty(2, L, dtype=torch.float32, device=x.device)
+        ws = _Workspace.get(x.device, ops.lognet_workspace_floats(B, F, D, L), tag="lognet")
+        ops.lognet_bwd(x, W, gamma1, beta1, gamma2, ctx.eps, stats, dy.contiguous(), dx, dW, d1[0], d1[1], d2[0],
+                       d2[1], ws)
+        return dx, dW, d1[0], d1[1], d2[0], d2[1], None, None, None
+
+
+def logarithmic_net(feature_emb, coefficient_W, log_batch_norm, exp_batch_norm, training):
+    """AFN.logarithmic_net (model_zoo/AFN/src/AFN.py:121-138): [B, F, D] -> [B, L * D].  coefficient_W is the
+    bias-free nn.Linear(F, L), the two nn.BatchNorm1d hold the affine pairs and the running buffers, which the
+    kernel updates.  On the GPU the layer is fx_lognet_*; a CPU tensor takes the reference's own torch ops."""
+    if feature_emb.is_cuda:
+        return _LogNetFn.apply(feature_emb, coefficient_W.weight, log_batch_norm.weight, log_batch_norm.bias,
+                               exp_batch_norm.weight, exp_batch_norm.bias, log_batch_norm, exp_batch_norm,
+                               bool(training))
+    feature_emb = torch.abs(feature_emb)
+    feature_emb = torch.clamp(feature_emb, min=1e-5)
+    log_feature_emb = torch.log(feature_emb)
+    log_feature_emb = log_batch_norm(log_feature_emb)
+    logarithmic_out = coefficient_W(log_feature_emb.transpose(2, 1)).transpose(1, 2)
+    cross_out = torch.exp(logarithmic_out)
+    cross_out = exp_batch_norm(cross_out)
+    return torch.flatten(cross_out, start_dim=1)
+
+
 class _SENetFn(torch.autograd.Function):
     """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
     three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are

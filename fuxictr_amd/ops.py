@@ -1129,6 +1129,64 @@ def dsa_bwd(X, W, bias, H, use_scale, relu_before_att, dY, dX, dW, workspace, dx
     return dX, dW
 
 
+# ---- AFN's logarithmic transformation layer (csrc/fx_lognet.hip) -----------------------------------
+def lognet_limits():
+    """The native envelope of lognet_fwd / lognet_bwd, stated once in the library.  tile_columns: the (sample, d)
+    columns of a workgroup tile; workgroups: the most a column kernel launches."""
+    lim = (C.c_int32 * 6)()
+    _lib.load().fx_lognet_limits(lim)
+    return dict(zip(("F_max", "D_max", "L_max", "tile_columns", "workgroups", "stat_chunks"), (int(v) for v in lim)))
+
+
+def _lognet_flops(X, W, *a, **kw):
+    B, F, D = X.shape
+    return 2.0 * B * D * W.shape[0] * F
+
+
+def lognet_workspace_floats(B, F, D, L):
+    return int(_lib.load().fx_lognet_workspace_floats(B, F, D, L))
+
+
+def lognet_stats_floats(F, L):
+    """Floats of the batch statistics lognet_fwd leaves for lognet_bwd: mean1 | var1 [F], mean2 | var2 [L]."""
+    return 2 * (F + L)
+
+
+@_timed("lognet_fwd", "lognet", lambda *a, **kw: 2.0 * _lognet_flops(*a, **kw))     # statistics pass + output pass
+def lognet_fwd(X, W, gamma1, beta1, gamma2, beta2, eps, momentum, training, running1, running2, stats, Y,
+               workspace):
+    """Y [B, L * D] = BN_exp(exp(W . BN_log(log(max(|X|, 1e-5))))), X [B, F, D] (sample stride free), W [L, F].
+    running1 / running2: (running_mean, running_var, num_batches_tracked) of the two BatchNorm1d, updated in
+    training; stats (lognet_stats_floats) is written in training only, where workspace is needed too."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    L = W.shape[0]
+    assert W.is_contiguous() and W.shape[1] == F and Y.is_contiguous() and Y.numel() == B * L * D
+    assert not training or (stats.numel() >= lognet_stats_floats(F, L)
+                            and workspace.numel() >= lognet_workspace_floats(B, F, D, L))
+    check(_lib.load().fx_lognet_fwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W), L, ptr(gamma1), ptr(beta1), ptr(gamma2),
+                                    ptr(beta2), eps, momentum, 1 if training else 0, *[ptr(t) for t in running1],
+                                    *[ptr(t) for t in running2], ptr(stats) if training else None, ptr(Y),
+                                    ptr(workspace) if training else None, stream_ptr(X.device)), "fx_lognet_fwd")
+    return Y
+
+
+@_timed("lognet_bwd", "lognet", lambda *a, **kw: 5.0 * _lognet_flops(*a, **kw))     # 3 recomputes, dahat, dW
+def lognet_bwd(X, W, gamma1, beta1, gamma2, eps, stats, dY, dX, dW, dgamma1, dbeta1, dgamma2, dbeta2, workspace,
+               dx_accumulate=False):
+    """The training-mode backward: dX [B, F, D] (sample stride free), dW [L, F], the four affine gradients."""
+    _need_cuda(X, "X")
+    B, F, D = X.shape
+    L = W.shape[0]
+    assert dY.is_contiguous() and dY.numel() == B * L * D and dW.is_contiguous()
+    assert workspace.numel() >= lognet_workspace_floats(B, F, D, L)
+    check(_lib.load().fx_lognet_bwd(ptr(X), _mhsa_x(X), B, F, D, ptr(W), L, ptr(gamma1), ptr(beta1), ptr(gamma2),
+                                    eps, ptr(stats), ptr(dY), ptr(dX), _mhsa_x(dX), 1 if dx_accumulate else 0,
+                                    ptr(dW), ptr(dgamma1), ptr(dbeta1), ptr(dgamma2), ptr(dbeta2), ptr(workspace),
+                                    stream_ptr(X.device)), "fx_lognet_bwd")
+    return dX, dW
+
+
 # ---- FiBiNET: squeeze-excitation and bilinear interaction -------------------------------------------
 BILINEAR_MAX = 64    # F, D (and the excitation's hidden width) of fx_senet_* / fx_bilinear_*
 BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN and DESTINE, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE and AFN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -12,7 +12,8 @@ model_zoo/FmFM/src/FmFM.py:25-94,
 model_zoo/BST/src/BST.py:33-366,
 model_zoo/DIEN/src/DIEN.py:27-503,
 model_zoo/FiGNN/src/FiGNN.py:27-231,
-model_zoo/DESTINE/src/DESTINE.py:37-227), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/DESTINE/src/DESTINE.py:37-227,
+model_zoo/AFN/src/AFN.py:25-138), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -26,7 +27,7 @@ from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
-                     _FMFn, afm_attention, afm_attention_native, pair_interaction, pair_interaction_native, side_by_side,
+                     _FMFn, afm_attention, afm_attention_native, logarithmic_net, pair_interaction, pair_interaction_native, side_by_side,
                      tower_pad)
 from . import ops
 from .rank_model import BaseModel
@@ -896,6 +897,53 @@ class DESTINE(_ZooModel):
         if self.dnn is not None:
             logit = self.dnn(feature_emb.flatten(start_dim=1), out_add=logit)
         return {"y_pred": self.output_activation(logit)}
+
+
+class AFN(_ZooModel):
+    """Adaptive Factorization Network (AFN.py:25-138): the logarithmic transformation layer (layers.logarithmic_net,
+    csrc/fx_lognet.hip) under a tower, optionally ensembled with a plain DNN on a second embedding layer.  The
+    reference keeps the layer as a method of the model, so its parameters sit on the model itself:
+    `coefficient_W`, `log_batch_norm`, `exp_batch_norm` (parameter and buffer holders; the kernel does the
+    arithmetic and the running update)."""
+
+    def __init__(self, feature_map, model_id="AFN", gpu=-1, learning_rate=1e-3, embedding_dim=10, ensemble_dnn=True,
+                 dnn_hidden_units=[64, 64, 64], dnn_activations="ReLU", dnn_dropout=0,
+                 afn_hidden_units=[64, 64, 64], afn_activations="ReLU", afn_dropout=0, logarithmic_neurons=5,
+                 batch_norm=True, embedding_regularizer=None, net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        lim = ops.lognet_limits()
+        for what, n, most in (("num_fields", feature_map.num_fields, lim["F_max"]),
+                              ("embedding_dim", embedding_dim, lim["D_max"]),
+                              ("logarithmic_neurons", logarithmic_neurons, lim["L_max"])):
+            if not 1 <= n <= most:
+                raise NotImplementedError("AFN: {}={}, the fused logarithmic net takes 1 <= {} <= {}"
+                                          .format(what, n, what, most))
+        self.num_fields = feature_map.num_fields
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.coefficient_W = nn.Linear(self.num_fields, logarithmic_neurons, bias=False)
+        self.dense_layer = self._tower(embedding_dim * logarithmic_neurons, afn_hidden_units, afn_activations,
+                                       afn_dropout, batch_norm)
+        self.log_batch_norm = nn.BatchNorm1d(self.num_fields)
+        self.exp_batch_norm = nn.BatchNorm1d(logarithmic_neurons)
+        self.ensemble_dnn = ensemble_dnn
+        if ensemble_dnn:
+            self.embedding_layer2 = FeatureEmbedding(feature_map, embedding_dim)
+            self.dnn = self._tower(embedding_dim * self.num_fields, dnn_hidden_units, dnn_activations, dnn_dropout,
+                                   batch_norm)
+            self.fc = nn.Linear(2, 1)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        dnn_input = logarithmic_net(feature_emb, self.coefficient_W, self.log_batch_norm, self.exp_batch_norm,
+                                    self.training)          # [B, L * D]
+        y_pred = self.dense_layer(dnn_input)
+        if self.ensemble_dnn:
+            feature_emb2 = self.embedding_layer2(X)
+            dnn_out = self.dnn(feature_emb2.flatten(start_dim=1))
+            y_pred = self.fc(torch.cat([y_pred, dnn_out], dim=-1))
+        return {"y_pred": self.output_activation(y_pred)}
 
 
 def _flat_len(fields):

@@ -728,6 +728,39 @@ int fx_dsa_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D_in,
                fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AFN's logarithmic transformation layer (csrc/fx_lognet.hip; AFN.logarithmic_net, model_zoo/AFN/src/AFN.py:121-138).
+ * X [B, F, D] (unit stride over d, D over f, sample stride x_ld), W [L, F] = coefficient_W.weight:
+ *     a = log(max(|x|, 1e-5));  ahat = BN_log(a): BatchNorm1d(F), affine gamma1 / beta1, statistics over the B D
+ *     elements of a field;  u[b, l, d] = sum_f W[l, f] ahat[b, f, d];  c = exp(u);
+ *     Y[b, l D + d] = BN_exp(c): BatchNorm1d(L), affine gamma2 / beta2                  Y: [B, L D] contiguous
+ * Both BatchNorms: the given eps and momentum, biased batch variance for normalising, unbiased for running_var,
+ * num_batches_tracked += 1 per training forward (nn.BatchNorm1d).  c [B, L, D] never reaches memory: it is
+ * recomputed on the matrix cores wherever it is needed.
+ *   fx_lognet_fwd : training != 0: five launches (BN_log statistics merged per chunk by Chan's formula, BN_exp
+ *                 statistics about the pivot exp(W beta1), output); stats[2 F + 2 L] = [mean1 | var1 | mean2 | var2]
+ *                 (biased) is written for the backward and the running buffers are updated.  B D = 1 is
+ *                 FX_ERR_INVALID, as torch refuses it.  training == 0: one launch on the running statistics; stats,
+ *                 workspace and the counters may be NULL and nothing but Y is written.
+ *   fx_lognet_bwd : the training-mode backward from dY [B, L D] contiguous and the forward's stats: dX (sample stride
+ *                 dx_ld; added to when dx_accumulate; exactly 0 where |x| < 1e-5), dW [L, F], dgamma1 / dbeta1 [F],
+ *                 dgamma2 / dbeta2 [L].  Eight launches, every reduce in a fixed order, no atomics.
+ *   fx_lognet_limits : limits[6] = {most F, most D, most L, columns (b, d) per workgroup tile, most workgroups of
+ *                 a column kernel, most chunks of the per-field statistics}; a shape outside is FX_ERR_INVALID.
+ * workspace: fx_lognet_workspace_floats(B, F, D, L) floats (0 outside the envelope), for either direction.
+ * ------------------------------------------------------------------------------------------ */
+void fx_lognet_limits(int32_t* limits);
+int64_t fx_lognet_workspace_floats(int64_t B, int32_t F, int32_t D, int32_t L);
+int fx_lognet_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W, int32_t L,
+                  const float* gamma1, const float* beta1, const float* gamma2, const float* beta2, float eps,
+                  float momentum, int32_t training, float* running_mean1, float* running_var1,
+                  int64_t* num_batches_tracked1, float* running_mean2, float* running_var2,
+                  int64_t* num_batches_tracked2, float* stats, float* Y, float* workspace, fx_stream_t stream);
+int fx_lognet_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, const float* W, int32_t L,
+                  const float* gamma1, const float* beta1, const float* gamma2, float eps, const float* stats,
+                  const float* dY, float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dW, float* dgamma1,
+                  float* dbeta1, float* dgamma2, float* dbeta2, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * FiBiNET's squeeze-excitation over the fields of a sample (SqueezeExcitation.forward,
  * fuxictr/pytorch/layers/attentions/squeeze_excitation.py:51-64; its autograd at rank_model.py:320):
  *     Z[b,f] = mean_d X[b,f,d]                      X: [B, F, D] (sample stride x_ld)
