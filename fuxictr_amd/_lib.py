@@ -159,6 +159,13 @@ SIGNATURES = {
                             vp, vp, vp, vp]),
     "fx_lognet_bwd": (i32, [vp, i64, i64, i32, i32, vp, i32, vp, vp, vp, C.c_float, vp, vp, vp, i64, i32, vp, vp, vp, vp,
                             vp, vp, vp]),
+    "fx_euler_limits": (None, [vp]),
+    "fx_euler_workspace_floats": (i64, [i64, i32, i32, i32]),
+    "fx_euler_polar_fwd": (i32, [vp, i64, vp, i64, i32, i32, vp, vp]),
+    "fx_euler_polar_bwd": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, i64, vp, vp, vp]),
+    "fx_euler_fwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp]),
+    "fx_euler_bwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp,
+                           vp, vp]),
     "fx_senet_workspace_floats": (i64, [i64, i32, i32]),
     "fx_senet_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
     "fx_senet_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),

@@ -3219,6 +3219,156 @@ def logarithmic_net(feature_emb, coefficient_W, log_batch_norm, exp_batch_norm, 
     return torch.flatten(cross_out, start_dim=1)
 
 
+class _EulerPolarFn(torch.autograd.Function):
+    """EulerNet's polar front end as ONE autograd node (EulerNet.py:90): RP [2, B, F, D] = mu (cos E | sin E).  Forward
+    one launch, backward two (dE and the chunk partials of dmu, then their fixed-order sum)."""
+
+    @staticmethod
+    def forward(ctx, E, mu):
+        if E.stride(2) != 1 or (E.shape[1] > 1 and E.stride(1) != E.shape[2]):
+            E = E.contiguous()
+        B, F, D = E.shape
+        RP = torch.empty(2, B, F, D, dtype=torch.float32, device=E.device)
+        ops.euler_polar_fwd(E, mu, RP)
+        ctx.E, ctx.mu = E, mu
+        return RP
+
+    @staticmethod
+    def backward(ctx, dRP):
+        E, mu = ctx.E, ctx.mu
+        B, F, D = E.shape
+        dE = torch.empty(B, F, D, dtype=torch.float32, device=E.device)
+        dmu = torch.empty_like(mu)
+        ws = _Workspace.get(E.device, ops.euler_workspace_floats(B, F, D, 1), tag="euler")
+        ops.euler_polar_bwd(E, mu, dRP.contiguous(), dE, dmu, ws)
+        return dE, dmu
+
+
+def euler_polar(feature_emb, mu):
+    """EulerNet.forward's r, p = mu cos(E), mu sin(E) (EulerNet.py:90).  On the GPU one tensor RP [2, B, F, D]
+    (fx_euler_polar_*); a CPU tensor takes the reference's torch ops and gives the pair (r, p)."""
+    if feature_emb.is_cuda:
+        return _EulerPolarFn.apply(feature_emb, mu)
+    return mu * torch.cos(feature_emb), mu * torch.sin(feature_emb)
+
+
+class _EulerLayerFn(torch.autograd.Function):
+    """One Euler interaction layer as ONE autograd node (EulerNet.py:139-170) on the pair RP [2, B, Fi, D].  Forward:
+    the dense path Z = X im.weight^T + im.bias as one GEMM over 2 B rows (X = RP, or its dropped-out copy), then
+    fx_euler_fwd.  Kept for the backward: RP, X, Z and the groups' (mean, rstd); exp / cos / sin are recomputed.
+    Backward: fx_euler_bwd (dZ, the explicit part of dRP, the small gradients), then the dense path's two products in
+    one launch, dRP += dZ im.weight in its epilogue."""
+
+    @staticmethod
+    def forward(ctx, RP, Xd, orders, W, b, bias_lam, bias_theta, wr, br, wp, bp, apply_norm, eps):
+        RP = RP.contiguous()
+        _, B, Fi, D = RP.shape
+        O = orders.shape[1]
+        X2 = (RP if Xd is None else Xd.contiguous()).view(2 * B, Fi * D)
+        Z = torch.empty(2 * B, O * D, dtype=torch.float32, device=RP.device)
+        ops.gemm(X2, W, Z, transa=False, transb=True, bias=b, act=0)
+        OP = torch.empty(2, B, O, D, dtype=torch.float32, device=RP.device)
+        stats = torch.empty(4, B, O, dtype=torch.float32, device=RP.device) if apply_norm else None
+        ops.euler_fwd(RP, Z, orders, bias_lam, bias_theta, (wr, br, wp, bp) if apply_norm else None, eps, stats, OP)
+        ctx.kept = (RP, X2, Z, stats, orders, W, bias_lam, bias_theta, wr, wp)
+        ctx.cfg = (apply_norm, eps, Xd is not None, b is not None)
+        return OP
+
+    @staticmethod
+    def backward(ctx, dOP):
+        RP, X2, Z, stats, orders, W, bias_lam, bias_theta, wr, wp = ctx.kept
+        apply_norm, eps, dropped, has_bias = ctx.cfg
+        _, B, Fi, D = RP.shape
+        O = orders.shape[1]
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=RP.device)    # noqa: E731
+        dZ, dRP, d_orders, d_bias = new(2 * B, O * D), new(2, B, Fi, D), new(Fi, O), new(2, 1, D, O)
+        d_norm = new(2, 2, D) if apply_norm else None
+        ws = _Workspace.get(RP.device, ops.euler_workspace_floats(B, Fi, D, O), tag="euler")
+        ops.euler_bwd(RP, Z, orders, bias_lam, bias_theta, (wr, wp) if apply_norm else None, eps, stats,
+                      dOP.contiguous(), dZ, dRP, d_orders, d_bias, d_norm, ws)
+        dW, db, dX = linear_grads(dZ, X2, W, has_bias, add=None if dropped else dRP.view(2 * B, Fi * D))
+        dX = dX.view(2, B, Fi, D)
+        dn = (d_norm[0, 0], d_norm[0, 1], d_norm[1, 0], d_norm[1, 1]) if apply_norm else (None,) * 4
+        return (dRP if dropped else dX, dX if dropped else None, d_orders, dW, db, d_bias[0], d_bias[1]) + dn \
+            + (None, None)
+
+
+class EulerInteractionLayer(nn.Module):
+    """EulerNet's Euler interaction layer (model_zoo/EulerNet/src/EulerNet.py:100-170), the reference's parameter
+    names and initialisers.  On the GPU the layer works on the pair as one tensor RP [2, B, Fi, D] -> [2, B, O, D]
+    (_EulerLayerFn: the dense path on the GEMM, everything else in csrc/fx_euler.hip); a pair (r, p) is taken and given
+    back as a pair.  CPU tensors take the reference's own sequence of torch ops.  `net_im_dropout` is an ordinary
+    nn.Dropout on the GEMM's input; `net_ex_dropout` > 0 (dropout on log-modulus and phase) has no kernel."""
+
+    def __init__(self, inshape, outshape, embedding_dim, apply_norm, net_ex_dropout, net_im_dropout):
+        super().__init__()
+        if net_ex_dropout and net_ex_dropout > 0:
+            raise NotImplementedError("EulerInteractionLayer: net_ex_dropout={} (dropout on the log-modulus and the "
+                                      "phase) is outside the fused kernel; use 0".format(net_ex_dropout))
+        self.inshape, self.outshape = int(inshape), int(outshape)
+        self.feature_dim = embedding_dim
+        self.apply_norm = apply_norm
+        fi, o = self.inshape // embedding_dim, self.outshape // embedding_dim
+        lim = ops.euler_limits()
+        for what, n, most in (("inshape / embedding_dim", fi, lim["F_max"]), ("embedding_dim", embedding_dim, lim["D_max"]),
+                              ("outshape / embedding_dim", o, lim["O_max"])):
+            if not 1 <= n <= most:
+                raise NotImplementedError("EulerInteractionLayer: {}={}, the fused Euler interaction takes 1 <= {} <= {}"
+                                          .format(what, n, what, most))
+        if inshape == outshape:
+            init_orders = torch.eye(fi, o)
+        else:
+            init_orders = torch.softmax(torch.randn(fi, o) / 0.01, dim=0)
+        self.inter_orders = nn.Parameter(init_orders)
+        self.im = nn.Linear(self.inshape, self.outshape)
+        nn.init.xavier_uniform_(self.im.weight)
+        self.bias_lam = nn.Parameter(torch.randn(1, embedding_dim, o) * 0.01)
+        self.bias_theta = nn.Parameter(torch.randn(1, embedding_dim, o) * 0.01)
+        self.drop_ex = nn.Dropout(p=net_ex_dropout)
+        self.drop_im = nn.Dropout(p=net_im_dropout)
+        self.norm_r = nn.LayerNorm([embedding_dim])
+        self.norm_p = nn.LayerNorm([embedding_dim])
+
+    def _reference(self, r, p):
+        D = self.feature_dim
+        lam = r ** 2 + p ** 2 + 1e-8
+        theta = torch.atan2(p, r)
+        lam, theta = lam.reshape(lam.shape[0], -1, D), theta.reshape(theta.shape[0], -1, D)
+        lam = 0.5 * torch.log(lam)
+        lam, theta = torch.transpose(lam, -2, -1), torch.transpose(theta, -2, -1)
+        lam, theta = lam @ self.inter_orders + self.bias_lam, theta @ self.inter_orders + self.bias_theta
+        lam = torch.exp(lam)
+        lam, theta = torch.transpose(lam, -2, -1), torch.transpose(theta, -2, -1)
+        r, p = r.reshape(r.shape[0], -1), p.reshape(p.shape[0], -1)
+        r, p = self.drop_im(r), self.drop_im(p)
+        r, p = self.im(r), self.im(p)
+        r, p = torch.relu(r), torch.relu(p)
+        r, p = r.reshape(r.shape[0], -1, D), p.reshape(p.shape[0], -1, D)
+        o_r, o_p = r + lam * torch.cos(theta), p + lam * torch.sin(theta)
+        if self.apply_norm:
+            o_r, o_p = self.norm_r(o_r), self.norm_p(o_p)
+        return o_r, o_p
+
+    def _native(self, RP):
+        D = self.feature_dim
+        RP = RP.reshape(2, RP.shape[1], -1, D)
+        dropped = self.drop_im(RP) if (self.training and self.drop_im.p > 0) else None
+        return _EulerLayerFn.apply(RP, dropped, self.inter_orders, self.im.weight, self.im.bias, self.bias_lam,
+                                   self.bias_theta, self.norm_r.weight, self.norm_r.bias, self.norm_p.weight,
+                                   self.norm_p.bias, bool(self.apply_norm), self.norm_r.eps)
+
+    def forward(self, complex_features):
+        if isinstance(complex_features, (tuple, list)):
+            r, p = complex_features
+            if not r.is_cuda:
+                return self._reference(r, p)
+            OP = self._native(torch.stack((r, p)))
+            return OP[0], OP[1]
+        if not complex_features.is_cuda:
+            return torch.stack(self._reference(complex_features[0], complex_features[1]))
+        return self._native(complex_features)
+
+
 class _SENetFn(torch.autograd.Function):
     """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
     three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are

@@ -1187,6 +1187,92 @@ def lognet_bwd(X, W, gamma1, beta1, gamma2, eps, stats, dY, dX, dW, dgamma1, dbe
     return dX, dW
 
 
+# ---- EulerNet's Euler interaction layer and polar front end (csrc/fx_euler.hip) ----------------------
+def euler_limits():
+    """The native envelope of euler_fwd / euler_bwd / euler_polar_*, stated once in the library.  tile_columns /
+    tile_samples: the most (sample, d) columns and samples of a workgroup tile; workgroups: the most a layer kernel
+    launches."""
+    lim = (C.c_int32 * 8)()
+    _lib.load().fx_euler_limits(lim)
+    return dict(zip(("F_max", "D_max", "O_max", "tile_columns", "tile_samples", "workgroups", "slabs",
+                     "polar_chunks"), (int(v) for v in lim)))
+
+
+def _euler_flops(RP, Z, orders, *a, **kw):
+    _, B, Fi, D = RP.shape
+    return 4.0 * B * D * orders.shape[1] * Fi
+
+
+def euler_workspace_floats(B, Fi, D, O):
+    return int(_lib.load().fx_euler_workspace_floats(B, Fi, D, O))
+
+
+def euler_polar_fwd(E, mu, RP):
+    """RP [2, B, F, D] = mu (cos E | sin E); E [B, F, D] (sample stride free), mu: F floats."""
+    _need_cuda(E, "E")
+    B, F, D = E.shape
+    assert RP.is_contiguous() and RP.numel() == 2 * B * F * D and mu.is_contiguous() and mu.numel() == F
+    check(_lib.load().fx_euler_polar_fwd(ptr(E), _mhsa_x(E), ptr(mu), B, F, D, ptr(RP), stream_ptr(E.device)),
+          "fx_euler_polar_fwd")
+    return RP
+
+
+def euler_polar_bwd(E, mu, dRP, dE, dmu, workspace):
+    """dE [B, F, D] (sample stride free) and dmu (F floats) from dRP [2, B, F, D]."""
+    _need_cuda(E, "E")
+    B, F, D = E.shape
+    assert dRP.is_contiguous() and dRP.numel() == 2 * B * F * D and dmu.is_contiguous() and dmu.numel() == F
+    assert workspace.numel() >= euler_workspace_floats(B, F, D, 1)
+    check(_lib.load().fx_euler_polar_bwd(ptr(E), _mhsa_x(E), ptr(mu), B, F, D, ptr(dRP), ptr(dE), _mhsa_x(dE),
+                                         ptr(dmu), ptr(workspace), stream_ptr(E.device)), "fx_euler_polar_bwd")
+    return dE, dmu
+
+
+def _euler_shapes(RP, Z, orders, bias_lam, bias_theta):
+    _, B, Fi, D = RP.shape
+    O = orders.shape[1]
+    assert RP.shape[0] == 2 and RP.is_contiguous() and Z.is_contiguous() and Z.numel() == 2 * B * O * D
+    assert orders.is_contiguous() and orders.shape[0] == Fi
+    assert bias_lam.is_contiguous() and bias_theta.is_contiguous() and bias_lam.numel() == bias_theta.numel() == D * O
+    return B, Fi, D, O
+
+
+@_timed("euler_fwd", "euler", _euler_flops)
+def euler_fwd(RP, Z, orders, bias_lam, bias_theta, norms, eps, stats, OP):
+    """OP [2, B, O, D] from RP [2, B, Fi, D] and the dense path's pre-activation Z [2 B, O D].  norms: None, or
+    (norm_r.weight, norm_r.bias, norm_p.weight, norm_p.bias) for the LayerNorm over D; stats [4, B, O] (mean | rstd of
+    the groups) is written when given and the norm is on."""
+    _need_cuda(RP, "RP")
+    B, Fi, D, O = _euler_shapes(RP, Z, orders, bias_lam, bias_theta)
+    assert OP.is_contiguous() and OP.numel() == Z.numel()
+    assert stats is None or (stats.is_contiguous() and stats.numel() >= 4 * B * O)
+    ln = norms is not None
+    check(_lib.load().fx_euler_fwd(ptr(RP), ptr(Z), B, Fi, D, O, ptr(orders), ptr(bias_lam), ptr(bias_theta),
+                                   1 if ln else 0, *([ptr(t) for t in norms] if ln else [None] * 4), eps,
+                                   ptr(stats) if ln else None, ptr(OP), stream_ptr(RP.device)), "fx_euler_fwd")
+    return OP
+
+
+@_timed("euler_bwd", "euler", lambda *a, **kw: 3.0 * _euler_flops(*a, **kw))     # recompute, da | dt, d orders
+def euler_bwd(RP, Z, orders, bias_lam, bias_theta, norms, eps, stats, dOP, dZ, dRP, d_orders, d_bias, d_norm,
+              workspace):
+    """dZ [2 B, O D], the explicit part of dRP, d_orders [Fi, O], d_bias [2, D, O] (lam | theta) and, with the norm
+    on (norms = (norm_r.weight, norm_p.weight)), d_norm [2, 2, D] (r: weight | bias, p: weight | bias)."""
+    _need_cuda(RP, "RP")
+    B, Fi, D, O = _euler_shapes(RP, Z, orders, bias_lam, bias_theta)
+    ln = norms is not None
+    assert dOP.is_contiguous() and dZ.is_contiguous() and dRP.is_contiguous() and dOP.numel() == dZ.numel() == Z.numel()
+    assert dRP.numel() == RP.numel() and d_orders.is_contiguous() and d_orders.numel() == Fi * O
+    assert d_bias.is_contiguous() and d_bias.numel() == 2 * D * O
+    assert not ln or (d_norm.is_contiguous() and d_norm.numel() == 4 * D and stats.numel() >= 4 * B * O)
+    assert workspace.numel() >= euler_workspace_floats(B, Fi, D, O)
+    check(_lib.load().fx_euler_bwd(ptr(RP), ptr(Z), B, Fi, D, O, ptr(orders), ptr(bias_lam), ptr(bias_theta),
+                                   1 if ln else 0, *([ptr(t) for t in norms] if ln else [None] * 2), eps,
+                                   ptr(stats) if ln else None, ptr(dOP), ptr(dZ), ptr(dRP), ptr(d_orders), ptr(d_bias),
+                                   ptr(d_norm) if ln else None, ptr(workspace), stream_ptr(RP.device)), "fx_euler_bwd")
+    return dZ, dRP
+
+
 # ---- FiBiNET: squeeze-excitation and bilinear interaction -------------------------------------------
 BILINEAR_MAX = 64    # F, D (and the excitation's hidden width) of fx_senet_* / fx_bilinear_*
 BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE and AFN, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN and EulerNet, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -13,7 +13,8 @@ model_zoo/BST/src/BST.py:33-366,
 model_zoo/DIEN/src/DIEN.py:27-503,
 model_zoo/FiGNN/src/FiGNN.py:27-231,
 model_zoo/DESTINE/src/DESTINE.py:37-227,
-model_zoo/AFN/src/AFN.py:25-138), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/AFN/src/AFN.py:25-138,
+model_zoo/EulerNet/src/EulerNet.py:22-170), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -23,7 +24,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
+from .layers import (EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -944,6 +945,46 @@ class AFN(_ZooModel):
             dnn_out = self.dnn(feature_emb2.flatten(start_dim=1))
             y_pred = self.fc(torch.cat([y_pred, dnn_out], dim=-1))
         return {"y_pred": self.output_activation(y_pred)}
+
+
+class EulerNet(_ZooModel):
+    """EulerNet (EulerNet.py:22-98): embeddings in polar form (layers.euler_polar), a stack of
+    layers.EulerInteractionLayer (csrc/fx_euler.hip) on the pair, and one linear head applied to both halves.  As in
+    the reference, `reset_parameters()` runs BEFORE the interaction layers and `reg` exist: their own initialisers
+    (eye / sharpened soft-max orders, xavier-uniform `im`, xavier-normal `reg`) survive."""
+
+    def __init__(self, feature_map, model_id="EulerNet", gpu=-1, shape=[3], learning_rate=1e-3, embedding_dim=10,
+                 net_ex_dropout=0, net_im_dropout=0, layer_norm=False, embedding_regularizer=None,
+                 net_regularizer=None, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        lim = ops.euler_limits()
+        for what, n, most in [("num_fields", feature_map.num_fields, lim["F_max"]),
+                              ("embedding_dim", embedding_dim, lim["D_max"])] \
+                + [("shape[{}]".format(i), n, lim["O_max"]) for i, n in enumerate(shape)]:
+            if not 1 <= n <= most:
+                raise NotImplementedError("EulerNet: {}={}, the fused Euler interaction takes 1 <= {} <= {}"
+                                          .format(what, n, what, most))
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        field_num = feature_map.num_fields
+        shape_list = [embedding_dim * field_num] + [num_neurons * embedding_dim for num_neurons in shape]
+        self.reset_parameters()
+        self.Euler_interaction_layers = nn.Sequential(*[
+            EulerInteractionLayer(inshape, outshape, embedding_dim, layer_norm, net_ex_dropout, net_im_dropout)
+            for inshape, outshape in zip(shape_list[:-1], shape_list[1:])])
+        self.mu = nn.Parameter(torch.ones(1, field_num, 1))
+        self.reg = FxLinear(shape_list[-1], 1, device=self.device)
+        nn.init.xavier_normal_(self.reg.weight)
+        self.compile(kwargs["optimizer"], kwargs["loss"], learning_rate)
+        self.model_to_device()
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        pair = self.Euler_interaction_layers(euler_polar(feature_emb, self.mu))     # [2, B, O, D], or (o_r, o_p)
+        o_r, o_p = pair[0], pair[1]
+        re = self.reg(o_r.reshape(o_r.shape[0], -1))
+        logit = self.reg(o_p.reshape(o_p.shape[0], -1), out_add=re)     # im + re; the bias counts twice
+        return {"y_pred": self.output_activation(logit)}
 
 
 def _flat_len(fields):

@@ -761,6 +761,48 @@ int fx_lognet_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D,
                   float* dbeta1, float* dgamma2, float* dbeta2, float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * EulerNet's Euler interaction layer and polar front end (csrc/fx_euler.hip; EulerInteractionLayer.forward and
+ * EulerNet.forward, model_zoo/EulerNet/src/EulerNet.py:139-170, :90).  A layer's pair is ONE tensor RP [2, B, Fi, D]
+ * (r | p, contiguous), its output OP [2, B, O, D]; Z [2 B, O D] = RP.view(2 B, Fi D) im.weight^T + im.bias is the
+ * caller's GEMM, WITHOUT the ReLU (the kernel applies it; the backward mask is Z > 0):
+ *     a = 0.5 log(r^2 + p^2 + 1e-8),  t = atan2(p, r)
+ *     ul[b, o, d] = sum_f inter_orders[f, o] a[b, f, d] + bias_lam[d, o],  ut likewise from t and bias_theta
+ *     o_r = relu(zr) + exp(ul) cos(ut),  o_p = relu(zp) + exp(ul) sin(ut)
+ *     layer_norm != 0: o_r = LayerNorm_D(o_r; norm_r), o_p = LayerNorm_D(o_p; norm_p), over d within each (b, o)
+ * inter_orders [Fi, O], bias_lam / bias_theta [D, O], the LayerNorm pairs [D] each.  exp / cos / sin are never stored.
+ *   fx_euler_fwd  : one launch.  stats (may be NULL, and is not touched with layer_norm == 0): mean [2, B, O] |
+ *                 rstd [2, B, O] of the groups, for the backward.
+ *   fx_euler_bwd  : from dOP [2, B, O, D]: dZ [2 B, O D] (0 where Z <= 0), the EXPLICIT part of dRP (through a and t;
+ *                 the atan2 terms are exactly 0 at r = p = 0; the caller adds dZ im.weight), d_inter_orders [Fi, O],
+ *                 d_bias [2, D, O] = d bias_lam | d bias_theta, and with layer_norm d_norm [2, 2, D] = d norm_r.weight |
+ *                 d norm_r.bias | d norm_p.weight | d norm_p.bias.  Two kernels and two (with layer_norm three)
+ *                 fixed-order reduces; no atomics.
+ *   fx_euler_polar_fwd : RP [2, B, F, D] = mu[f] (cos E | sin E), E [B, F, D] with sample stride x_ld.  One launch.
+ *   fx_euler_polar_bwd : dE (sample stride de_ld) = mu (-sin E dr + cos E dp), dmu [F] = sum_{b, d} cos E dr + sin E dp.
+ *                 Two launches.
+ *   fx_euler_limits : limits[8] = {most Fi, most D, most O, most columns (b, d) of a workgroup tile, most samples of
+ *                 one, most workgroups of a layer kernel, most slabs of the orders gradient, most chunks of the polar
+ *                 backward}; a shape outside is FX_ERR_INVALID.
+ * workspace: fx_euler_workspace_floats(B, Fi, D, O) floats (0 outside the envelope), for fx_euler_bwd and (with
+ * Fi = F, any O inside the envelope) fx_euler_polar_bwd.
+ * ------------------------------------------------------------------------------------------ */
+void fx_euler_limits(int32_t* limits);
+int64_t fx_euler_workspace_floats(int64_t B, int32_t Fi, int32_t D, int32_t O);
+int fx_euler_polar_fwd(const float* E, int64_t x_ld, const float* mu, int64_t B, int32_t F, int32_t D, float* RP,
+                       fx_stream_t stream);
+int fx_euler_polar_bwd(const float* E, int64_t x_ld, const float* mu, int64_t B, int32_t F, int32_t D,
+                       const float* dRP, float* dE, int64_t de_ld, float* dmu, float* workspace, fx_stream_t stream);
+int fx_euler_fwd(const float* RP, const float* Z, int64_t B, int32_t Fi, int32_t D, int32_t O,
+                 const float* inter_orders, const float* bias_lam, const float* bias_theta, int32_t layer_norm,
+                 const float* norm_r_weight, const float* norm_r_bias, const float* norm_p_weight,
+                 const float* norm_p_bias, float eps, float* stats, float* OP, fx_stream_t stream);
+int fx_euler_bwd(const float* RP, const float* Z, int64_t B, int32_t Fi, int32_t D, int32_t O,
+                 const float* inter_orders, const float* bias_lam, const float* bias_theta, int32_t layer_norm,
+                 const float* norm_r_weight, const float* norm_p_weight, float eps, const float* stats,
+                 const float* dOP, float* dZ, float* dRP, float* d_inter_orders, float* d_bias, float* d_norm,
+                 float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * FiBiNET's squeeze-excitation over the fields of a sample (SqueezeExcitation.forward,
  * fuxictr/pytorch/layers/attentions/squeeze_excitation.py:51-64; its autograd at rank_model.py:320):
  *     Z[b,f] = mean_d X[b,f,d]                      X: [B, F, D] (sample stride x_ld)
