@@ -166,6 +166,12 @@ SIGNATURES = {
     "fx_euler_fwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp]),
     "fx_euler_bwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp,
                            vp, vp]),
+    "fx_sam_limits": (None, [vp]),
+    "fx_sam_workspace_floats": (i64, [i64, i32, i32, i32]),
+    "fx_sam_logit_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "fx_sam_logit_bwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "fx_sam_layer_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "fx_sam_layer_bwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
     "fx_senet_workspace_floats": (i64, [i64, i32, i32]),
     "fx_senet_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
     "fx_senet_bwd": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),

@@ -3369,6 +3369,183 @@ class EulerInteractionLayer(nn.Module):
         return self._native(complex_features)
 
 
+class _SamLogitFn(torch.autograd.Function):
+    """SAM's SAM2A / SAM2E block AND the model's final linear as ONE autograd node (SAM.py:150-204, :88):
+    logit [B, 1] from X [B, F, D], the head's weight [1, F F D] and bias [1] and, with SAM2A, W [F, F, D]; the
+    reference's [B, F, F, D] tensor is never formed (csrc/fx_sam.hip).  Kept for the backward: X and the parameters;
+    S is recomputed.  Forward two launches, backward four."""
+
+    @staticmethod
+    def forward(ctx, X, W, w, bias, kind):
+        if X.stride(2) != 1 or (X.shape[1] > 1 and X.stride(1) != X.shape[2]):
+            X = X.contiguous()
+        B, F, D = X.shape
+        w = w.contiguous()
+        logit = torch.empty(B, 1, dtype=torch.float32, device=X.device)
+        ws = _Workspace.get(X.device, ops.sam_workspace_floats(B, F, D, kind), tag="sam")
+        ops.sam_logit_fwd(X, kind, W, w, bias, logit, ws)
+        ctx.kept, ctx.kind = (X, W, w), kind
+        return logit
+
+    @staticmethod
+    def backward(ctx, dlogit):
+        (X, W, w), kind = ctx.kept, ctx.kind
+        B, F, D = X.shape
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=X.device)    # noqa: E731
+        dX, dw, dbias = new(B, F, D), new(*w.shape), new(1)
+        dW = new(F, F, D) if W is not None else None
+        ws = _Workspace.get(X.device, ops.sam_workspace_floats(B, F, D, kind), tag="sam")
+        ops.sam_logit_bwd(X, kind, W, w, dlogit.contiguous(), dX, dW, dw, dbias, ws)
+        return dX, dW, dw, dbias, None
+
+
+class SAM2A(nn.Module):
+    """SAM's SAM2A layer (model_zoo/SAM/src/SAM.py:150-176): out [B, F, F, D] = S (.) W, S = X X^T.  The module holds
+    the parameter under the reference's name; its forward is the reference's torch formula and serves CPU tensors
+    only: on the GPU the block never forms `out` (SAMBlock.logit)."""
+
+    def __init__(self, num_fields, embedding_dim, dropout=0):
+        super().__init__()
+        self.W = nn.Parameter(torch.ones(num_fields, num_fields, embedding_dim))
+
+    def forward(self, F):
+        S = torch.bmm(F, F.transpose(1, 2))
+        return S.unsqueeze(-1) * self.W
+
+
+class SAM2E(nn.Module):
+    """SAM's SAM2E layer (SAM.py:179-204): out [B, F, F, D] = S (.) U, U[n, m, d] = X[n, d] X[m, d]; no parameters.
+    As SAM2A: the torch formula, for CPU tensors only."""
+
+    def __init__(self, embedding_dim, dropout=0):
+        super().__init__()
+
+    def forward(self, F):
+        S = torch.bmm(F, F.transpose(1, 2))
+        return S.unsqueeze(-1) * torch.einsum("bnd,bmd->bnmd", F, F)
+
+
+class _SamLayerFn(torch.autograd.Function):
+    """One SAM3A / SAM3E layer as ONE autograd node (SAM.py:234-240, :268-275): out [B, F, D] from X [B, F, D], K, Q
+    (None: no residual) and, with SAM3A, W [F, F, D]; neither layer forms [B, F, F, D] (csrc/fx_sam.hip).  Kept for
+    the backward: X and the parameters; KF and S are recomputed."""
+
+    @staticmethod
+    def forward(ctx, X, K, Q, W, kind):
+        if X.stride(2) != 1 or (X.shape[1] > 1 and X.stride(1) != X.shape[2]):
+            X = X.contiguous()
+        B, F, D = X.shape
+        out = torch.empty(B, F, D, dtype=torch.float32, device=X.device)
+        ws = _Workspace.get(X.device, ops.sam_workspace_floats(B, F, D, kind), tag="sam")
+        ops.sam_layer_fwd(X, kind, K, Q, W, out, ws)
+        ctx.kept, ctx.kind = (X, K, Q, W), kind
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (X, K, Q, W), kind = ctx.kept, ctx.kind
+        B, F, D = X.shape
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=X.device)    # noqa: E731
+        dX, dK = new(B, F, D), new(D, D)
+        dQ = new(D, D) if Q is not None else None
+        dW = new(F, F, D) if W is not None else None
+        ws = _Workspace.get(X.device, ops.sam_workspace_floats(B, F, D, kind), tag="sam")
+        ops.sam_layer_bwd(X, kind, K, Q, W, dout.contiguous(), dX, dK, dQ, dW, ws)
+        return dX, dK, dQ, dW, None
+
+
+class _SAM3(nn.Module):
+    """What SAM3A and SAM3E share (SAM.py:207-275): K, the optional residual Q, torch dropout on the layer output; on
+    the GPU one fused node (_SamLayerFn), on CPU tensors the reference's torch ops."""
+
+    def __init__(self, embedding_dim, use_residual, dropout):
+        super().__init__()
+        self.K = nn.Linear(embedding_dim, embedding_dim, bias=False)
+        self.use_residual = use_residual
+        if use_residual:
+            self.Q = nn.Linear(embedding_dim, embedding_dim, bias=False)
+        self.dropout = nn.Dropout(p=dropout) if dropout > 0 else None
+
+    def forward(self, F):
+        if F.is_cuda:
+            out = _SamLayerFn.apply(F, self.K.weight, self.Q.weight if self.use_residual else None,
+                                    getattr(self, "W", None), type(self).__name__)
+        else:
+            S = torch.bmm(F, self.K(F).transpose(1, 2))
+            other = self.W if hasattr(self, "W") else torch.einsum("bnd,bmd->bnmd", F, F)
+            out = (S.unsqueeze(-1) * other).sum(dim=2)
+            if self.use_residual:
+                out = out + self.Q(F)
+        return self.dropout(out) if self.dropout else out
+
+
+class SAM3A(_SAM3):
+    def __init__(self, num_fields, embedding_dim, use_residual=True, dropout=0):
+        super().__init__(embedding_dim, use_residual, dropout)
+        self.W = nn.Parameter(torch.ones(num_fields, num_fields, embedding_dim))
+
+
+class SAM3E(_SAM3):
+    def __init__(self, embedding_dim, use_residual=True, dropout=0):
+        super().__init__(embedding_dim, use_residual, dropout)
+
+
+class SAMBlock(nn.Module):
+    """SAM's interaction block (SAM.py:94-147), the reference's parameter names (`layers.i.W`, `.K.weight`,
+    `.Q.weight`, `weight` for weighted_pooling).  `logit(X, fc)` is the block, the aggregation and the model's final
+    linear: for SAM2A / SAM2E on the GPU one fused pass that writes one float per sample (_SamLogitFn; the
+    [B, F, F, D] tensor is never formed), for SAM3A / SAM3E the fused layers, then the aggregation (a view or torch's
+    pooling) into `fc`.  CPU tensors take the reference's sequence of torch ops.  The reference's asserts stay.  Not
+    native: dropout > 0 with SAM2A / SAM2E (it would act on the tensor that no longer exists)."""
+
+    def __init__(self, num_layers, num_fields, embedding_dim, use_residual=False, interaction_type="SAM2E",
+                 aggregation="concat", dropout=0):
+        super().__init__()
+        assert aggregation in ["concat", "weighted_pooling", "mean_pooling", "sum_pooling"]
+        self.aggregation = aggregation
+        self.interaction_type = interaction_type
+        if interaction_type not in ("SAM2A", "SAM2E", "SAM3A", "SAM3E"):
+            raise ValueError("interaction_type={} not supported.".format(interaction_type))
+        lim = ops.sam_limits()
+        for what, n, most in (("num_fields", num_fields, lim["F_max"]), ("embedding_dim", embedding_dim, lim["D_max"])):
+            if not 1 <= n <= most:
+                raise NotImplementedError("SAM: {}={}, the fused SAM block takes 1 <= {} <= {}"
+                                          .format(what, n, what, most))
+        if self.aggregation == "weighted_pooling":
+            self.weight = nn.Parameter(torch.ones(num_fields, 1))
+        if interaction_type in ("SAM2A", "SAM2E"):
+            assert aggregation == "concat", "Only aggregation=concat is supported for {}.".format(interaction_type)
+            if dropout and dropout > 0:
+                raise NotImplementedError("SAMBlock: net_dropout={} with {} (dropout on the [B, F, F, D] tensor, which "
+                                          "the fused kernel never forms); use 0".format(dropout, interaction_type))
+            self.layers = nn.ModuleList([SAM2A(num_fields, embedding_dim, dropout) if interaction_type == "SAM2A"
+                                         else SAM2E(embedding_dim, dropout)])
+        elif interaction_type == "SAM3A":
+            self.layers = nn.ModuleList([SAM3A(num_fields, embedding_dim, use_residual, dropout)
+                                         for _ in range(num_layers)])
+        else:
+            self.layers = nn.ModuleList([SAM3E(embedding_dim, use_residual, dropout) for _ in range(num_layers)])
+
+    def forward(self, F):
+        if F.is_cuda and self.interaction_type in ("SAM2A", "SAM2E"):
+            raise RuntimeError("SAMBlock: the [B, F, F, D] output is not formed on the GPU; call logit(X, fc)")
+        for layer in self.layers:
+            F = layer(F)
+        if self.aggregation == "concat":
+            return F.flatten(start_dim=1)
+        if self.aggregation == "weighted_pooling":
+            return (F * self.weight).sum(dim=1)
+        return F.mean(dim=1) if self.aggregation == "mean_pooling" else F.sum(dim=1)
+
+    def logit(self, F, fc):
+        """fc(block(F)) [B, 1]."""
+        if F.is_cuda and self.interaction_type in ("SAM2A", "SAM2E"):
+            return _SamLogitFn.apply(F, getattr(self.layers[0], "W", None), fc.weight, fc.bias, self.interaction_type)
+        if not F.is_cuda:
+            return nn.functional.linear(self.forward(F), fc.weight, fc.bias)
+        return fc(self.forward(F))
+
+
 class _SENetFn(torch.autograd.Function):
     """Squeeze-excitation as ONE autograd node (squeeze_excitation.py:51-64): forward one launch, backward
     three.  Kept for the backward: X (a view), the gates A [B, F] and the weights; Z and the hidden layer are

@@ -1273,6 +1273,100 @@ def euler_bwd(RP, Z, orders, bias_lam, bias_theta, norms, eps, stats, dOP, dZ, d
     return dZ, dRP
 
 
+# ---- SAM's SAM2A / SAM2E block with the final linear folded in (csrc/fx_sam.hip) ---------------------
+SAM_TYPES = {"SAM2A": 0, "SAM2E": 1, "SAM3A": 2, "SAM3E": 3}
+
+
+def sam_limits():
+    """The native envelope of sam_logit_fwd / sam_logit_bwd, stated once in the library.  workgroups: the most a main
+    pass launches; tile_samples: the most samples of a workgroup tile."""
+    lim = (C.c_int32 * 6)()
+    _lib.load().fx_sam_limits(lim)
+    return dict(zip(("F_max", "D_max", "workgroups", "tile_samples", "slabs", "slab_rows"), (int(v) for v in lim)))
+
+
+def _sam_flops(X, *a, **kw):
+    B, F, D = X.shape
+    return 4.0 * B * F * F * D
+
+
+def sam_workspace_floats(B, F, D, kind):
+    return int(_lib.load().fx_sam_workspace_floats(B, F, D, SAM_TYPES[kind]))
+
+
+def _sam_shapes(X, kind, W, w):
+    B, F, D = X.shape
+    assert w.is_contiguous() and w.numel() == F * F * D
+    assert (kind == "SAM2A") == (W is not None) and (W is None or (W.is_contiguous() and W.numel() == F * F * D))
+    return B, F, D
+
+
+@_timed("sam_logit_fwd", "sam", _sam_flops)
+def sam_logit_fwd(X, kind, W, w, bias, logit, workspace):
+    """logit [B] = fc(SAM2A / SAM2E block of X [B, F, D] (sample stride free)), w = fc.weight (F F D floats), bias =
+    fc.bias; W [F, F, D] with kind "SAM2A", None with "SAM2E"."""
+    _need_cuda(X, "X")
+    B, F, D = _sam_shapes(X, kind, W, w)
+    assert logit.is_contiguous() and logit.numel() == B and bias.numel() == 1
+    assert workspace.numel() >= sam_workspace_floats(B, F, D, kind)
+    check(_lib.load().fx_sam_logit_fwd(ptr(X), _mhsa_x(X), B, F, D, SAM_TYPES[kind], ptr(W), ptr(w), ptr(bias),
+                                       ptr(logit), ptr(workspace), stream_ptr(X.device)), "fx_sam_logit_fwd")
+    return logit
+
+
+@_timed("sam_logit_bwd", "sam", lambda *a, **kw: 3.0 * _sam_flops(*a, **kw))      # recompute, dX, the parameter gradients
+def sam_logit_bwd(X, kind, W, w, dlogit, dX, dW, dw, dbias, workspace, dx_accumulate=False):
+    """dX [B, F, D] (sample stride free; added to when dx_accumulate), dw (F F D floats), dbias (1 float) and with
+    "SAM2A" dW [F, F, D], from dlogit [B]."""
+    _need_cuda(X, "X")
+    B, F, D = _sam_shapes(X, kind, W, w)
+    assert dlogit.is_contiguous() and dlogit.numel() == B and dbias.numel() == 1
+    assert dw.is_contiguous() and dw.numel() == w.numel() and tuple(dX.shape) == (B, F, D)
+    assert (W is None) == (dW is None) and (dW is None or (dW.is_contiguous() and dW.numel() == W.numel()))
+    assert workspace.numel() >= sam_workspace_floats(B, F, D, kind)
+    check(_lib.load().fx_sam_logit_bwd(ptr(X), _mhsa_x(X), B, F, D, SAM_TYPES[kind], ptr(W), ptr(w), ptr(dlogit),
+                                       ptr(dX), _mhsa_x(dX), 1 if dx_accumulate else 0, ptr(dW), ptr(dw), ptr(dbias),
+                                       ptr(workspace), stream_ptr(X.device)), "fx_sam_logit_bwd")
+    return dX, dw
+
+
+def _sam_layer_shapes(X, kind, K, Q, W):
+    B, F, D = X.shape
+    assert K.is_contiguous() and tuple(K.shape) == (D, D) and (Q is None or (Q.is_contiguous() and Q.shape == K.shape))
+    assert (kind == "SAM3A") == (W is not None) and (W is None or (W.is_contiguous() and W.numel() == F * F * D))
+    return B, F, D
+
+
+@_timed("sam_layer_fwd", "sam", lambda X, *a, **kw: 2.0 * X.shape[0] * X.shape[1] * X.shape[2] * (2 * X.shape[1] + 2 * X.shape[2]))
+def sam_layer_fwd(X, kind, K, Q, W, out, workspace):
+    """One SAM3A / SAM3E layer: out [B, F, D] contiguous from X [B, F, D] (sample stride free); K, Q (None: no
+    residual) [D, D], W [F, F, D] with "SAM3A"."""
+    _need_cuda(X, "X")
+    B, F, D = _sam_layer_shapes(X, kind, K, Q, W)
+    assert out.is_contiguous() and out.numel() == B * F * D
+    assert workspace.numel() >= sam_workspace_floats(B, F, D, kind)
+    check(_lib.load().fx_sam_layer_fwd(ptr(X), _mhsa_x(X), B, F, D, SAM_TYPES[kind], ptr(K), ptr(Q), ptr(W), ptr(out),
+                                       ptr(workspace), stream_ptr(X.device)), "fx_sam_layer_fwd")
+    return out
+
+
+@_timed("sam_layer_bwd", "sam", lambda X, *a, **kw: 6.0 * X.shape[0] * X.shape[1] * X.shape[2] * (2 * X.shape[1] + 2 * X.shape[2]))
+def sam_layer_bwd(X, kind, K, Q, W, dout, dX, dK, dQ, dW, workspace, dx_accumulate=False):
+    """dX [B, F, D] (sample stride free; added to when dx_accumulate), dK, dQ (with Q) and with "SAM3A" dW, from
+    dout [B, F, D] contiguous."""
+    _need_cuda(X, "X")
+    B, F, D = _sam_layer_shapes(X, kind, K, Q, W)
+    assert dout.is_contiguous() and dout.numel() == B * F * D and tuple(dX.shape) == (B, F, D)
+    assert dK.is_contiguous() and dK.numel() == D * D and (Q is None or (dQ.is_contiguous() and dQ.numel() == D * D))
+    assert (W is None) == (dW is None) and (dW is None or (dW.is_contiguous() and dW.numel() == W.numel()))
+    assert workspace.numel() >= sam_workspace_floats(B, F, D, kind)
+    check(_lib.load().fx_sam_layer_bwd(ptr(X), _mhsa_x(X), B, F, D, SAM_TYPES[kind], ptr(K), ptr(Q), ptr(W), ptr(dout),
+                                       ptr(dX), _mhsa_x(dX), 1 if dx_accumulate else 0, ptr(dK),
+                                       ptr(dQ) if Q is not None else None, ptr(dW), ptr(workspace),
+                                       stream_ptr(X.device)), "fx_sam_layer_bwd")
+    return dX
+
+
 # ---- FiBiNET: squeeze-excitation and bilinear interaction -------------------------------------------
 BILINEAR_MAX = 64    # F, D (and the excitation's hidden width) of fx_senet_* / fx_bilinear_*
 BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN and EulerNet, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN, EulerNet and SAM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -14,7 +14,8 @@ model_zoo/DIEN/src/DIEN.py:27-503,
 model_zoo/FiGNN/src/FiGNN.py:27-231,
 model_zoo/DESTINE/src/DESTINE.py:37-227,
 model_zoo/AFN/src/AFN.py:25-138,
-model_zoo/EulerNet/src/EulerNet.py:22-170), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/EulerNet/src/EulerNet.py:22-170,
+model_zoo/SAM/src/SAM.py:23-204), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -24,7 +25,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
+from .layers import (SAMBlock, EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -985,6 +986,35 @@ class EulerNet(_ZooModel):
         re = self.reg(o_r.reshape(o_r.shape[0], -1))
         logit = self.reg(o_p.reshape(o_p.shape[0], -1), out_add=re)     # im + re; the bias counts twice
         return {"y_pred": self.output_activation(logit)}
+
+
+class SAM(_ZooModel):
+    """SAM (SAM.py:23-91).  SAM2A / SAM2E (the reference's default and the configs it ships): the block, the flatten and
+    `fc` are one fused pass that writes one float per sample; SAM3A / SAM3E: a stack of fused layers, the aggregation,
+    then `fc` (layers.SAMBlock.logit, csrc/fx_sam.hip).  `fc` has the reference's in_features per variant.  Outside the
+    envelope, a non-concat aggregation with SAM2A / SAM2E (the reference's own assert) and net_dropout > 0 with them
+    raise in the block."""
+
+    def __init__(self, feature_map, model_id="SAM", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 interaction_type="SAM2E", aggregation="concat", num_interaction_layers=3, use_residual=False,
+                 embedding_regularizer=None, net_regularizer=None, net_dropout=0, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.block = SAMBlock(num_interaction_layers, feature_map.num_fields, embedding_dim, use_residual,
+                              interaction_type, aggregation, net_dropout)
+        if aggregation != "concat":
+            width = embedding_dim
+        elif interaction_type in ("SAM2A", "SAM2E"):
+            width = embedding_dim * feature_map.num_fields ** 2
+        else:
+            width = feature_map.num_fields * embedding_dim
+        self.fc = FxLinear(width, 1, device=self.device)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feature_emb = self.embedding_layer(X)               # [B, F, D]
+        return {"y_pred": self.output_activation(self.block.logit(feature_emb, self.fc))}
 
 
 def _flat_len(fields):

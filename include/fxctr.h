@@ -803,6 +803,48 @@ int fx_euler_bwd(const float* RP, const float* Z, int64_t B, int32_t Fi, int32_t
                  float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SAM's self-attentive interaction block SAM2A / SAM2E WITH the model's final linear folded in (csrc/fx_sam.hip;
+ * SAM2A.forward, SAM2E.forward and SAM.forward, model_zoo/SAM/src/SAM.py:150-204, :88).  X [B, F, D] with sample stride
+ * x_ld, S_b = X_b X_b^T, w = fc.weight viewed [F, F, D], bias = fc.bias [1]; type 0 = SAM2A (W [F, F, D]), 1 = SAM2E
+ * (W unused, may be NULL):
+ *     SAM2A: logit_b = sum_{n, m, d} S_b[n, m] W[n, m, d] w[n, m, d] + bias
+ *     SAM2E: logit_b = sum_{n, m, d} S_b[n, m] X_b[n, d] X_b[m, d] w[n, m, d] + bias
+ * The reference's [B, F, F, D] tensor is never formed; logit [B] is all that leaves the forward.
+ *   fx_sam_logit_fwd : two launches (the symmetric parts of W . w or of w into workspace, then the main pass).
+ *   fx_sam_logit_bwd : from dlogit [B]: dX [B, F, D] (sample stride dx_ld; added to when dx_accumulate), dw [F, F, D],
+ *                 dbias [1] and with SAM2A dW [F, F, D] (NULL with SAM2E).  The forward is recomputed from X.  Four
+ *                 launches; fixed-order reduces, no atomics.
+ *   fx_sam_limits : limits[6] = {most F, most D, most workgroups of a main pass, most samples of a workgroup tile, most
+ *                 batch slabs of SAM3A's dW, samples of one slab at the least}; a shape outside is FX_ERR_INVALID.
+ * workspace: fx_sam_workspace_floats(B, F, D, type) floats (0 outside the envelope), for both directions:
+ *     SAM2A: up4(F F) + (min(ceil(B / ST), workgroups) + 1) up4(256 T + 1), T = t (t + 1) / 2, t = ceil(F / 16)
+ *     SAM2E: 2 up4(F F D) + up4(B F F) + 4 (min(ceil(B / ST), workgroups) + 1)
+ *     SAM3A: up4(B F F) + min(B, workgroups) up4(2 D D) + (slabs > 1 ? slabs F F D : 0), slabs = min(ceil(B / 256), 8)
+ *     SAM3E: min(B, workgroups) up4(2 D D)
+ * with ST the backward's samples per tile (LDS permitting, at most limits[3]) and up4 rounding up to 4.
+ *
+ * The stackable layers SAM3A (type 2) and SAM3E (type 3), SAM.py:207-275: X [B, F, D] -> out [B, F, D] contiguous,
+ *     KF = X K^T,  S = X KF^T,  out = sum_m S[n, m] W[n, m, :] (SAM3A) | X (.) (S X) (SAM3E), + X Q^T when Q != NULL
+ * K, Q [D, D] (nn.Linear weights), W [F, F, D] (SAM3A; NULL with SAM3E).
+ *   fx_sam_layer_fwd : one launch; SAM3A two (S [B, F, F] to workspace, then a per-field GEMM against W).
+ *   fx_sam_layer_bwd : from dout [B, F, D]: dX (sample stride dx_ld; added to when dx_accumulate), dK, dQ (with Q) and
+ *                 with SAM3A dW.  The forward is recomputed from X.  SAM3E: the layer pass and one reduce; SAM3A adds the
+ *                 per-field GEMMs for dS (before) and dW (after, K = B in at most limits[4] slabs) and their reduce.
+ * ------------------------------------------------------------------------------------------ */
+void fx_sam_limits(int32_t* limits);
+int64_t fx_sam_workspace_floats(int64_t B, int32_t F, int32_t D, int32_t type);
+int fx_sam_logit_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, int32_t type, const float* W,
+                     const float* w, const float* bias, float* logit, float* workspace, fx_stream_t stream);
+int fx_sam_logit_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, int32_t type, const float* W,
+                     const float* w, const float* dlogit, float* dX, int64_t dx_ld, int32_t dx_accumulate, float* dW,
+                     float* dw, float* dbias, float* workspace, fx_stream_t stream);
+int fx_sam_layer_fwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, int32_t type, const float* K,
+                     const float* Q, const float* W, float* out, float* workspace, fx_stream_t stream);
+int fx_sam_layer_bwd(const float* X, int64_t x_ld, int64_t B, int32_t F, int32_t D, int32_t type, const float* K,
+                     const float* Q, const float* W, const float* dout, float* dX, int64_t dx_ld, int32_t dx_accumulate,
+                     float* dK, float* dQ, float* dW, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * FiBiNET's squeeze-excitation over the fields of a sample (SqueezeExcitation.forward,
  * fuxictr/pytorch/layers/attentions/squeeze_excitation.py:51-64; its autograd at rank_model.py:320):
  *     Z[b,f] = mean_d X[b,f,d]                      X: [B, F, D] (sample stride x_ld)
