@@ -204,6 +204,10 @@ SIGNATURES = {
     "fx_afm_attn_workspace_floats": (i64, [i64, i32, i32, i32]),
     "fx_afm_attn_fwd": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "fx_afm_attn_bwd": (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp]),
+    "fx_ffm_limits": (None, [vp]),
+    "fx_ffm_tile_rows": (i32, [i32, i32, i32]),
+    "fx_ffm_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, i64, vp]),
+    "fx_ffm_bwd": (i32, [vp, i64, vp, i64, i64, i32, i32, i32, vp, i64, vp]),
     "fx_pairfm_limits": (None, [vp]),
     "fx_pairfm_tile_rows": (i32, [i32, i32, i32]),
     "fx_pairfm_workspace_floats": (i64, [i32, i64, i32, i32]),

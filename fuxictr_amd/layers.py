@@ -4533,6 +4533,59 @@ def pair_interaction_native(F, D, mode):
     return mode in ops.PAIRFM_MODES and ops.pairfm_in_envelope(F, D)
 
 
+def field_aware_composition(emb, F, D, mode, addend=None):
+    """The field-aware interaction tensor by tensor in torch (FFMv2.py:71-73, :87-91; ONNv2.py:88-92, :107-109), any
+    device and dtype: emb [B, F, C * D] -> "onn" [B, F * D + P] = [own vectors | pair terms], "ffm" [B, 1]."""
+    B = emb.shape[0]
+    E = emb.reshape(B, F, ops.ffm_slots(mode, F), D)
+    i, j = torch.triu_indices(F, F, offset=1, device=emb.device)
+    if mode == "onn":
+        own = torch.arange(F, device=emb.device)
+        pairs = (E[:, i, j, :] * E[:, j, i, :]).sum(dim=-1)
+        return torch.cat([E[:, own, own, :].reshape(B, F * D), pairs], dim=1)
+    out = (E[:, i, j - 1, :] * E[:, j, i, :]).sum(dim=-1).sum(dim=-1, keepdim=True)
+    return out if addend is None else out + addend
+
+
+class _FieldAwareFn(torch.autograd.Function):
+    """The field-aware interaction of FFMv2 / ONNv2 as ONE autograd node over the gather record [B, F, C * D]: forward
+    one launch (ops.ffm_fwd), backward one launch (ops.ffm_bwd).  Kept for the backward: the record (a view, no copy);
+    nothing per pair exists and nothing is recomputed.  addend ("ffm"): [B, 1] or None; its gradient is dout."""
+
+    @staticmethod
+    def forward(ctx, emb, F, D, mode, addend):
+        rows = _field_rows(emb)
+        B = rows.shape[0]
+        out = _empty(B, ops.ffm_out_floats(mode, F, D), device=emb.device)
+        if addend is not None:
+            addend = addend.contiguous()
+        ops.ffm_fwd(rows, F, D, mode, addend, out)
+        ctx.rows, ctx.cfg, ctx.shape, ctx.has_add = rows, (F, D, mode), emb.shape, addend is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        F, D, mode = ctx.cfg
+        dx = _empty(*ctx.shape, device=g.device)
+        g = g.contiguous().view(-1).view(g.shape)          # (a [B, 1] gradient: unit strides, whatever it came with)
+        ops.ffm_bwd(g, ctx.rows, F, D, mode, dx.view(ctx.shape[0], -1))
+        return dx, None, None, None, (g if ctx.has_add else None)
+
+
+def field_aware_interaction(emb, F, D, mode, addend=None):
+    """The node behind zoo.FFMv2 / zoo.ONNv2.  emb: the wide embedding [B, F, C * D], C = F ("onn": ONNv2, -> the DNN's
+    input [B, F * D + P]) or F - 1 ("ffm": FFMv2, -> [B, 1], addend = lr_layer(X) [B, 1]).  CUDA tensors take the
+    kernel (a shape outside field_aware_native() is the library's error: no fall-back), CPU tensors the torch
+    composition."""
+    if emb.is_cuda:
+        return _FieldAwareFn.apply(emb, F, D, mode, addend)
+    return field_aware_composition(emb, F, D, mode, addend)
+
+
+def field_aware_native(F, D, mode):
+    return ops.ffm_in_envelope(mode, F, D)
+
+
 class _BSTBlockFn(torch.autograd.Function):
     """One transformer block of BST (BST.py:345-366, with the pooling of BST.py:209-229 behind the last one) as ONE
     autograd node: forward one launch (ops.bst_block_fwd), backward one launch and the fixed-order reduce of the

@@ -1858,6 +1858,79 @@ def pairfm_bwd(g, rec, F, D, mode, W, wlin, has_bias, drec, grads, workspace):
     return drec, grads
 
 
+# ---- FFMv2 / ONNv2: the field-aware interaction (csrc/fx_ffm.hip) ---------------------------------------
+FFM_MODES = {"onn": 0, "ffm": 1}
+
+
+def ffm_limits():
+    """The native envelope of ffm_fwd / ffm_bwd, stated once in the library: F_min <= F <= F_max, C * D <= CD_max (the
+    gather's row width; C = F slots with "onn", F - 1 with "ffm").  workgroups: the most a launch starts;
+    tile_samples: the most samples of a workgroup's tile."""
+    lim = (C.c_int32 * 5)()
+    _lib.load().fx_ffm_limits(lim)
+    return dict(zip(("F_min", "F_max", "CD_max", "workgroups", "tile_samples"), (int(v) for v in lim)))
+
+
+def ffm_slots(mode, F):
+    """Vectors a field keeps: one per field with "onn" (its own included), one per OTHER field with "ffm"."""
+    assert mode in FFM_MODES, mode
+    return F if mode == "onn" else F - 1
+
+
+def ffm_out_floats(mode, F, D):
+    """Floats of a sample's output row: the F own vectors and the P pair terms with "onn", the one sum with "ffm"."""
+    return F * D + F * (F - 1) // 2 if mode == "onn" else 1
+
+
+def ffm_in_envelope(mode, F, D):
+    lim = ffm_limits()
+    return mode in FFM_MODES and lim["F_min"] <= F <= lim["F_max"] and D >= 1 and \
+        ffm_slots(mode, F) * D <= lim["CD_max"]
+
+
+def ffm_tile_rows(mode, F, D):
+    """Samples one workgroup owns at a time (what fits the LDS); 0 outside the envelope."""
+    return int(_lib.load().fx_ffm_tile_rows(FFM_MODES[mode], F, D))
+
+
+def _ffm_flops(rec, F, D, mode, *a, **kw):
+    return 2.0 * rec.shape[0] * (F * (F - 1) // 2) * D
+
+
+def _ffm_check(rec, F, D, mode):
+    _need_cuda(rec, "rec")
+    assert mode in FFM_MODES, mode
+    assert rec.dim() == 2 and rec.shape[1] == F * ffm_slots(mode, F) * D and rec.stride(1) == 1
+    assert rec.dtype == torch.float32
+    return rec.shape[0]
+
+
+@_timed("ffm_fwd", "ffm", _ffm_flops)
+def ffm_fwd(rec, F, D, mode, addend, out):
+    """rec [B, F * C * D] (unit column stride, any row stride) viewed as E[b, i, c, :].  "onn": out [B, F * D + P] (own
+    row stride) = [E[b, i, i, :] for every i | <E[b, i, j], E[b, j, i]> for the pairs i < j in triu order]; "ffm":
+    out [B, 1] = sum over the pairs of <E[b, i, j - 1], E[b, j, i]> (+ addend [B, 1]).  A shape outside ffm_limits() is
+    the library's invalid-argument error."""
+    B = _ffm_check(rec, F, D, mode)
+    assert tuple(out.shape) == (B, ffm_out_floats(mode, F, D)) and out.stride(1) == 1 and out.dtype == torch.float32
+    assert addend is None or (mode == "ffm" and addend.numel() == B and addend.is_contiguous())
+    check(_lib.load().fx_ffm_fwd(ptr(rec), _rows(rec), B, F, D, FFM_MODES[mode], ptr(addend), ptr(out), _rows(out),
+                                 stream_ptr(rec.device)), "fx_ffm_fwd")
+    return out
+
+
+@_timed("ffm_bwd", "ffm", _ffm_flops)
+def ffm_bwd(g, rec, F, D, mode, drec):
+    """From g = dout ("onn" [B, F * D + P], "ffm" [B, 1]; own row stride): every element of drec [B, F * C * D] (own row
+    stride), each from its one contributor.  The addend's gradient is g."""
+    B = _ffm_check(rec, F, D, mode)
+    assert tuple(g.shape) == (B, ffm_out_floats(mode, F, D)) and g.stride(1) == 1 and g.dtype == torch.float32
+    assert tuple(drec.shape) == tuple(rec.shape) and drec.stride(1) == 1 and drec.dtype == torch.float32
+    check(_lib.load().fx_ffm_bwd(ptr(g), _rows(g), ptr(rec), _rows(rec), B, F, D, FFM_MODES[mode], ptr(drec),
+                                 _rows(drec), stream_ptr(rec.device)), "fx_ffm_bwd")
+    return drec
+
+
 # ---- BST: one fused transformer block over the positions of a sample --------------------------------
 BST_MAX = 64         # L1 = history + target positions, and dm of fx_bst_block_*
 BST_MAX_PARTS = 3

@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN, EulerNet and SAM, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN, EulerNet, SAM, FFMv2 and ONNv2, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -15,7 +15,8 @@ model_zoo/FiGNN/src/FiGNN.py:27-231,
 model_zoo/DESTINE/src/DESTINE.py:37-227,
 model_zoo/AFN/src/AFN.py:25-138,
 model_zoo/EulerNet/src/EulerNet.py:22-170,
-model_zoo/SAM/src/SAM.py:23-204), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/SAM/src/SAM.py:23-204,
+model_zoo/FFM/src/FFMv2.py:24-91, model_zoo/ONN/ONN_torch/src/ONNv2.py:25-109), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -25,7 +26,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (SAMBlock, EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
+from .layers import (field_aware_composition, field_aware_interaction, field_aware_native, SAMBlock, EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -764,6 +765,76 @@ class FmFM(_ZooModel):
         y_pred = (left_emb * right_emb).sum(dim=-1).sum(dim=-1, keepdim=True)
         y_pred = y_pred + self.lr_layer(X)
         return {"y_pred": self.output_activation(y_pred)}
+
+
+def _field_aware_width(name, mode, num_fields, embedding_dim):
+    """The row width of the one wide table of FFMv2 / ONNv2; wider than the gather and the fused kernel take: raise,
+    these models have no other route."""
+    width = embedding_dim * ops.ffm_slots(mode, num_fields)
+    most = ops.ffm_limits()["CD_max"]
+    if width > most or not field_aware_native(num_fields, embedding_dim, mode):
+        raise NotImplementedError("{}: embedding_dim * {} = {} floats per table row, the limit of the embedding gather "
+                                  "and of the fused field-aware interaction is {} (and {} <= num_fields <= {})"
+                                  .format(name, "num_fields" if mode == "onn" else "(num_fields - 1)", width, most,
+                                          ops.ffm_limits()["F_min"], ops.ffm_limits()["F_max"]))
+    return width
+
+
+class FFMv2(_ZooModel):
+    """Field-aware Factorization Machine, the one-table form (FFMv2.py:24-91): a field keeps a vector per OTHER field
+    in one FeatureEmbedding of width embedding_dim * (F - 1); the sum of the pair terms and `+ lr_layer(X)` are one
+    fused launch per direction (layers.field_aware_interaction, csrc/fx_ffm.hip)."""
+
+    def __init__(self, feature_map, model_id="FFMv2", gpu=-1, learning_rate=1e-3, embedding_dim=2, regularizer=None,
+                 **kwargs):
+        self._base(feature_map, model_id, gpu, regularizer, regularizer, kwargs)      # one keyword feeds both
+        self.num_fields = feature_map.num_fields
+        self.embedding_dim = embedding_dim
+        width = _field_aware_width("FFMv2", "ffm", self.num_fields, embedding_dim)
+        self.lr_layer = LogisticRegression(feature_map, use_bias=True)
+        self.embedding_layer = FeatureEmbedding(feature_map, width)
+        # (the reference's triu_mask / tril_mask are plain attributes, not state: the slot rule lives in the kernel)
+        # fused=False: the torch composition tensor by tensor on the same device: the same numbers
+        self._fused = self._fused_flag(kwargs, "FX_FFM_FUSED")
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        lr_out = self.lr_layer(X)
+        emb = self.embedding_layer(X)                       # [B, F, (F - 1) * D]
+        mix = field_aware_interaction if self._fused else field_aware_composition
+        y_pred = mix(emb, self.num_fields, self.embedding_dim, "ffm", addend=lr_out)
+        return {"y_pred": self.output_activation(y_pred)}
+
+
+class ONNv2(_ZooModel):
+    """Operation-aware Neural Network, the one-table form, also NFFM / DeepFFM (ONNv2.py:25-109): a field keeps a
+    vector per field in one FeatureEmbedding of width embedding_dim * F; its own vectors and the F (F - 1) / 2 pair
+    terms feed the DNN.  The fused node writes the DNN's input row in one launch (layers.field_aware_interaction,
+    csrc/fx_ffm.hip): no masked_select, no transposed copy, no cat."""
+
+    def __init__(self, feature_map, model_id="ONNv2", gpu=-1, learning_rate=1e-3, embedding_dim=2,
+                 embedding_regularizer=None, net_regularizer=None, hidden_units=[64, 64, 64],
+                 hidden_activations="ReLU", net_dropout=0, batch_norm=False, **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.num_fields = feature_map.num_fields
+        self.embedding_dim = embedding_dim
+        self.interact_units = int(self.num_fields * (self.num_fields - 1) / 2)
+        width = _field_aware_width("ONNv2", "onn", self.num_fields, embedding_dim)
+        self.dnn = self._tower(embedding_dim * self.num_fields + self.interact_units, hidden_units,
+                               hidden_activations, net_dropout, batch_norm)
+        self.embedding_layer = FeatureEmbedding(feature_map, width)
+        self.diag_mask = torch.eye(self.num_fields).bool().to(self.device)         # plain attributes, as the
+        self.triu_mask = torch.triu(torch.ones(self.num_fields, self.num_fields), 1).bool().to(self.device)  # reference's
+        self._fused = self._fused_flag(kwargs, "FX_FFM_FUSED")
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        emb = self.embedding_layer(X)                       # [B, F, F * D]
+        mix = field_aware_interaction if self._fused else field_aware_composition
+        dnn_input = mix(emb, self.num_fields, self.embedding_dim, "onn")           # [B, F * D + P]
+        return {"y_pred": self.output_activation(self.dnn(dnn_input))}
 
 
 class BST(_ZooModel):

@@ -1088,6 +1088,37 @@ int fx_pairfm_bwd(const float* g, const float* X, int64_t ldx, int64_t B, int32_
                   float* workspace, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FFMv2 / ONNv2 (csrc/fx_ffm.hip): the field-aware interaction fused over the gather record X [B, F*C*D] (row stride
+ * ldx floats), viewed as E[b, i, c, :]: field i keeps one D-vector per partner field, slot c.  Pairs p = (i, j),
+ * i < j, in the row-major upper-triangle order (the triu_mask selects of both models).
+ *   mode 0 ONN: C = F, the slot of partner j is j, slot i of field i is the field's own vector
+ *               (model_zoo/ONN/ONN_torch/src/ONNv2.py:88-92 and ffm_interaction, ONNv2.py:107-109):
+ *                   out[b] = [E[b,0,0,:] .. E[b,F-1,F-1,:] | <E[b,i,j,:], E[b,j,i,:]> for every p]   [F*D + P] floats
+ *               at row stride ldo: the DNN's input, without the masked_select, the transposed copy and the cat.
+ *   mode 1 FFM: C = F - 1, in field i the slot of partner j is j - 1 for j > i and j for j < i
+ *               (model_zoo/FFM/src/FFMv2.py:71-73 and ffm_interaction, FFMv2.py:87-91):
+ *                   out[b] = sum_p <E[b,i,j-1,:], E[b,j,i,:]>  (+ addend[b], nullable: lr_layer(X))   one float per
+ *               sample, at row stride ldo (>= 1).
+ *   fx_ffm_fwd : one launch.  The dot runs in the order d = 0 .. D-1; the FFM sum of a sample over its pairs in a
+ *                fixed order.  addend must be NULL in ONN mode.
+ *   fx_ffm_bwd : from g (ONN: [B, F*D + P], FFM: [B, 1]; row stride ldg) one launch writes every element of
+ *                dX [B, F*C*D] (row stride lddx) once: dX[b,i,s(j),:] = g_p E[b,j,s(i),:] (FFM: g_p = g[b]) and in ONN
+ *                mode dX[b,i,i,:] = g[b, i*D : (i+1)*D].  Needs X only; the addend's gradient is g.
+ *   A workgroup owns a tile of whole samples in LDS (fx_ffm_tile_rows).  No atomics: two runs give the same bits.
+ *   fp32.  16-byte accesses of X and dX when F*C*D % 4 == 0 and base pointers and row strides are 16-byte aligned,
+ *   4-byte otherwise.
+ *   fx_ffm_limits : limits[5] = {least F, most F, most C*D (the gather's row width), most workgroups of a launch,
+ *                most samples of a tile} (housekeeping); a shape outside is refused with FX_ERR_INVALID.
+ *   fx_ffm_tile_rows : samples one workgroup owns at a time, 0 outside the envelope (housekeeping).
+ * ------------------------------------------------------------------------------------------ */
+void fx_ffm_limits(int32_t* limits);
+int32_t fx_ffm_tile_rows(int32_t mode, int32_t F, int32_t D);
+int fx_ffm_fwd(const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t mode, const float* addend,
+               float* out, int64_t ldo, fx_stream_t stream);
+int fx_ffm_bwd(const float* g, int64_t ldg, const float* X, int64_t ldx, int64_t B, int32_t F, int32_t D, int32_t mode,
+               float* dX, int64_t lddx, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A sample's column parts (new functionality: the layout BST and DIEN below share).  A behaviour history of width
  * n_parts * D per position is n_parts column parts of D floats; so is the target item.  Each part is a view (of the
  * gather record, say) with strides of its own, read in place:
