@@ -208,6 +208,12 @@ SIGNATURES = {
     "fx_ffm_tile_rows": (i32, [i32, i32, i32]),
     "fx_ffm_fwd": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, i64, vp]),
     "fx_ffm_bwd": (i32, [vp, i64, vp, i64, i64, i32, i32, i32, vp, i64, vp]),
+    "fx_gin_limits": (None, [vp]),
+    "fx_gin_tile_rows": (i32, [i32, i32, i32, i32]),
+    "fx_gin_param_floats": (i64, [i32, i32, i32, i32]),
+    "fx_gin_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
+    "fx_gin_fwd": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp]),
+    "fx_gin_bwd": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp]),
     "fx_pairfm_limits": (None, [vp]),
     "fx_pairfm_tile_rows": (i32, [i32, i32, i32]),
     "fx_pairfm_workspace_floats": (i64, [i32, i64, i32, i32]),

@@ -4586,6 +4586,86 @@ def field_aware_native(F, D, mode):
     return ops.ffm_in_envelope(mode, F, D)
 
 
+def generalized_interaction_composition(B_0, B_i, W, alpha, h):
+    """One generalized-interaction layer (AOANet.py:155-171) without the reference's outer_product [B, S * F, D, D],
+    in torch ops on any device and dtype.  With n = s * F + f (its two repeats) and Wh[o, h, d] = W[o, h, d] h[o, d]:
+    out[b, o, h] = sum_s P[b, o, s, h] Q[b, o, s, h], P = sum_d Wh B_i[b, s, d], Q = sum_f alpha[s F + f, o] B_0[b, f, h]."""
+    F, S, O = B_0.shape[1], B_i.shape[1], W.shape[0]
+    P = torch.einsum("ohd,bsd->bosh", W * h.view(O, 1, -1), B_i)
+    Q = torch.einsum("sfo,bfh->bosh", alpha.view(S, F, O), B_0)
+    return (P * Q).sum(dim=2)
+
+
+class _GinFn(torch.autograd.Function):
+    """The whole generalized-interaction stack as ONE autograd node (AOANet.py:122-134; csrc/fx_gin.hip): out [B, O, D]
+    from B_0 [B, F, D] and the packed parameters of the L layers.  Kept for the backward: B_0 (a view, no copy), the
+    parameters and every layer's output [L, B, O, D]; P and Q are recomputed.  Forward one launch, backward two."""
+
+    @staticmethod
+    def forward(ctx, B_0, params, O, L):
+        B_0 = _field_view(B_0)
+        B, F, D = B_0.shape
+        outs = _empty(L, B, O, D, device=B_0.device)
+        ops.gin_fwd(B_0, O, L, params, outs)
+        ctx.kept, ctx.cfg = (B_0, params, outs), (O, L)
+        return outs[L - 1]
+
+    @staticmethod
+    def backward(ctx, dout):
+        (B_0, params, outs), (O, L) = ctx.kept, ctx.cfg
+        B, F, D = B_0.shape
+        dB_0, dparams = _empty(B, F, D, device=B_0.device), torch.empty_like(params)
+        ws = _Workspace.get(B_0.device, ops.gin_workspace_floats(B, F, D, O, L), tag="gin")
+        ops.gin_bwd(dout.contiguous(), B_0, O, L, params, outs, dB_0, dparams, ws)
+        return dB_0, dparams, None, None
+
+
+class GeneralizedInteraction(nn.Module):
+    """AOANet's GeneralizedInteraction layer (AOANet.py:137-171): the reference's parameter names, shapes and initial
+    values (W eye, alpha and h ones).  Its own forward is the factorised torch formula; on the GPU the stack runs as a
+    whole (GeneralizedInteractionNet)."""
+
+    def __init__(self, input_subspaces, output_subspaces, num_fields, embedding_dim):
+        super().__init__()
+        self.input_subspaces = input_subspaces
+        self.num_fields = num_fields
+        self.embedding_dim = embedding_dim
+        self.W = nn.Parameter(torch.eye(embedding_dim, embedding_dim).unsqueeze(0).repeat(output_subspaces, 1, 1))
+        self.alpha = nn.Parameter(torch.ones(input_subspaces * num_fields, output_subspaces))
+        self.h = nn.Parameter(torch.ones(output_subspaces, embedding_dim, 1))
+
+    def forward(self, B_0, B_i):
+        return generalized_interaction_composition(B_0, B_i, self.W, self.alpha, self.h)
+
+
+class GeneralizedInteractionNet(nn.Module):
+    """AOANet's interaction stack (AOANet.py:105-134), parameters `layers.<i>.W / alpha / h`.  CUDA tensors take the
+    fused stack (_GinFn; the layers' parameters travel as one packed buffer, one torch.cat per step), unless
+    fused=False: then, and on CPU tensors, the layers run the factorised formula in torch ops, one after the other."""
+
+    def __init__(self, num_layers, num_subspaces, num_fields, embedding_dim, fused=True):
+        super().__init__()
+        lim = ops.gin_limits()
+        for what, n, most in (("num_fields", num_fields, lim["F_max"]), ("embedding_dim", embedding_dim, lim["D_max"]),
+                              ("num_subspaces", num_subspaces, lim["O_max"]),
+                              ("num_interaction_layers", num_layers, lim["L_max"])):
+            if not 1 <= n <= most:
+                raise NotImplementedError("AOANet: {}={}, the fused generalized interaction takes 1 <= {} <= {}"
+                                          .format(what, n, what, most))
+        self.num_subspaces, self.fused = num_subspaces, fused
+        self.layers = nn.ModuleList([GeneralizedInteraction(num_fields if i == 0 else num_subspaces, num_subspaces,
+                                                            num_fields, embedding_dim) for i in range(num_layers)])
+
+    def forward(self, B_0):
+        if B_0.is_cuda and self.fused:
+            params = torch.cat([p.reshape(-1) for layer in self.layers for p in (layer.W, layer.alpha, layer.h)])
+            return _GinFn.apply(B_0, params, self.num_subspaces, len(self.layers))
+        B_i = B_0
+        for layer in self.layers:
+            B_i = layer(B_0, B_i)
+        return B_i
+
+
 class _BSTBlockFn(torch.autograd.Function):
     """One transformer block of BST (BST.py:345-366, with the pooling of BST.py:209-229 behind the last one) as ONE
     autograd node: forward one launch (ops.bst_block_fwd), backward one launch and the fixed-order reduce of the

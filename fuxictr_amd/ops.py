@@ -1931,6 +1931,63 @@ def ffm_bwd(g, rec, F, D, mode, drec):
     return drec
 
 
+# ---- AOANet: the generalized-interaction stack (csrc/fx_gin.hip) -------------------------------------
+def gin_limits():
+    """The native envelope of gin_fwd / gin_bwd, stated once in the library: 1 <= F <= F_max, D <= D_max, num_subspaces
+    <= O_max, layers <= L_max.  workgroups: the most a launch starts; tile_samples: the most samples of a tile."""
+    lim = (C.c_int32 * 6)()
+    _lib.load().fx_gin_limits(lim)
+    return dict(zip(("F_max", "D_max", "O_max", "L_max", "workgroups", "tile_samples"), (int(v) for v in lim)))
+
+
+def gin_param_floats(F, D, O, L):
+    """Floats of the packed parameters [W [O, D, D] | alpha [S * F, O] | h [O, D]] per layer, S = F, then O."""
+    return int(_lib.load().fx_gin_param_floats(F, D, O, L))
+
+
+def gin_workspace_floats(B, F, D, O, L):
+    return int(_lib.load().fx_gin_workspace_floats(B, F, D, O, L))
+
+
+def _gin_flops(B0, O, L, *a, **kw):
+    # per sample, layer and (o, s): P over d and Q over f, one row of h each
+    B, F, D = B0.shape
+    return 2.0 * B * O * D * (D + F) * (F + (L - 1) * O)
+
+
+def _gin_check(B0, O, L, params, outs):
+    _need_cuda(B0, "B0")
+    B, F, D = B0.shape
+    assert params.is_contiguous() and params.numel() == gin_param_floats(F, D, O, L) and params.dtype == torch.float32
+    assert outs.is_contiguous() and tuple(outs.shape) == (L, B, O, D) and outs.dtype == torch.float32
+    return B, F, D
+
+
+@_timed("gin_fwd", "gin", _gin_flops)
+def gin_fwd(B0, O, L, params, outs):
+    """The stack of L generalized-interaction layers over B0 [B, F, D] (sample stride free): outs [L, B, O, D] gets
+    every layer's output, outs[L - 1] is the result.  params: the packed parameters (gin_param_floats).  One launch."""
+    B, F, D = _gin_check(B0, O, L, params, outs)
+    check(_lib.load().fx_gin_fwd(ptr(B0), _mhsa_x(B0), B, F, D, O, L, ptr(params), ptr(outs), stream_ptr(B0.device)),
+          "fx_gin_fwd")
+    return outs
+
+
+@_timed("gin_bwd", "gin", lambda dout, *a, **kw: 3.0 * _gin_flops(*a[:3]))      # recompute, dB, the parameter gradients
+def gin_bwd(dout, B0, O, L, params, outs, dB0, dparams, workspace, dx_accumulate=False):
+    """From dout [B, O, D] and the forward's outs: dB0 [B, F, D] (sample stride free; added to when dx_accumulate) and
+    dparams, in the layout of params.  Two launches: the stack in reverse, and the fixed-order sum of the workgroups'
+    partial rows."""
+    B, F, D = _gin_check(B0, O, L, params, outs)
+    assert dout.is_contiguous() and tuple(dout.shape) == (B, O, D) and tuple(dB0.shape) == (B, F, D)
+    assert dparams.is_contiguous() and dparams.numel() == params.numel()
+    assert workspace.numel() >= gin_workspace_floats(B, F, D, O, L)
+    check(_lib.load().fx_gin_bwd(ptr(dout), ptr(B0), _mhsa_x(B0), B, F, D, O, L, ptr(params), ptr(outs), ptr(dB0),
+                                 _mhsa_x(dB0), 1 if dx_accumulate else 0, ptr(dparams), ptr(workspace),
+                                 stream_ptr(B0.device)), "fx_gin_bwd")
+    return dB0, dparams
+
+
 # ---- BST: one fused transformer block over the positions of a sample --------------------------------
 BST_MAX = 64         # L1 = history + target positions, and dm of fx_bst_block_*
 BST_MAX_PARTS = 3

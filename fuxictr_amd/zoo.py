@@ -1,5 +1,5 @@
 """The callers of the hot path that BASELINE.json's configs name — DeepFM, DCNv2, DIN, DLRM, xDeepFM —
-and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN, EulerNet, SAM, FFMv2 and ONNv2, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
+and AutoInt, FiBiNET, MaskNet, FinalMLP, DualMLP, GDCN, GDCNP, AFM, DCN, FwFM, FmFM, BST, DIEN, FiGNN, DESTINE, AFN, EulerNet, SAM, FFMv2, ONNv2 and AOANet, on the native drop-in layers.  Constructor keywords, attribute (= state_dict) names and the forward
 composition are the reference's (model_zoo/DeepFM/DeepFM_torch/src/DeepFM.py:41-88,
 model_zoo/DCNv2/src/DCNv2.py:44-132, model_zoo/DIN/src/DIN.py:50-150, model_zoo/DLRM/src/DLRM.py:44-124,
 model_zoo/xDeepFM/src/xDeepFM.py:41-97, model_zoo/AutoInt/src/AutoInt.py:49-119,
@@ -16,7 +16,8 @@ model_zoo/DESTINE/src/DESTINE.py:37-227,
 model_zoo/AFN/src/AFN.py:25-138,
 model_zoo/EulerNet/src/EulerNet.py:22-170,
 model_zoo/SAM/src/SAM.py:23-204,
-model_zoo/FFM/src/FFMv2.py:24-91, model_zoo/ONN/ONN_torch/src/ONNv2.py:25-109), so its checkpoints and YAML configs apply unchanged.  These
+model_zoo/FFM/src/FFMv2.py:24-91, model_zoo/ONN/ONN_torch/src/ONNv2.py:25-109,
+model_zoo/AOANet/src/AOANet.py:24-171), so its checkpoints and YAML configs apply unchanged.  These
 classes exist because /root/reference does not travel to the GPU box; with the reference installed,
 its own model_zoo classes run unmodified on the same layers through `fuxictr_amd.patch.install()`
 (INTEGRATION.md, tests/test_dropin_reference_zoo.py).
@@ -26,7 +27,7 @@ import os as _os
 import torch
 from torch import nn
 
-from .layers import (field_aware_composition, field_aware_interaction, field_aware_native, SAMBlock, EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
+from .layers import (GeneralizedInteractionNet, field_aware_composition, field_aware_interaction, field_aware_native, SAMBlock, EulerInteractionLayer, euler_polar, AttentionLayer, AttentionalPrediction, BehaviorTransformer, FiGNN_Layer, DynamicGRU, GRU, MaskedSumPooling, BilinearInteractionV2, CompressedInteractionNet, CrossNet, CrossNetMix, CrossNetV2, DIN_Attention, Dice, DisentangledSelfAttention,
                      FactorizationMachine, FeatureEmbedding, FeatureEmbeddingDict, FeatureSelection, FieldLayerNorm,
                      FxLinear, GateCrossLayer, InnerProductInteraction, InteractionAggregation, LogisticRegression, MLP_Block, MultiHeadSelfAttention,
                      ParallelMaskNet, SerialMaskNet, SqueezeExcitation, _DlrmMixFn, _FiBiNETMixFn, _RecordGradSlot, din_record_layout,
@@ -1086,6 +1087,33 @@ class SAM(_ZooModel):
         X = self.get_inputs(inputs)
         feature_emb = self.embedding_layer(X)               # [B, F, D]
         return {"y_pred": self.output_activation(self.block.logit(feature_emb, self.fc))}
+
+
+class AOANet(_ZooModel):
+    """AOANet (AOANet.py:24-102): a deep tower next to the generalized-interaction stack `gin`
+    (layers.GeneralizedInteractionNet: one fused launch per direction for all its layers, csrc/fx_gin.hip); `fc` reads
+    [dnn_out | gin_out].  The two halves are joined by torch.cat: side_by_side writes [cross | deep], the other order.
+    fused=False / FX_GIN_FUSED=0 runs the stack's factorised formula in torch ops on the same device."""
+
+    def __init__(self, feature_map, model_id="AOANet", gpu=-1, learning_rate=1e-3, embedding_dim=10,
+                 dnn_hidden_units=[64, 64, 64], dnn_hidden_activations="ReLU", num_interaction_layers=3,
+                 num_subspaces=4, net_dropout=0, batch_norm=False, embedding_regularizer=None, net_regularizer=None,
+                 **kwargs):
+        self._base(feature_map, model_id, gpu, embedding_regularizer, net_regularizer, kwargs)
+        self.embedding_layer = FeatureEmbedding(feature_map, embedding_dim)
+        self.dnn = self._tower(feature_map.sum_emb_out_dim(), dnn_hidden_units, dnn_hidden_activations, net_dropout,
+                               batch_norm, output_dim=None)
+        self.gin = GeneralizedInteractionNet(num_interaction_layers, num_subspaces, feature_map.num_fields,
+                                             embedding_dim, fused=self._fused_flag(kwargs, "FX_GIN_FUSED"))
+        self.fc = FxLinear(dnn_hidden_units[-1] + num_subspaces * embedding_dim, 1, device=self.device)
+        self._ready(kwargs, learning_rate)
+
+    def forward(self, inputs):
+        X = self.get_inputs(inputs)
+        feat_emb = self.embedding_layer(X)                  # [B, F, D]
+        dnn_out = self.dnn(feat_emb.flatten(start_dim=1))
+        interact_out = self.gin(feat_emb).flatten(start_dim=1)
+        return {"y_pred": self.output_activation(self.fc(torch.cat([dnn_out, interact_out], dim=-1)))}
 
 
 def _flat_len(fields):

@@ -1119,6 +1119,38 @@ int fx_ffm_bwd(const float* g, int64_t ldg, const float* X, int64_t ldx, int64_t
                float* dX, int64_t lddx, fx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AOANet (csrc/fx_gin.hip): the whole GeneralizedInteractionNet stack (model_zoo/AOANet/src/AOANet.py:105-134) of L
+ * GeneralizedInteraction layers (AOANet.py:137-171) over B_0 [B, F, D] (sample stride ldb floats, >= F*D), O =
+ * num_subspaces.  The reference forms outer_product [B, S*F, D, D] per layer (AOANet.py:165-167, n = s*F + f after its
+ * two repeats); the kernels never do.  With S = F for layer 0 and O after it, and Wh[o,h,d] = W[o,h,d] h[o,d]:
+ *     P[b,o,s,h] = sum_d Wh[o,h,d] B_i[b,s,d]      Q[b,o,s,h] = sum_f alpha[s*F+f, o] B_0[b,f,h]
+ *     out[b,o,h] = sum_s P[b,o,s,h] Q[b,o,s,h]                                        (AOANet.py:168-170)
+ *   params : ONE packed buffer, layer after layer [W [O,D,D] | alpha [S*F, O] | h [O,D]] (the reference's W, alpha
+ *            and h, AOANet.py:151-153); dparams has the same layout.  fx_gin_param_floats gives its length.
+ *   fx_gin_fwd : one launch.  outs [L, B, O, D] contiguous receives EVERY layer's output (the backward needs them);
+ *            slab L-1 is the result.  B_i moves from layer to layer through LDS.
+ *   fx_gin_bwd : one launch runs the stack in reverse from dout [B, O, D] (contiguous), recomputing P and Q from outs
+ *            and B_0, and writes dB0 [B, F, D] (sample stride lddb; added to when dx_accumulate) once per sample; a
+ *            workgroup accumulates its weight gradients in its own row of workspace, and one fx_rowsum launch adds the
+ *            rows in a fixed order into dparams.  No atomics: two runs give the same bits.
+ *   fx_gin_workspace_floats : floats of workspace for fx_gin_bwd (the forward needs none), 0 outside the envelope.
+ *   fx_gin_limits : limits[6] = {most F, most D, most O, most L, most workgroups of a launch, most samples of a
+ *            workgroup tile} (housekeeping); a shape outside is refused with FX_ERR_INVALID before the device is touched.
+ *   fx_gin_tile_rows : samples one workgroup owns at a time in the forward (bwd = 0) or the backward (bwd = 1), 0
+ *            outside the envelope (housekeeping).
+ *   fp32, every product on v_mfma_f32_16x16x4_f32, every sum in a fixed order.
+ * ------------------------------------------------------------------------------------------ */
+void fx_gin_limits(int32_t* limits);
+int32_t fx_gin_tile_rows(int32_t F, int32_t D, int32_t O, int32_t bwd);
+int64_t fx_gin_param_floats(int32_t F, int32_t D, int32_t O, int32_t L);
+int64_t fx_gin_workspace_floats(int64_t B, int32_t F, int32_t D, int32_t O, int32_t L);
+int fx_gin_fwd(const float* B0, int64_t ldb, int64_t B, int32_t F, int32_t D, int32_t O, int32_t L,
+               const float* params, float* outs, fx_stream_t stream);
+int fx_gin_bwd(const float* dout, const float* B0, int64_t ldb, int64_t B, int32_t F, int32_t D, int32_t O, int32_t L,
+               const float* params, const float* outs, float* dB0, int64_t lddb, int32_t dx_accumulate,
+               float* dparams, float* workspace, fx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A sample's column parts (new functionality: the layout BST and DIEN below share).  A behaviour history of width
  * n_parts * D per position is n_parts column parts of D floats; so is the target item.  Each part is a view (of the
  * gather record, say) with strides of its own, read in place:
